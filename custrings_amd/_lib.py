@@ -124,6 +124,21 @@ _PROTOS = {
     "cs_contains_re": (i32, [vp, vp, vp, i32, vp, P(i64)]),
     "cs_match_re": (i32, [vp, vp, vp, i32, vp, P(i64)]),
     "cs_count_re": (i32, [vp, vp, vp, i32, vp, P(i64)]),
+    # conversions (convert.cu)
+    "cs_hash": (i32, [vp, vp, i32, vp, P(i64)]),
+    "cs_stoi": (i32, [vp, vp, i32, vp, P(i64)]),
+    "cs_stol": (i32, [vp, vp, i32, vp, P(i64)]),
+    "cs_stof": (i32, [vp, vp, i32, vp, P(i64)]),
+    "cs_stod": (i32, [vp, vp, i32, vp, P(i64)]),
+    "cs_htoi": (i32, [vp, vp, i32, vp, P(i64)]),
+    "cs_ip2int": (i32, [vp, vp, i32, vp, P(i64)]),
+    "cs_to_bools": (i32, [vp, cp, vp, i32, vp, P(i64)]),
+    "cs_itos": (i32, [vp, i64, vp, i32, vp, P(vp)]),
+    "cs_ltos": (i32, [vp, i64, vp, i32, vp, P(vp)]),
+    "cs_ftos": (i32, [vp, i64, vp, i32, vp, P(vp)]),
+    "cs_dtos": (i32, [vp, i64, vp, i32, vp, P(vp)]),
+    "cs_int2ip": (i32, [vp, i64, vp, i32, vp, P(vp)]),
+    "cs_from_bools": (i32, [vp, i64, cp, cp, vp, i32, vp, P(vp)]),
     "cs_replace_re": (i32, [vp, vp, cp, i32, vp, P(vp)]),
     "cs_replace_with_backrefs": (i32, [vp, vp, cp, vp, P(vp)]),
     "cs_extract": (i32, [vp, vp, vp, P(P(vp)), P(i32)]),

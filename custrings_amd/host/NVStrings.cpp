@@ -467,3 +467,87 @@ int NVStrings::count_re(const char* pattern, int* results, bool devmem) {
   check(cs_count_re(m_col, re.h, results, devmem ? 1 : 0, nullptr, &n));
   return (int)n;
 }
+
+// ---- conversions (convert.cu) --------------------------------------------------------------------------------------
+// Parse members: the count of non-zero results, -1 for an empty instance or no output array (convert.cu:36-38).
+int NVStrings::stoi(int* results, bool devmem) {
+  int64_t n = -1;
+  check(cs_stoi(m_col, reinterpret_cast<int32_t*>(results), devmem ? 1 : 0, nullptr, &n));
+  return (int)n;
+}
+int NVStrings::stol(long* results, bool devmem) {
+  static_assert(sizeof(long) == sizeof(int64_t), "long is 64-bit on the supported hosts");
+  int64_t n = -1;
+  check(cs_stol(m_col, reinterpret_cast<int64_t*>(results), devmem ? 1 : 0, nullptr, &n));
+  return (int)n;
+}
+int NVStrings::htoi(unsigned int* results, bool devmem) {
+  int64_t n = -1;
+  check(cs_htoi(m_col, reinterpret_cast<uint32_t*>(results), devmem ? 1 : 0, nullptr, &n));
+  return (int)n;
+}
+int NVStrings::stof(float* results, bool devmem) {
+  int64_t n = -1;
+  check(cs_stof(m_col, results, devmem ? 1 : 0, nullptr, &n));
+  return (int)n;
+}
+int NVStrings::stod(double* results, bool devmem) {
+  int64_t n = -1;
+  check(cs_stod(m_col, results, devmem ? 1 : 0, nullptr, &n));
+  return (int)n;
+}
+int NVStrings::hash(unsigned int* results, bool devmem) {
+  int64_t n = -1;
+  check(cs_hash(m_col, reinterpret_cast<uint32_t*>(results), devmem ? 1 : 0, nullptr, &n));
+  return (int)n;
+}
+int NVStrings::ip2int(unsigned int* results, bool devmem) {
+  int64_t n = -1;
+  check(cs_ip2int(m_col, reinterpret_cast<uint32_t*>(results), devmem ? 1 : 0, nullptr, &n));
+  return (int)n;
+}
+// convert.cu:878-925: rows minus falses, nulls counting as false
+int NVStrings::to_bools(bool* results, const char* true_string, bool devmem) {
+  static_assert(sizeof(bool) == 1, "bool results are one byte");
+  int64_t n = -1;
+  check(cs_to_bools(m_col, true_string, reinterpret_cast<uint8_t*>(results), devmem ? 1 : 0, nullptr, &n));
+  return (int)n;
+}
+// Format members: std::invalid_argument on values == nullptr or count == 0 (convert.cu:258-260).
+NVStrings* NVStrings::itos(const int* values, unsigned int count, const unsigned char* nullbitmask, bool devmem) {
+  ensure_device();
+  cs_column* c = nullptr;
+  check(cs_itos(reinterpret_cast<const int32_t*>(values), count, nullbitmask, devmem ? 1 : 0, nullptr, &c));
+  return adopt(c);
+}
+NVStrings* NVStrings::ltos(const long* values, unsigned int count, const unsigned char* nullbitmask, bool devmem) {
+  ensure_device();
+  cs_column* c = nullptr;
+  check(cs_ltos(reinterpret_cast<const int64_t*>(values), count, nullbitmask, devmem ? 1 : 0, nullptr, &c));
+  return adopt(c);
+}
+NVStrings* NVStrings::ftos(const float* values, unsigned int count, const unsigned char* nullbitmask, bool devmem) {
+  ensure_device();
+  cs_column* c = nullptr;
+  check(cs_ftos(values, count, nullbitmask, devmem ? 1 : 0, nullptr, &c));
+  return adopt(c);
+}
+NVStrings* NVStrings::dtos(const double* values, unsigned int count, const unsigned char* nullbitmask, bool devmem) {
+  ensure_device();
+  cs_column* c = nullptr;
+  check(cs_dtos(values, count, nullbitmask, devmem ? 1 : 0, nullptr, &c));
+  return adopt(c);
+}
+NVStrings* NVStrings::int2ip(const unsigned int* values, unsigned int count, const unsigned char* nullbitmask, bool devmem) {
+  ensure_device();
+  cs_column* c = nullptr;
+  check(cs_int2ip(reinterpret_cast<const uint32_t*>(values), count, nullbitmask, devmem ? 1 : 0, nullptr, &c));
+  return adopt(c);
+}
+NVStrings* NVStrings::create_from_bools(const bool* values, unsigned int count, const char* true_string, const char* false_string,
+                                        const unsigned char* nullbitmask, bool devmem) {
+  ensure_device();
+  cs_column* c = nullptr;
+  check(cs_from_bools(reinterpret_cast<const uint8_t*>(values), count, true_string, false_string, nullbitmask, devmem ? 1 : 0, nullptr, &c));
+  return adopt(c);
+}

@@ -3,6 +3,8 @@
 #include "pyni_common.h"
 #include "nvstrings/ipc_transfer.h"
 #include <cstring>
+#include <memory>
+#include <type_traits>
 
 using namespace pyni;
 
@@ -523,6 +525,155 @@ static PyObject* n_device_memory(PyObject*, PyObject* args) { return PyLong_From
 
 static PyObject* n_dropWrapper(PyObject*, PyObject* args) { return drop_wrapper<NVStrings>(args); }
 
+// ---- conversions (pystrings.cpp:451-880, 1047-1440; convert.cu) ----------------------------------------------------------
+// (self, devptr): the results go to the device pointer when one is given; else a host list with None for the null rows
+// (pystrings.cpp:1088-1128).  An empty instance gives an empty list.
+template <class T, class Call, class Py>
+static PyObject* conv_results(PyObject* args, int devarg, Call&& call, Py&& to_py) {
+  NVStrings* s = SELF(args);
+  const unsigned int count = s->size();
+  if (count == 0) return PyList_New(0);
+  T* devptr = ptr_arg<T>(args, devarg);
+  if (devptr) {
+    if (!guarded([&] { call(s, devptr, true); })) return nullptr;
+    return PyLong_FromVoidPtr(devptr);
+  }
+  std::unique_ptr<T[]> host(new T[count]);  // (not a vector: vector<bool> has no data())
+  if (!guarded([&] { call(s, host.get(), false); })) return nullptr;
+  std::vector<unsigned char> nulls((count + 7) / 8, 0);
+  unsigned int ncount = 0;
+  if (!guarded([&] { ncount = s->set_null_bitarray(nulls.data(), false, false); })) return nullptr;
+  PyObject* ret = PyList_New(count);
+  for (unsigned int i = 0; i < count; ++i) {
+    if (ncount && !((nulls[i / 8] >> (i % 8)) & 1)) {
+      Py_INCREF(Py_None);
+      PyList_SetItem(ret, i, Py_None);
+    } else {
+      PyList_SetItem(ret, i, to_py(host[i]));
+    }
+  }
+  return ret;
+}
+static PyObject* py_long(long v) { return PyLong_FromLong(v); }
+static PyObject* py_ulong(unsigned long v) { return PyLong_FromUnsignedLong(v); }
+static PyObject* n_hash(PyObject*, PyObject* args) {
+  return conv_results<unsigned int>(args, 1, [](NVStrings* s, unsigned int* o, bool d) { s->hash(o, d); }, py_ulong);
+}
+static PyObject* n_stoi(PyObject*, PyObject* args) {
+  return conv_results<int>(args, 1, [](NVStrings* s, int* o, bool d) { s->stoi(o, d); }, py_long);
+}
+static PyObject* n_stol(PyObject*, PyObject* args) {
+  return conv_results<long>(args, 1, [](NVStrings* s, long* o, bool d) { s->stol(o, d); }, py_long);
+}
+static PyObject* n_stof(PyObject*, PyObject* args) {
+  return conv_results<float>(args, 1, [](NVStrings* s, float* o, bool d) { s->stof(o, d); }, [](float v) { return PyFloat_FromDouble((double)v); });
+}
+static PyObject* n_stod(PyObject*, PyObject* args) {
+  return conv_results<double>(args, 1, [](NVStrings* s, double* o, bool d) { s->stod(o, d); }, [](double v) { return PyFloat_FromDouble(v); });
+}
+static PyObject* n_htoi(PyObject*, PyObject* args) {
+  return conv_results<unsigned int>(args, 1, [](NVStrings* s, unsigned int* o, bool d) { s->htoi(o, d); }, py_ulong);
+}
+static PyObject* n_ip2int(PyObject*, PyObject* args) {
+  return conv_results<unsigned int>(args, 1, [](NVStrings* s, unsigned int* o, bool d) { s->ip2int(o, d); }, py_ulong);
+}
+static PyObject* n_to_bools(PyObject*, PyObject* args) {  // (self, true, devptr)
+  const char* t = str_arg(args, 1);
+  return conv_results<bool>(args, 2, [t](NVStrings* s, bool* o, bool d) { s->to_bools(o, t, d); }, [](bool v) { return PyBool_FromLong(v); });
+}
+
+// (values, count, nulls, bdevmem): values / nulls are a list, a host buffer or an address (device memory when bdevmem,
+// as the reference's DataBuffer has it); `count` is needed for an address only.
+template <class T>
+struct Values {
+  std::unique_ptr<T[]> own;  // (not a vector: vector<bool> has no data())
+  Py_buffer view{};
+  bool has_view = false;
+  const T* data = nullptr;
+  size_t count = 0;
+  const char* error = nullptr;
+  explicit Values(PyObject* o) {
+    if (o == Py_None) {
+      error = "values required";
+    } else if (PyList_Check(o)) {
+      count = (size_t)PyList_Size(o);
+      own.reset(new T[count ? count : 1]);
+      for (size_t i = 0; i < count; ++i) {
+        PyObject* e = PyList_GetItem(o, (Py_ssize_t)i);
+        if (e == Py_None) own[i] = T(0);
+        else if (std::is_floating_point<T>::value) own[i] = T(PyFloat_AsDouble(e));
+        else if (PyBool_Check(e)) own[i] = T(e == Py_True);
+        else own[i] = T(PyLong_AsLongLong(e));
+      }
+      if (PyErr_Occurred()) {
+        PyErr_Clear();
+        error = "values must be numbers";
+      }
+      data = own.get();
+    } else if (PyLong_Check(o)) {
+      data = static_cast<const T*>(PyLong_AsVoidPtr(o));
+    } else if (PyObject_CheckBuffer(o) && PyObject_GetBuffer(o, &view, PyBUF_FORMAT | PyBUF_ND | PyBUF_C_CONTIGUOUS) == 0) {
+      has_view = true;
+      if ((size_t)view.itemsize != sizeof(T)) {
+        error = "values are not of the expected width";
+      } else {
+        data = static_cast<const T*>(view.buf);
+        count = (size_t)view.len / sizeof(T);
+      }
+    } else {
+      PyErr_Clear();
+      error = "values must be a list, a buffer or a memory address";
+    }
+  }
+  ~Values() {
+    if (has_view) PyBuffer_Release(&view);
+  }
+};
+template <class T, class Make>
+static PyObject* from_values(PyObject* args, const char* what, int nulls_arg, int dev_arg, Make&& make) {
+  Values<T> vals(arg(args, 0));
+  if (vals.error) {
+    PyErr_Format(PyExc_TypeError, "nvstrings.%s(): %s", what, vals.error);
+    return nullptr;
+  }
+  unsigned int count = (unsigned int)vals.count;
+  if (count == 0) count = (unsigned int)int_arg(args, 1, 0);
+  Values<unsigned char> nulls(arg(args, nulls_arg));
+  if (arg(args, nulls_arg) != Py_None && nulls.error) {
+    PyErr_Format(PyExc_TypeError, "nvstrings.%s(): nulls: %s", what, nulls.error);
+    return nullptr;
+  }
+  const bool dev = bool_arg(args, dev_arg);
+  return make_instance([&] { return make(vals.data, count, arg(args, nulls_arg) == Py_None ? nullptr : nulls.data, dev); });
+}
+static PyObject* n_createFromInt32s(PyObject*, PyObject* args) {
+  return from_values<int>(args, "itos", 2, 3, [](const int* v, unsigned n, const unsigned char* m, bool d) { return NVStrings::itos(v, n, m, d); });
+}
+static PyObject* n_createFromInt64s(PyObject*, PyObject* args) {
+  return from_values<long>(args, "ltos", 2, 3, [](const long* v, unsigned n, const unsigned char* m, bool d) { return NVStrings::ltos(v, n, m, d); });
+}
+static PyObject* n_createFromFloat32s(PyObject*, PyObject* args) {
+  return from_values<float>(args, "ftos", 2, 3, [](const float* v, unsigned n, const unsigned char* m, bool d) { return NVStrings::ftos(v, n, m, d); });
+}
+static PyObject* n_createFromFloat64s(PyObject*, PyObject* args) {
+  return from_values<double>(args, "dtos", 2, 3, [](const double* v, unsigned n, const unsigned char* m, bool d) { return NVStrings::dtos(v, n, m, d); });
+}
+static PyObject* n_createFromIPv4Integers(PyObject*, PyObject* args) {
+  return from_values<unsigned int>(args, "int2ip", 2, 3,
+                                   [](const unsigned int* v, unsigned n, const unsigned char* m, bool d) { return NVStrings::int2ip(v, n, m, d); });
+}
+static PyObject* n_createFromBools(PyObject*, PyObject* args) {  // (values, count, nulls, true, false, bdevmem)
+  if (arg(args, 3) == Py_None || arg(args, 4) == Py_None) {
+    PyErr_SetString(PyExc_ValueError, "nvstrings.from_bools(): true and false must not be null");
+    return nullptr;
+  }
+  const char* t = str_arg(args, 3);
+  const char* f = str_arg(args, 4);
+  return from_values<bool>(args, "from_bools", 2, 5, [t, f](const bool* v, unsigned n, const unsigned char* m, bool d) {
+    return NVStrings::create_from_bools(v, n, t, f, m, d);
+  });
+}
+
 static PyMethodDef s_Methods[] = {
 #define M(n) {#n, n, METH_VARARGS, ""}
     M(n_dropWrapper), M(n_getIPCData), M(n_createFromIPC),
@@ -532,6 +683,8 @@ static PyMethodDef s_Methods[] = {
     M(n_rstrip), M(n_lower), M(n_upper), M(n_find), M(n_rfind), M(n_find_from), M(n_find_multiple), M(n_compare), M(n_match_strings), M(n_startswith), M(n_endswith), M(n_contains), M(n_match), M(n_count), M(n_findall), M(n_findall_record), M(n_extract),
     M(n_extract_record), M(n_sort), M(n_order), M(n_gather), M(n_sublist), M(n_scatter), M(n_scalar_scatter), M(n_remove_strings),
     M(n_add_strings), M(n_cat), M(n_join), M(n_device_memory),
+    M(n_hash), M(n_stoi), M(n_stol), M(n_stof), M(n_stod), M(n_htoi), M(n_ip2int), M(n_to_bools), M(n_createFromInt32s),
+    M(n_createFromInt64s), M(n_createFromFloat32s), M(n_createFromFloat64s), M(n_createFromIPv4Integers), M(n_createFromBools),
 #undef M
     {NULL, NULL, 0, NULL}};
 static struct PyModuleDef s_Module = {PyModuleDef_HEAD_INIT, "pyniNVStrings", "CPython glue of nvstrings over the MI355X back-end", -1, s_Methods};

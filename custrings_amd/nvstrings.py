@@ -13,7 +13,8 @@ import numpy as np
 from . import _lib
 from ._lib import lib, check, b, addr
 
-__all__ = ["to_device", "from_strings", "from_offsets", "free", "bind_cpointer", "create_from_ipc", "nvstrings"]
+__all__ = ["to_device", "from_strings", "from_offsets", "free", "bind_cpointer", "create_from_ipc", "nvstrings",
+           "itos", "ltos", "ftos", "dtos", "int2ip", "from_booleans"]
 
 
 def to_device(strs):
@@ -108,13 +109,84 @@ def bind_cpointer(cptr, own=True):
 
 
 _NOT_BUILT = (
-    "compare hash stoi stol stof stod htoi to_booleans ip2int timestamp2int "
+    "compare timestamp2int "
     "get repeat pad ljust center rjust zfill wrap slice slice_from "
     "slice_replace insert fillna capitalize swapcase title index rindex "
     "find_from rfind match_strings startswith endswith isalnum "
     "isalpha isdigit isspace isdecimal isnumeric islower isupper is_empty translate "
     "find_multiple url_encode url_decode get_ipc_data"
 ).split()
+
+
+# ---- numbers / booleans -> strings (nvstrings.py:153-340; convert.cu) ---------------------------------------------------
+def _values(values, count, dtype, bdevmem):
+    """values argument of the format functions -> (address, count, keepalive): a list or numpy array on the host, or
+    (bdevmem=True) a device address / torch tensor; `count` is needed for a bare address."""
+    if isinstance(values, int):
+        return values, int(count), None
+    if hasattr(values, "data_ptr"):
+        return values.data_ptr(), int(count) or values.numel(), values
+    if bdevmem:
+        raise ValueError("bdevmem=True needs a device address or a device tensor")
+    if isinstance(values, (list, tuple)):
+        values = [0 if v is None else v for v in values]
+    a = np.ascontiguousarray(values, dtype=dtype)
+    return a.ctypes.data, int(count) or len(a), a
+
+
+def _nulls(nulls):
+    """the Arrow validity bitmask (bit = 1 valid, LSB first): list of bytes, numpy array, address or tensor."""
+    if nulls is None:
+        return None, None
+    if isinstance(nulls, int):
+        return nulls, None
+    if hasattr(nulls, "data_ptr"):
+        return nulls.data_ptr(), nulls
+    a = np.ascontiguousarray(nulls, dtype=np.uint8)
+    return a.ctypes.data, a
+
+
+def _format(fn, values, count, nulls, bdevmem, dtype):
+    _lib.ensure_init()
+    pv, n, k1 = _values(values, count, dtype, bdevmem)
+    pn, k2 = _nulls(nulls)
+    out = C.c_void_p()
+    check(fn(pv, n, pn, 1 if bdevmem else 0, None, C.byref(out)))
+    del k1, k2
+    return nvstrings(out.value)
+
+
+def itos(values, count=0, nulls=None, bdevmem=False):
+    """nvstrings.py:153-174 -- strings from int32 values (NVStrings::itos, NVStrings.h:1042)."""
+    return _format(lib.cs_itos, values, count, nulls, bdevmem, np.int32)
+
+
+def ltos(values, count=0, nulls=None, bdevmem=False):
+    """nvstrings.py:177-198 -- strings from int64 values (NVStrings::ltos, NVStrings.h:1053)."""
+    return _format(lib.cs_ltos, values, count, nulls, bdevmem, np.int64)
+
+
+def ftos(values, count=0, nulls=None, bdevmem=False):
+    """nvstrings.py:201-223 -- strings from float32 values, up to 10 significant digits (NVStrings::ftos, NVStrings.h:1067)."""
+    return _format(lib.cs_ftos, values, count, nulls, bdevmem, np.float32)
+
+
+def dtos(values, count=0, nulls=None, bdevmem=False):
+    """nvstrings.py:226-248 -- strings from float64 values, up to 10 significant digits (NVStrings::dtos, NVStrings.h:1081)."""
+    return _format(lib.cs_dtos, values, count, nulls, bdevmem, np.float64)
+
+
+def int2ip(values, count=0, nulls=None, bdevmem=False):
+    """nvstrings.py:251-271 -- dotted-quad strings from uint32 values (NVStrings::int2ip, NVStrings.h:1124)."""
+    return _format(lib.cs_int2ip, values, count, nulls, bdevmem, np.uint32)
+
+
+def from_booleans(values, count=0, nulls=None, true="True", false="False", bdevmem=False):
+    """nvstrings.py:313-345 -- `true` / `false` per bool value (NVStrings::create_from_bools, NVStrings.h:1105)."""
+    if true is None or false is None:
+        raise ValueError("nvstrings.from_booleans: true and false must not be None")
+    return _format(lambda pv, n, pn, dev, st, out: lib.cs_from_bools(pv, n, b(true), b(false), pn, dev, st, out),
+                   values, count, nulls, bdevmem, np.uint8)
 
 
 def _int_array(values, count=0):
@@ -710,6 +782,55 @@ class nvstrings:
             lib.cs_regex_destroy(re)
         nulls = self._null_flags()
         return [None if nulls[i] else int(res[i]) for i in range(rows)]
+
+    # ---- strings -> numbers / booleans (nvstrings.py:675-850; convert.cu) -----------------------------------------------
+    def _convert(self, fn, dtype, devptr, to_py):
+        """one value per row: to `devptr` (device address or tensor) when given, else a host list, None for null rows."""
+        rows = self.size()
+        cnt = C.c_int64()
+        if devptr:
+            p = devptr.data_ptr() if hasattr(devptr, "data_ptr") else int(devptr)
+            check(fn(p, 1, C.byref(cnt)))
+            return devptr
+        if rows == 0:
+            return []
+        res = np.zeros(rows, dtype=dtype)
+        check(fn(res.ctypes.data, 0, C.byref(cnt)))
+        nulls = self._null_flags()
+        return [None if nulls[i] else to_py(v) for i, v in enumerate(res.tolist())]
+
+    def hash(self, devptr=0):
+        """nvstrings.py:675-694 -- MurmurHash3 (seed 31) of every row as uint32 (NVStrings::hash)."""
+        return self._convert(lambda p, d, f: lib.cs_hash(self.m_cptr, p, d, None, f), np.uint32, devptr, int)
+
+    def stoi(self, devptr=0):
+        """nvstrings.py:696-715 -- int32 per row (NVStrings::stoi)."""
+        return self._convert(lambda p, d, f: lib.cs_stoi(self.m_cptr, p, d, None, f), np.int32, devptr, int)
+
+    def stol(self, devptr=0):
+        """nvstrings.py:717-736 -- int64 per row (NVStrings::stol)."""
+        return self._convert(lambda p, d, f: lib.cs_stol(self.m_cptr, p, d, None, f), np.int64, devptr, int)
+
+    def stof(self, devptr=0):
+        """nvstrings.py:738-758 -- float32 per row (NVStrings::stof)."""
+        return self._convert(lambda p, d, f: lib.cs_stof(self.m_cptr, p, d, None, f), np.float32, devptr, float)
+
+    def stod(self, devptr=0):
+        """nvstrings.py:760-780 -- float64 per row (NVStrings::stod)."""
+        return self._convert(lambda p, d, f: lib.cs_stod(self.m_cptr, p, d, None, f), np.float64, devptr, float)
+
+    def htoi(self, devptr=0):
+        """nvstrings.py:782-802 -- hexadecimal strings to uint32 (NVStrings::htoi)."""
+        return self._convert(lambda p, d, f: lib.cs_htoi(self.m_cptr, p, d, None, f), np.uint32, devptr, int)
+
+    def ip2int(self, devptr=0):
+        """nvstrings.py:827-848 -- dotted-quad strings to uint32 (NVStrings::ip2int)."""
+        return self._convert(lambda p, d, f: lib.cs_ip2int(self.m_cptr, p, d, None, f), np.uint32, devptr, int)
+
+    def to_booleans(self, true="True", devptr=0):
+        """nvstrings.py:804-825 -- True where the row equals `true`; a null row is None in the host list
+        (on the device: 1 when `true` is None, else 0)."""
+        return self._convert(lambda p, d, f: lib.cs_to_bools(self.m_cptr, b(true), p, d, None, f), np.uint8, devptr, bool)
 
     # ---- parity helper ---------------------------------------------------------------------
     def digest(self):

@@ -522,6 +522,35 @@ int cs_prof_get(const char* kernel, double* total_ms, int64_t* launches);
  * size their grids for an empty device). */
 int cs_debug_spin(int blocks, int lds_bytes, int milliseconds, cs_stream stream);
 
+/* ---- numeric and boolean conversions (reference: cpp/src/strings/convert.cu; per-row logic in
+ * custrings_amd/csrc/convert_ops.h) ---------------------------------------------------------------------
+ * Parse ops: one value per row into `results` (rows entries; device memory when on_device).  A null row
+ * gives 0.  `count` receives the number of non-zero results, or -1 for an empty column or a NULL
+ * `results` (then nothing is written) -- the reference's return value. */
+int cs_hash(const cs_column* col, uint32_t* results, int on_device, cs_stream stream, int64_t* count); /* NVStrings::hash, NVStrings.h:1031: MurmurHash3_x86_32, seed 31 */
+int cs_stoi(const cs_column* col, int32_t* results, int on_device, cs_stream stream, int64_t* count);  /* NVStrings::stoi, NVStrings.h:991 */
+int cs_stol(const cs_column* col, int64_t* results, int on_device, cs_stream stream, int64_t* count);  /* NVStrings::stol, NVStrings.h:999 */
+int cs_stof(const cs_column* col, float* results, int on_device, cs_stream stream, int64_t* count);    /* NVStrings::stof, NVStrings.h:1015 */
+int cs_stod(const cs_column* col, double* results, int on_device, cs_stream stream, int64_t* count);   /* NVStrings::stod, NVStrings.h:1023 */
+int cs_htoi(const cs_column* col, uint32_t* results, int on_device, cs_stream stream, int64_t* count); /* NVStrings::htoi, NVStrings.h:1007 */
+int cs_ip2int(const cs_column* col, uint32_t* results, int on_device, cs_stream stream, int64_t* count); /* NVStrings::ip2int, NVStrings.h:1113 */
+/* NVStrings::to_bools, NVStrings.h:1092: 1 where the row equals `true_string`; a null row gives
+ * (true_string == NULL).  `count` = rows minus the false results (nulls count as false). */
+int cs_to_bools(const cs_column* col, const char* true_string, uint8_t* results, int on_device, cs_stream stream,
+                int64_t* count);
+/* Format ops: a new column of `count` rows from `count` values; `nulls` (optional, (count + 7) / 8 bytes,
+ * LSB-first, bit = 1 valid) makes the cleared rows null.  `values` and `nulls` live on the device when
+ * on_device.  values == NULL or count == 0: CS_ERR_INVALID_ARG (std::invalid_argument in the reference). */
+int cs_itos(const int32_t* values, int64_t count, const uint8_t* nulls, int on_device, cs_stream stream, cs_column** out);  /* NVStrings::itos, NVStrings.h:1042 */
+int cs_ltos(const int64_t* values, int64_t count, const uint8_t* nulls, int on_device, cs_stream stream, cs_column** out);  /* NVStrings::ltos, NVStrings.h:1053 */
+int cs_ftos(const float* values, int64_t count, const uint8_t* nulls, int on_device, cs_stream stream, cs_column** out);    /* NVStrings::ftos, NVStrings.h:1067 */
+int cs_dtos(const double* values, int64_t count, const uint8_t* nulls, int on_device, cs_stream stream, cs_column** out);   /* NVStrings::dtos, NVStrings.h:1081 */
+int cs_int2ip(const uint32_t* values, int64_t count, const uint8_t* nulls, int on_device, cs_stream stream, cs_column** out); /* NVStrings::int2ip, NVStrings.h:1124 */
+/* NVStrings::create_from_bools, NVStrings.h:1105: `true_string` / `false_string` (both required) per value
+ * (one byte each, non-zero = true). */
+int cs_from_bools(const uint8_t* values, int64_t count, const char* true_string, const char* false_string,
+                  const uint8_t* nulls, int on_device, cs_stream stream, cs_column** out);
+
 #ifdef __cplusplus
 }
 #endif

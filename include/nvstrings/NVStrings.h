@@ -115,6 +115,24 @@ class NVStrings {
   int match(const char* pattern, bool* results, bool devmem = true);
   int count_re(const char* pattern, int* results, bool devmem = true);
 
+  /* ---- conversions (NVStrings.h:991-1124; convert.cu).  Parse members return the count of non-zero results,
+   * -1 for an empty instance or a null `results`; `long*` stays `long*` so the mangled names match. ---- */
+  int stoi(int* results, bool devmem = true);
+  int stol(long* results, bool devmem = true);
+  int htoi(unsigned int* results, bool devmem = true);
+  int stof(float* results, bool devmem = true);
+  int stod(double* results, bool devmem = true);
+  int hash(unsigned int* results, bool devmem = true);
+  static NVStrings* itos(const int* values, unsigned int count, const unsigned char* nullbitmask = nullptr, bool devmem = true);
+  static NVStrings* ltos(const long* values, unsigned int count, const unsigned char* nullbitmask = nullptr, bool devmem = true);
+  static NVStrings* ftos(const float* values, unsigned int count, const unsigned char* nullbitmask = nullptr, bool devmem = true);
+  static NVStrings* dtos(const double* values, unsigned int count, const unsigned char* nullbitmask = nullptr, bool devmem = true);
+  int to_bools(bool* results, const char* true_string, bool devmem = true);
+  static NVStrings* create_from_bools(const bool* values, unsigned int count, const char* true_string, const char* false_string,
+                                      const unsigned char* nullbitmask = nullptr, bool devmem = true);
+  int ip2int(unsigned int* results, bool devmem = true);
+  static NVStrings* int2ip(const unsigned int* values, unsigned int count, const unsigned char* nullbitmask = nullptr, bool devmem = true);
+
   /* ---- not in the reference: the bridge to the C ABI (used by libNVCategory / libNVText and by callers that
    * want the native record form or the engine's handles) ---- */
   static NVStrings* adopt(cs_column* column); /* takes ownership of a handle produced by the C ABI */

@@ -61,7 +61,7 @@ def report(config, op, rows, in_bytes, alg_bytes, dt):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scale", type=float, default=1.0, help="row-count multiplier (1.0 = BASELINE.json single-GPU sizes)")
-    ap.add_argument("--only", default="C2,C3,C4,C5", help="comma-separated configs to run")
+    ap.add_argument("--only", default="C2,C3,C4,C5", help="comma-separated configs to run (CONV: the conversion ops)")
     a = ap.parse_args()
     only = set(a.only.split(","))
     ov = 8.125  # native offset + validity bytes per row
@@ -74,6 +74,8 @@ def main():
         run_c4(a, ov)
     if "C5" in only:
         run_c5(a, ov)
+    if "CONV" in only:
+        run_conv(a, ov)
 
 
 def run_c2(a, ov):
@@ -229,6 +231,40 @@ def run_c5(a, ov):
     rep = c5.replace(r"[aeiou]+", "*") if False else None
     ng = nvtext.ngrams(tok, 2, "_")
     report("C5", "ngrams(2)", t, nbytes(tok), nbytes(tok) + ov * t + nbytes(ng) + ov * ng.size(), timed(lambda: nvtext.ngrams(tok, 2, "_"), reps=2))
+
+
+def run_conv(a, ov):
+    # ---- the conversion ops (convert.cu) at 100M rows, on the route the library picks and with CS_CONVERT_ROWWISE=1.
+    # Parse: (L + 8.125) read + the result written per row; format: the value (+ 1/8 mask bit) read + (L' + 8.125) written.
+    rows = int(100_000_000 * a.scale)
+    gen = torch.Generator(device="cuda").manual_seed(SEED)
+    i32 = torch.randint(-(1 << 31), (1 << 31) - 1, (rows,), dtype=torch.int32, device="cuda", generator=gen)
+    i64 = torch.randint(-(1 << 63), (1 << 63) - 1, (rows,), dtype=torch.int64, device="cuda", generator=gen)
+    f32 = (torch.randn(rows, device="cuda", generator=gen) * 1e3).float()
+    f64 = torch.randn(rows, device="cuda", generator=gen, dtype=torch.float64) * 1e6
+    bools = torch.randint(0, 2, (rows,), dtype=torch.uint8, device="cuda", generator=gen)
+    c3, c4 = synth(3, rows), synth(4, rows, 1000)
+    ip = c3.split(" ")[2]
+    itos_col, dtos_col = nvstrings.itos(i32, bdevmem=True), nvstrings.dtos(f64, bdevmem=True)
+    out = {w: torch.empty(rows, dtype=t, device="cuda") for w, t in ((1, torch.uint8), (4, torch.int32), (8, torch.int64))}
+    parse = (("C3", "hash", c3, 4), ("C4", "hash", c4, 4), ("C3 field 3", "ip2int", ip, 4), ("itos output", "stoi", itos_col, 4),
+             ("dtos output", "stod", dtos_col, 8))
+    fmt = (("itos", i32, 4), ("ltos", i64, 8), ("ftos", f32, 4), ("dtos", f64, 8), ("int2ip", i32, 4), ("from_booleans", bools, 1))
+    for route in ("default", "rowwise"):
+        if route == "rowwise":
+            L.cs_config_set(b"CS_CONVERT_ROWWISE", b"1")
+        for cfg, op, col, w in parse:
+            b = nbytes(col)
+            fn = getattr(col, op)
+            dt = timed(lambda: fn(devptr=out[w].data_ptr()))
+            report("CONV %s [%s]" % (cfg, L.cs_debug_last_route().decode()), op, rows, b, b + ov * rows + w * rows, dt)
+        for op, vals, w in fmt:
+            res = getattr(nvstrings, op)(vals, bdevmem=True)
+            b = nbytes(res)
+            dt = timed(lambda: getattr(nvstrings, op)(vals, bdevmem=True), reps=2)
+            report("CONV seeded values [%s]" % L.cs_debug_last_route().decode(), op, rows, w * rows, w * rows + b + col_ov(res) * rows, dt)
+            del res
+    L.cs_config_set(b"CS_CONVERT_ROWWISE", None)
 
 
 if __name__ == "__main__":
