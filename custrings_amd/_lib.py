@@ -139,6 +139,9 @@ _PROTOS = {
     "cs_dtos": (i32, [vp, i64, vp, i32, vp, P(vp)]),
     "cs_int2ip": (i32, [vp, i64, vp, i32, vp, P(vp)]),
     "cs_from_bools": (i32, [vp, i64, cp, cp, vp, i32, vp, P(vp)]),
+    # timestamps (datetime.cu)
+    "cs_timestamp2long": (i32, [vp, cp, i32, vp, i32, vp, P(i64)]),
+    "cs_long2timestamp": (i32, [vp, i64, i32, cp, vp, i32, vp, P(vp)]),
     "cs_replace_re": (i32, [vp, vp, cp, i32, vp, P(vp)]),
     "cs_replace_with_backrefs": (i32, [vp, vp, cp, vp, P(vp)]),
     "cs_extract": (i32, [vp, vp, vp, P(P(vp)), P(i32)]),

@@ -1,6 +1,6 @@
 // Numeric and boolean conversions to and from string columns (reference: cpp/src/strings/convert.cu, the members
 // hash / stoi / stol / stof / stod / htoi / ip2int / to_bools and itos / ltos / ftos / dtos / int2ip /
-// create_from_bools; the timestamp pair is not here).  The per-row logic is convert_ops.h, shared with the CPU
+// create_from_bools; the timestamp pair is cs_datetime.hip).  The per-row logic is convert_ops.h, shared with the CPU
 // harness of tests/test_convert_cpu.py.
 //
 // Parse ops (string -> one value per row), two routes:

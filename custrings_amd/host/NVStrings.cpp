@@ -551,3 +551,22 @@ NVStrings* NVStrings::create_from_bools(const bool* values, unsigned int count, 
   check(cs_from_bools(reinterpret_cast<const uint8_t*>(values), count, true_string, false_string, nullbitmask, devmem ? 1 : 0, nullptr, &c));
   return adopt(c);
 }
+
+// ---- timestamps (datetime.cu) ----------------------------------------------------------------------------------------
+static_assert(NVStrings::years == CS_TS_YEARS && NVStrings::seconds == CS_TS_SECONDS && NVStrings::ns == CS_TS_NS,
+              "timestamp_units and cs_timestamp_units agree");
+// the count of non-zero results, -1 for an empty instance or a null `results` (datetime.cu:351-378)
+int NVStrings::timestamp2long(const char* format, timestamp_units units, unsigned long* results, bool devmem) {
+  static_assert(sizeof(unsigned long) == sizeof(int64_t), "long is 64-bit on the supported hosts");
+  int64_t n = -1;
+  check(cs_timestamp2long(m_col, format, (int)units, reinterpret_cast<int64_t*>(results), devmem ? 1 : 0, nullptr, &n));
+  return (int)n;
+}
+// std::invalid_argument on values == nullptr or count == 0 (datetime.cu:641-642) and on a bad format
+NVStrings* NVStrings::long2timestamp(const unsigned long* values, unsigned int count, timestamp_units units, const char* format,
+                                     const unsigned char* nullbitmask, bool devmem) {
+  ensure_device();
+  cs_column* c = nullptr;
+  check(cs_long2timestamp(reinterpret_cast<const int64_t*>(values), count, (int)units, format, nullbitmask, devmem ? 1 : 0, nullptr, &c));
+  return adopt(c);
+}

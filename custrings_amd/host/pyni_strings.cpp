@@ -674,6 +674,54 @@ static PyObject* n_createFromBools(PyObject*, PyObject* args) {  // (values, cou
   });
 }
 
+// ---- timestamps (pystrings.cpp:707-780, 1335-1388; datetime.cu) ---------------------------------------------------------
+// the unit names of the Python API; an unknown name is a ValueError
+static bool units_arg(PyObject* args, int i, NVStrings::timestamp_units* units) {
+  static const struct {
+    const char* name;
+    NVStrings::timestamp_units units;
+  } names[] = {{"Y", NVStrings::years}, {"M", NVStrings::months}, {"D", NVStrings::days},  {"h", NVStrings::hours}, {"m", NVStrings::minutes},
+               {"s", NVStrings::seconds}, {"ms", NVStrings::ms},  {"us", NVStrings::us}, {"ns", NVStrings::ns}};
+  const char* u = str_arg(args, i);
+  for (const auto& n : names) {
+    if (u && !strcmp(u, n.name)) {
+      *units = n.units;
+      return true;
+    }
+  }
+  if (!PyErr_Occurred()) PyErr_SetString(PyExc_ValueError, "nvstrings: units parameter value unrecognized");
+  return false;
+}
+static PyObject* n_timestamp2int(PyObject*, PyObject* args) {  // (self, format, units, devptr)
+  const char* format = str_arg(args, 1);
+  NVStrings::timestamp_units units;
+  if (!units_arg(args, 2, &units)) return nullptr;
+  return conv_results<unsigned long>(args, 3, [&](NVStrings* s, unsigned long* o, bool d) { s->timestamp2long(format, units, o, d); },
+                                     [](unsigned long v) { return PyLong_FromLong((long)v); });
+}
+static PyObject* n_createFromTimestamp(PyObject*, PyObject* args) {  // (values, count, nulls, format, units, bdevmem)
+  const char* format = str_arg(args, 3);
+  NVStrings::timestamp_units units;
+  if (!units_arg(args, 4, &units)) return nullptr;
+  PyObject* v = arg(args, 0);
+  if (PyObject_CheckBuffer(v)) {  // (pystrings.cpp:743-747: the values must be 8 bytes wide)
+    Py_buffer view;
+    if (PyObject_GetBuffer(v, &view, PyBUF_FORMAT | PyBUF_ND) == 0) {
+      const bool wide = view.itemsize == (Py_ssize_t)sizeof(long) && (!view.format || strchr("qlQL", view.format[strlen(view.format) - 1]));
+      PyBuffer_Release(&view);
+      if (!wide) {
+        PyErr_SetString(PyExc_TypeError, "nvstrings.int2timestamp(): values must be of type int64");
+        return nullptr;
+      }
+    } else {
+      PyErr_Clear();
+    }
+  }
+  return from_values<long>(args, "int2timestamp", 2, 5, [&](const long* p, unsigned n, const unsigned char* m, bool d) {
+    return NVStrings::long2timestamp(reinterpret_cast<const unsigned long*>(p), n, units, format, m, d);
+  });
+}
+
 static PyMethodDef s_Methods[] = {
 #define M(n) {#n, n, METH_VARARGS, ""}
     M(n_dropWrapper), M(n_getIPCData), M(n_createFromIPC),
@@ -685,6 +733,7 @@ static PyMethodDef s_Methods[] = {
     M(n_add_strings), M(n_cat), M(n_join), M(n_device_memory),
     M(n_hash), M(n_stoi), M(n_stol), M(n_stof), M(n_stod), M(n_htoi), M(n_ip2int), M(n_to_bools), M(n_createFromInt32s),
     M(n_createFromInt64s), M(n_createFromFloat32s), M(n_createFromFloat64s), M(n_createFromIPv4Integers), M(n_createFromBools),
+    M(n_timestamp2int), M(n_createFromTimestamp),
 #undef M
     {NULL, NULL, 0, NULL}};
 static struct PyModuleDef s_Module = {PyModuleDef_HEAD_INIT, "pyniNVStrings", "CPython glue of nvstrings over the MI355X back-end", -1, s_Methods};

@@ -14,7 +14,7 @@ from . import _lib
 from ._lib import lib, check, b, addr
 
 __all__ = ["to_device", "from_strings", "from_offsets", "free", "bind_cpointer", "create_from_ipc", "nvstrings",
-           "itos", "ltos", "ftos", "dtos", "int2ip", "from_booleans"]
+           "itos", "ltos", "ftos", "dtos", "int2ip", "from_booleans", "int2timestamp"]
 
 
 def to_device(strs):
@@ -109,7 +109,7 @@ def bind_cpointer(cptr, own=True):
 
 
 _NOT_BUILT = (
-    "compare timestamp2int "
+    "compare "
     "get repeat pad ljust center rjust zfill wrap slice slice_from "
     "slice_replace insert fillna capitalize swapcase title index rindex "
     "find_from rfind match_strings startswith endswith isalnum "
@@ -187,6 +187,52 @@ def from_booleans(values, count=0, nulls=None, true="True", false="False", bdevm
         raise ValueError("nvstrings.from_booleans: true and false must not be None")
     return _format(lambda pv, n, pn, dev, st, out: lib.cs_from_bools(pv, n, b(true), b(false), pn, dev, st, out),
                    values, count, nulls, bdevmem, np.uint8)
+
+
+# ---- timestamps (nvstrings.py:275-310, 849-879; datetime.cu) -----------------------------------------------------------
+_TS_UNITS = {"Y": 0, "M": 1, "D": 2, "h": 3, "m": 4, "s": 5, "ms": 6, "us": 7, "ns": 8}  # NVStrings::timestamp_units
+
+
+def _ts_units(units):
+    if units not in _TS_UNITS:
+        raise ValueError("nvstrings: units parameter value unrecognized")
+    return _TS_UNITS[units]
+
+
+def int2timestamp(values, count=0, nulls=None, format=None, units="s", bdevmem=False):
+    """
+    Create date/time strings from an array of int64 values.
+    The values must be in units as specified by the units parameter.
+    The values is expected to be from epoch time and in UTC.
+
+    Parameters
+    ----------
+    values : list, memory address or buffer
+        Array of int64 values to convert to date-time strings.
+    count : int
+        Number of integers in values.
+        This is only required if values is a memory pointer.
+    nulls : list, memory address or buffer
+        Bit array indicating which values should be considered null.
+        Uses the arrow format for valid bitmask.
+    format : str
+        May include the following strftime specifiers only:
+        %Y,%y,%m,%d,%H,%I,%p,%M,%S,%f,%z
+        Default format is "%Y-%m-%dT%H:%M:%SZ"
+    units : str
+        The units of the values and must be one of the following:
+        Y,M,D,h,m,s,ms,us,ns
+        Default is 's' for seconds
+    bdevmem : boolean
+        Default (False) interprets memory pointers as CPU memory.
+
+    """
+    u = _ts_units(units)
+    fmt = None if format is None else b(format)
+    if isinstance(values, np.ndarray) and (values.dtype.kind not in "iu" or values.dtype.itemsize != 8):
+        raise TypeError("nvstrings.int2timestamp(): values must be of type int64")
+    return _format(lambda pv, n, pn, dev, st, out: lib.cs_long2timestamp(pv, n, u, fmt, pn, dev, st, out),
+                   values, count, nulls, bdevmem, np.int64)
 
 
 def _int_array(values, count=0):
@@ -831,6 +877,39 @@ class nvstrings:
         """nvstrings.py:804-825 -- True where the row equals `true`; a null row is None in the host list
         (on the device: 1 when `true` is None, else 0)."""
         return self._convert(lambda p, d, f: lib.cs_to_bools(self.m_cptr, b(true), p, d, None, f), np.uint8, devptr, bool)
+
+    def timestamp2int(self, format=None, units="s", devptr=0):
+        """
+        Returns integer value represented by each string.
+        String is interpretted using the format provided.
+        The values are returned in the units specified based
+        on epoch time and in UTC.
+
+        Parameters
+        ----------
+        format : str
+            May include the following strptime specifiers only:
+            %Y,%y,%m,%d,%H,%I,%p,%M,%S,%f,%z
+            Default format is "%Y-%m-%dT%H:%M:%SZ"
+        units : str
+            The units of the values and must be one of the following:
+            Y,M,D,h,m,s,ms,us,ns
+            Default is 's' for seconds
+        devptr : GPU memory pointer
+            Where resulting integer values will be written.
+            Memory must be able to hold at least size() of int64 values.
+
+        Examples
+        --------
+        >>> import nvstrings
+        >>> s = nvstrings.to_device(["2019-03-20T12:34:56Z"])
+        >>> print(s.timestamp2int())
+        [1553085296]
+
+        """
+        u = _ts_units(units)
+        fmt = None if format is None else b(format)
+        return self._convert(lambda p, d, f: lib.cs_timestamp2long(self.m_cptr, fmt, u, p, d, None, f), np.int64, devptr, int)
 
     # ---- parity helper ---------------------------------------------------------------------
     def digest(self):

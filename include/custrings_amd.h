@@ -551,6 +551,34 @@ int cs_int2ip(const uint32_t* values, int64_t count, const uint8_t* nulls, int o
 int cs_from_bools(const uint8_t* values, int64_t count, const char* true_string, const char* false_string,
                   const uint8_t* nulls, int on_device, cs_stream stream, cs_column** out);
 
+/* ---- timestamp conversions (reference: cpp/src/strings/datetime.cu; per-row logic in
+ * custrings_amd/csrc/datetime_ops.h) ---------------------------------------------------------------------
+ * `format` holds strptime / strftime specifiers (%Y %y %m %d %j %H %I %M %S %f %p %z %Z; %% is a literal
+ * '%'); NULL means "%Y-%m-%dT%H:%M:%SZ".  A '%' at the end, an unknown specifier or units outside the enum
+ * are CS_ERR_INVALID_ARG (std::invalid_argument in the reference). */
+typedef enum cs_timestamp_units { /* NVStrings::timestamp_units, NVStrings.h:1128 */
+  CS_TS_YEARS = 0,
+  CS_TS_MONTHS = 1,
+  CS_TS_DAYS = 2,
+  CS_TS_HOURS = 3,
+  CS_TS_MINUTES = 4,
+  CS_TS_SECONDS = 5,
+  CS_TS_MS = 6,
+  CS_TS_US = 7,
+  CS_TS_NS = 8
+} cs_timestamp_units;
+/* NVStrings::timestamp2long, NVStrings.h:1153: one int64 per row since the epoch, in `units` (a
+ * cs_timestamp_units), into `results` (device memory when on_device).  A null, empty or unparsable row gives
+ * 0.  `count` receives the number of non-zero results, or -1 for an empty column or a NULL `results` (checked
+ * before the format is read; nothing is written). */
+int cs_timestamp2long(const cs_column* col, const char* format, int units, int64_t* results, int on_device, cs_stream stream,
+                      int64_t* count);
+/* NVStrings::long2timestamp, NVStrings.h:1171: a column of `count` rows from int64 `values` in `units`; `nulls`
+ * (optional, (count + 7) / 8 bytes, LSB-first, bit = 1 valid) makes the cleared rows null.  Every other row has
+ * the same width.  values == NULL or count == 0: CS_ERR_INVALID_ARG (checked before the format is read). */
+int cs_long2timestamp(const int64_t* values, int64_t count, int units, const char* format, const uint8_t* nulls, int on_device,
+                      cs_stream stream, cs_column** out);
+
 #ifdef __cplusplus
 }
 #endif

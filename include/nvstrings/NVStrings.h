@@ -133,6 +133,23 @@ class NVStrings {
   int ip2int(unsigned int* results, bool devmem = true);
   static NVStrings* int2ip(const unsigned int* values, unsigned int count, const unsigned char* nullbitmask = nullptr, bool devmem = true);
 
+  /* ---- timestamps (NVStrings.h:1126-1171; datetime.cu).  The enumerators and their order are the reference's: they are
+   * part of the mangled names.  Format errors and a null `values` / zero `count` throw std::invalid_argument. ---- */
+  enum timestamp_units {
+    years,    ///< precision is years
+    months,   ///< precision is months
+    days,     ///< precision is days
+    hours,    ///< precision is hours
+    minutes,  ///< precision is minutes
+    seconds,  ///< precision is seconds
+    ms,       ///< precision is milliseconds
+    us,       ///< precision is microseconds
+    ns        ///< precision is nanoseconds
+  };
+  int timestamp2long(const char* format, timestamp_units units, unsigned long* results, bool devmem = true);
+  static NVStrings* long2timestamp(const unsigned long* values, unsigned int count, timestamp_units units, const char* format,
+                                   const unsigned char* nullbitmask = nullptr, bool devmem = true);
+
   /* ---- not in the reference: the bridge to the C ABI (used by libNVCategory / libNVText and by callers that
    * want the native record form or the engine's handles) ---- */
   static NVStrings* adopt(cs_column* column); /* takes ownership of a handle produced by the C ABI */

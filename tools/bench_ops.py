@@ -61,7 +61,7 @@ def report(config, op, rows, in_bytes, alg_bytes, dt):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scale", type=float, default=1.0, help="row-count multiplier (1.0 = BASELINE.json single-GPU sizes)")
-    ap.add_argument("--only", default="C2,C3,C4,C5", help="comma-separated configs to run (CONV: the conversion ops)")
+    ap.add_argument("--only", default="C2,C3,C4,C5", help="comma-separated configs to run (CONV: the conversion ops, TS: the timestamp ones)")
     a = ap.parse_args()
     only = set(a.only.split(","))
     ov = 8.125  # native offset + validity bytes per row
@@ -76,6 +76,8 @@ def main():
         run_c5(a, ov)
     if "CONV" in only:
         run_conv(a, ov)
+    if "TS" in only:
+        run_ts(a)
 
 
 def run_c2(a, ov):
@@ -264,6 +266,33 @@ def run_conv(a, ov):
             dt = timed(lambda: getattr(nvstrings, op)(vals, bdevmem=True), reps=2)
             report("CONV seeded values [%s]" % L.cs_debug_last_route().decode(), op, rows, w * rows, w * rows + b + col_ov(res) * rows, dt)
             del res
+    L.cs_config_set(b"CS_CONVERT_ROWWISE", None)
+
+
+def run_ts(a):
+    # ---- the timestamp conversions (datetime.cu) at 100M rows in the default format ("%Y-%m-%dT%H:%M:%SZ", 20 bytes a row).
+    # Parse: the chars + the offsets read, the int64 written; format: the int64 (+ 1/8 mask bit) read, the chars + the
+    # offsets (+ validity) written.  Both routes / both writers: the default and CS_CONVERT_ROWWISE=1.
+    rows = int(100_000_000 * a.scale)
+    gen = torch.Generator(device="cuda").manual_seed(SEED)
+    secs = torch.randint(0, 253402300799, (rows,), dtype=torch.int64, device="cuda", generator=gen)
+    ms = secs * 1000 + torch.randint(0, 1000, (rows,), dtype=torch.int64, device="cuda", generator=gen)
+    nulls = torch.randint(0, 256, ((rows + 7) // 8,), dtype=torch.uint8, device="cuda", generator=gen)
+    col = nvstrings.int2timestamp(secs, bdevmem=True)
+    out = torch.empty(rows, dtype=torch.int64, device="cuda")
+    for route in ("default", "rowwise"):
+        L.cs_config_set(b"CS_CONVERT_ROWWISE", b"1" if route == "rowwise" else None)
+        b = nbytes(col)
+        dt = timed(lambda: col.timestamp2int(devptr=out.data_ptr()))
+        report("TS default format [%s]" % L.cs_debug_last_route().decode(), "timestamp2int(s)", rows, b, b + col_ov(col) * rows + 8 * rows, dt)
+        for units, vals in (("s", secs), ("ms", ms)):
+            for nl in (None, nulls):
+                res = nvstrings.int2timestamp(vals, nulls=nl, units=units, bdevmem=True)
+                b = nbytes(res)
+                dt = timed(lambda: nvstrings.int2timestamp(vals, nulls=nl, units=units, bdevmem=True), reps=3)
+                cfg = "TS seeded values%s [%s]" % (" + nulls" if nl is not None else "", L.cs_debug_last_route().decode())
+                report(cfg, "int2timestamp(%s)" % units, rows, 8 * rows, 8 * rows + (0.125 * rows if nl is not None else 0) + b + col_ov(res) * rows, dt)
+                del res
     L.cs_config_set(b"CS_CONVERT_ROWWISE", None)
 
 
