@@ -58,35 +58,12 @@ __global__ void __launch_bounds__(256) k_case_tile(CaseTileArgs a) {
   uint8_t* lds_out = base + a.cap;
   uint32_t* bitmap = reinterpret_cast<uint32_t*>(base + 2 * a.cap);  // bit i: byte i of the tile is >= 0x80
   const ColView& in = a.in;
-  const int R = a.rows_per_tile;
-  const long long waves = (long long)gridDim.x * 4;
-  const long long per = (a.ntiles + waves - 1) / waves;
-  long long tile = ((long long)blockIdx.x * 4 + wv) * per;
-  const long long tile_end = min(a.ntiles, tile + per);
-  if (tile >= tile_end) return;
-  auto load_offs = [&](long long t) {
-    const long long r0 = t * R;
-    const int nrows = (int)min((long long)R, in.rows - r0);
-    cstile::TileOffs o;
-    o.o0 = in.offsets[r0 + min(lane, nrows)];
-    o.o1 = in.offsets[r0 + min(lane + 1, nrows)];
-    return o;
-  };
-  cstile::TileOffs cur = load_offs(tile);
-  cstile::TileOffs nxt = cur;
-  if (tile + 1 < tile_end) nxt = load_offs(tile + 1);
-  cstile::TileChars pf;
-#pragma unroll
-  for (int j = 0; j < cstile::kPfChunks; ++j) pf.v[j] = make_uint4(0, 0, 0, 0);
-  cstile::issue_chars(in.chars, cstile::rl64(cur.o0, 0), cstile::rl64(cur.o1, 63), lane, pf);
+  cstile::RowTileWalk walk(in, a.rows_per_tile, a.ntiles, wv, lane);
+  if (walk.done()) return;
   for (;;) {
-    const long long r0 = tile * R;
-    const int nrows = (int)min((long long)R, in.rows - r0);
-    const long long g0 = cstile::rl64(cur.o0, 0), g1 = cstile::rl64(cur.o1, 63);
-    const bool live = lane < nrows && row_is_valid(in.validity, r0 + lane);
-    const int rbeg = (int)(cur.o0 - g0);
-    const int n = live ? (int)(cur.o1 - cur.o0) : 0;
-    const int lead = (int)((uintptr_t)(in.chars + g0) & 15);
+    const cstile::RowTile cur = walk.current();
+    const long long g0 = cur.g0, g1 = cur.g1;
+    const int rbeg = cur.rbeg, n = cur.n, lead = cur.lead;
     const long long want64 = g1 - g0 + lead;
     if (want64 + 16 > a.cap) {
       // A tile beyond the staging buffer (the host sized it for all but a few tiles: one long row among millions of
@@ -124,14 +101,7 @@ __global__ void __launch_bounds__(256) k_case_tile(CaseTileArgs a) {
         if (row_case_size(p, n, a.flags, a.cases, a.bit) != n) atomicOr(a.changed, 1u);
         else row_case_write(p, n, a.flags, a.cases, a.bit, a.out_chars + (g0 + rbeg));
       }
-      const bool more = tile + 1 < tile_end;
-      if (more) {
-        cur = nxt;
-        cstile::issue_chars(in.chars, cstile::rl64(cur.o0, 0), cstile::rl64(cur.o1, 63), lane, pf);
-        if (tile + 2 < tile_end) nxt = load_offs(tile + 2);
-      }
-      if (!more) break;
-      ++tile;
+      if (!walk.advance()) break;
       continue;
     }
     const int want = (int)want64;
@@ -142,7 +112,7 @@ __global__ void __launch_bounds__(256) k_case_tile(CaseTileArgs a) {
     for (int j = 0; j < cstile::kPfChunks; ++j) {
       const int i = j * 1024 + lane * 16;
       if (i < want) {
-        const uint4 q = pf.v[j];
+        const uint4 q = walk.pf.v[j];
         *reinterpret_cast<uint4*>(lds_in + i) = q;
         uint4 o;
         o.x = flip_ascii(q.x, a.bit);
@@ -157,12 +127,7 @@ __global__ void __launch_bounds__(256) k_case_tile(CaseTileArgs a) {
         reinterpret_cast<uint16_t*>(bitmap)[i >> 4] = (uint16_t)bits;
       }
     }
-    const bool has_next = tile + 1 < tile_end;
-    if (has_next) {
-      cur = nxt;
-      cstile::issue_chars(in.chars, cstile::rl64(cur.o0, 0), cstile::rl64(cur.o1, 63), lane, pf);
-      if (tile + 2 < tile_end) nxt = load_offs(tile + 2);
-    }
+    const bool has_next = walk.advance();
     cstile::wave_lds_fence();
     if (__any(any_high != 0)) {  // some row of the tile holds non-ASCII characters
       // Row lanes visit only the non-ASCII bytes of their row (bitmap bits), in order: a lead byte
@@ -219,7 +184,6 @@ __global__ void __launch_bounds__(256) k_case_tile(CaseTileArgs a) {
     cstile::wave_flush(a.out_chars + g0, (int)(g1 - g0), lds_out, lead, lane);
     cstile::wave_lds_fence();
     if (!has_next) break;
-    ++tile;
   }
 }
 
@@ -230,21 +194,11 @@ namespace cs {
 bool change_case_fast(const cs_column* col, unsigned bit, bool ascii_rule_ok, hipStream_t s, cs_column** out) {
   const int64_t rows = col->rows;
   if (rows == 0 || !ascii_rule_ok || col->nbytes == 0 || cs::cfg("CS_CASE_ROWWISE")) return false;
-  int R = 0;
-  for (int r : {64, 32, 16}) {
-    if (max_span_rows(col, r, s) + 32 <= cstile::kPfBytes) {
-      R = r;
-      break;
-    }
-  }
-  int64_t span = R ? max_span_rows(col, R, s) : 0;
-  if (!R && !cs::cfg("CS_NO_OUTLIER_TILES")) {
-    // no tile size fits every tile (one long row among short ones, or rows of hundreds of bytes throughout): 64-row tiles,
-    // the kernel maps a tile beyond the staging size with the whole wave, sixteen bytes a lane, straight from memory --
-    // row by row only when the tile holds non-ASCII bytes
-    R = 64;
-    span = cstile::kPfBytes - 64;
-  }
+  // (no tile size fits every tile -- one long row among short ones, or rows of hundreds of bytes throughout: 64-row tiles,
+  // the kernel maps a tile beyond the staging size with the whole wave, sixteen bytes a lane, straight from memory --
+  // row by row only when the tile holds non-ASCII bytes)
+  const TilePlan tp = plan_row_tiles(col, 32, s, true);
+  const int R = tp.R;
   if (!R) return false;
   CaseTileArgs a{};
   a.in = view_of(col);
@@ -253,7 +207,7 @@ bool change_case_fast(const cs_column* col, unsigned bit, bool ascii_rule_ok, hi
   a.bit = bit;
   a.flags = d_unicode_flags();
   a.cases = d_charcases();
-  a.cap = (int)((span + 32 + 15) & ~(int64_t)15);
+  a.cap = (int)((tp.span + 32 + 15) & ~(int64_t)15);
   Buf chars = dev_alloc((size_t)col->nbytes, s);
   Buf flag = dev_alloc(sizeof(unsigned), s);
   CS_HIP(hipMemsetAsync(flag->p, 0, sizeof(unsigned), s));
@@ -262,15 +216,10 @@ bool change_case_fast(const cs_column* col, unsigned bit, bool ascii_rule_ok, hi
   constexpr size_t kBitmapBytes = cstile::kPfBytes / 8 + 32;
   const size_t lds = (2 * (size_t)a.cap + kBitmapBytes) * 4;
   if (lds > 150 * 1024) return false;
-  if (lds > 48 * 1024)
-    CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_case_tile), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)lds));
   {
-    const unsigned g = resident_grid(reinterpret_cast<const void*>(&k_case_tile), lds, (a.ntiles + 3) / 4);
     ProfScope ps(bit == 32 ? "k_lower_write" : "k_upper_write", s);
-    hipLaunchKernelGGL(k_case_tile, dim3(g), dim3(256), lds, s, a);
+    launch_resident(&k_case_tile, lds, (a.ntiles + 3) / 4, s, a);
   }
-  CS_HIP(hipGetLastError());
   unsigned* h = (unsigned*)pinned_scratch(sizeof(unsigned));
   CS_HIP(hipMemcpyAsync(h, flag->p, sizeof(unsigned), hipMemcpyDeviceToHost, s));
   CS_HIP(hipStreamSynchronize(s));

@@ -3,13 +3,8 @@
 // create_from_bools; the timestamp pair is cs_datetime.hip).  The per-row logic is convert_ops.h, shared with the CPU
 // harness of tests/test_convert_cpu.py.
 //
-// Parse ops (string -> one value per row), two routes:
-//  - tile: a wave stages the bytes of R = 64 / 32 / 16 consecutive rows in LDS with one coalesced prefetch
-//    (cstile::issue_chars / stage_chars; R as find_tiles chooses it), each lane parses its row out of LDS and the
-//    wave stores its R results side by side.  Taken when every R-row tile of the column fits the prefetch.
-//  - rows: a thread per row reading its bytes from memory (columns no tile size fits -- rows of several KB -- and
-//    CS_CONVERT_ROWWISE=1).  hash reads every byte of a long row.
-//  Both count the non-zero results with one atomic per workgroup (see k_len, cs_array.hip).
+// Parse ops (string -> one value per row): the tile and row-wise routes of parse_route.h, with the per-row parsers of
+// convert_ops.h.
 // Format ops (value -> string): a length pass (-1 = null), the shared lengths -> offsets scan, a write pass; the
 // output has int32 offsets when rows x the op's widest row < 2^31, else int64 (include/custrings_amd.h).
 //
@@ -23,7 +18,7 @@
 #include "convert_ops.h"
 #include "cs_internal.h"
 #include "device_utils.h"
-#include "tile_utils.h"
+#include "parse_route.h"
 
 using namespace cs;
 using namespace csdev;
@@ -41,170 +36,24 @@ template <> struct ParseOut<P_HTOI> { using T = uint32_t; };
 template <> struct ParseOut<P_IP2INT> { using T = uint32_t; };
 template <> struct ParseOut<P_BOOL> { using T = uint8_t; };
 
-struct ParseArgs {
-  ColView in;
-  void* out;
-  const uint8_t* tstr;  // to_bools: the true string on the device (nullptr: none given)
-  int tlen;
-  unsigned long long* nonzero;
-  // tile route
-  int rows_per_tile, cap;
-  long long ntiles;
-};
-
 // the value of a row; `valid` false = a null row (0, or `true_string == nullptr` for to_bools)
 template <int OP>
-__device__ __forceinline__ typename ParseOut<OP>::T parse_row(const uint8_t* p, int n, bool valid, const ParseArgs& a) {
+struct ConvertParse {
   using T = typename ParseOut<OP>::T;
-  if constexpr (OP == P_BOOL) return valid ? csconv::to_bool_row(p, n, a.tstr, a.tlen) : (T)(a.tstr == nullptr);
-  if (!valid) return (T)0;
-  if constexpr (OP == P_HASH) return csconv::hash_row(p, n);
-  else if constexpr (OP == P_STOI) return csconv::stoi_row(p, n);
-  else if constexpr (OP == P_STOL) return csconv::stol_row(p, n);
-  else if constexpr (OP == P_STOF) return csconv::stof_row(p, n);
-  else if constexpr (OP == P_STOD) return csconv::stod_row(p, n);
-  else if constexpr (OP == P_HTOI) return csconv::htoi_row(p, n);
-  else return csconv::ip2int_row(p, n);
-}
-
-template <int OP>
-__global__ void __launch_bounds__(256) k_convert_rows(ParseArgs a) {
-  using T = typename ParseOut<OP>::T;
-  T* out = static_cast<T*>(a.out);
-  long long v = 0;
-  for (int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x; r < a.in.rows; r += (int64_t)gridDim.x * kBlock) {
-    const bool ok = row_is_valid(a.in.validity, r);
-    const int64_t o0 = a.in.offsets[r];
-    const T x = parse_row<OP>(a.in.chars + o0, ok ? (int)(a.in.offsets[r + 1] - o0) : 0, ok, a);
-    out[r] = x;
-    v += x != (T)0;
+  const uint8_t* tstr;  // to_bools: the true string on the device (nullptr: none given)
+  int tlen;
+  __device__ __forceinline__ T operator()(const uint8_t* p, int n, bool valid) const {
+    if constexpr (OP == P_BOOL) return valid ? csconv::to_bool_row(p, n, tstr, tlen) : (T)(tstr == nullptr);
+    if (!valid) return (T)0;
+    if constexpr (OP == P_HASH) return csconv::hash_row(p, n);
+    else if constexpr (OP == P_STOI) return csconv::stoi_row(p, n);
+    else if constexpr (OP == P_STOL) return csconv::stol_row(p, n);
+    else if constexpr (OP == P_STOF) return csconv::stof_row(p, n);
+    else if constexpr (OP == P_STOD) return csconv::stod_row(p, n);
+    else if constexpr (OP == P_HTOI) return csconv::htoi_row(p, n);
+    else return csconv::ip2int_row(p, n);
   }
-  const long long t = block_reduce_sum_ll(v);
-  if (threadIdx.x == 0 && t) atomicAdd(a.nonzero, (unsigned long long)t);
-}
-
-// A wave per R-row tile (persistent: each wave walks a contiguous run of tiles, prefetching the next tile's bytes while
-// it parses the current one out of LDS).
-template <int OP>
-__global__ void __launch_bounds__(256) k_convert_tile(ParseArgs a) {
-  using T = typename ParseOut<OP>::T;
-  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-  uint8_t* lds_in = reinterpret_cast<uint8_t*>(smem) + (size_t)wv * a.cap;
-  const ColView& in = a.in;
-  const int R = a.rows_per_tile;
-  T* out = static_cast<T*>(a.out);
-  const long long waves = (long long)gridDim.x * 4;
-  const long long per = (a.ntiles + waves - 1) / waves;
-  long long tile = ((long long)blockIdx.x * 4 + wv) * per;
-  const long long tile_end = min(a.ntiles, tile + per);
-  long long v = 0;
-  if (tile < tile_end) {
-    auto load_offs = [&](long long t) {
-      const long long r0 = t * R;
-      const int nrows = (int)min((long long)R, in.rows - r0);
-      cstile::TileOffs o;
-      o.o0 = in.offsets[r0 + min(lane, nrows)];
-      o.o1 = in.offsets[r0 + min(lane + 1, nrows)];
-      return o;
-    };
-    cstile::TileOffs cur = load_offs(tile);
-    cstile::TileChars pf;
-#pragma unroll
-    for (int j = 0; j < cstile::kPfChunks; ++j) pf.v[j] = make_uint4(0, 0, 0, 0);
-    cstile::issue_chars(in.chars, cstile::rl64(cur.o0, 0), cstile::rl64(cur.o1, 63), lane, pf);
-    for (;;) {
-      const long long r0 = tile * R;
-      const int nrows = (int)min((long long)R, in.rows - r0);
-      const long long g0 = cstile::rl64(cur.o0, 0), g1 = cstile::rl64(cur.o1, 63);
-      const int lead = (int)((uintptr_t)(in.chars + g0) & 15);
-      const int want = (int)(g1 - g0) + lead;  // <= cap: every tile's span fits (checked by the host)
-      cstile::stage_chars(lds_in, want, lane, pf);
-      const bool in_tile = lane < nrows;
-      const bool ok = in_tile && row_is_valid(in.validity, r0 + lane);
-      const int rbeg = (int)(cur.o0 - g0) + lead;
-      const int n = ok ? (int)(cur.o1 - cur.o0) : 0;
-      const bool more = tile + 1 < tile_end;
-      if (more) {  // the next tile's bytes travel while this one is parsed
-        cur = load_offs(tile + 1);
-        cstile::issue_chars(in.chars, cstile::rl64(cur.o0, 0), cstile::rl64(cur.o1, 63), lane, pf);
-      }
-      cstile::wave_lds_fence();
-      if (in_tile) {
-        const T x = parse_row<OP>(lds_in + rbeg, n, ok, a);
-        out[r0 + lane] = x;
-        v += x != (T)0;
-      }
-      cstile::wave_lds_fence();  // (the LDS is restaged next round)
-      if (!more) break;
-      ++tile;
-    }
-  }
-  const long long t = block_reduce_sum_ll(v);
-  if (threadIdx.x == 0 && t) atomicAdd(a.nonzero, (unsigned long long)t);
-}
-
-template <int OP>
-bool parse_tiles(const cs_column* col, ParseArgs a, hipStream_t s) {
-  if (cs::cfg("CS_CONVERT_ROWWISE")) return false;
-  int R = 0;
-  for (int r : {64, 32, 16}) {
-    if (max_span_rows(col, r, s) + 32 <= cstile::kPfBytes) {
-      R = r;
-      break;
-    }
-  }
-  if (!R) return false;
-  a.rows_per_tile = R;
-  a.cap = (int)((max_span_rows(col, R, s) + 48 + 15) & ~(int64_t)15);
-  a.ntiles = (col->rows + R - 1) / R;
-  const size_t lds = (size_t)a.cap * 4;
-  if (lds > 150 * 1024) return false;
-  auto kern = &k_convert_tile<OP>;
-  if (lds > 48 * 1024)
-    CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const unsigned g = resident_grid(reinterpret_cast<const void*>(kern), lds, (a.ntiles + 3) / 4);
-  hipLaunchKernelGGL(kern, dim3(g), dim3(256), lds, s, a);
-  CS_HIP(hipGetLastError());
-  return true;
-}
-
-// results to the caller's buffer (device or host); returns the count of non-zero results
-template <int OP>
-int64_t run_parse(const cs_column* col, void* results, int on_device, const char* true_string, hipStream_t s) {
-  using T = typename ParseOut<OP>::T;
-  const int64_t rows = col->rows;
-  Buf tmp, tb;
-  void* d_out = results;
-  if (!on_device) {
-    tmp = dev_alloc(sizeof(T) * (size_t)rows, s);
-    d_out = tmp->p;
-  }
-  Buf acc = dev_alloc(8, s);
-  CS_HIP(hipMemsetAsync(acc->p, 0, 8, s));
-  ParseArgs a{};
-  a.in = view_of(col);
-  a.out = d_out;
-  a.nonzero = ptr<unsigned long long>(acc);
-  if (OP == P_BOOL && true_string) {
-    a.tlen = (int)strlen(true_string);
-    tb = dev_alloc((size_t)a.tlen + 1, s);
-    CS_HIP(hipMemcpyAsync(tb->p, true_string, (size_t)a.tlen + 1, hipMemcpyHostToDevice, s));
-    a.tstr = ptr<const uint8_t>(tb);
-  }
-  if (parse_tiles<OP>(col, a, s)) {
-    note_route("tile");
-  } else {
-    note_route("rows");
-    hipLaunchKernelGGL(k_convert_rows<OP>, dim3(std::min(blocks_for(rows), 8192u)), dim3(kBlock), 0, s, a);
-    CS_HIP(hipGetLastError());
-  }
-  if (!on_device) CS_HIP(hipMemcpyAsync(results, d_out, sizeof(T) * (size_t)rows, hipMemcpyDeviceToHost, s));
-  int64_t* host = (int64_t*)pinned_scratch(8);
-  CS_HIP(hipMemcpyAsync(host, acc->p, 8, hipMemcpyDeviceToHost, s));
-  CS_HIP(hipStreamSynchronize(s));
-  return host[0];
-}
+};
 
 template <int OP>
 int parse_entry(const cs_column* col, void* results, int on_device, const char* true_string, cs_stream stream, int64_t* count) {
@@ -213,7 +62,16 @@ int parse_entry(const cs_column* col, void* results, int on_device, const char* 
     if (count) *count = -1;  // convert.cu: an empty column or no output array returns -1
     if (!results || col->rows == 0) return;
     require_device();
-    const int64_t n = run_parse<OP>(col, results, on_device, true_string, S(stream));
+    const hipStream_t s = S(stream);
+    ConvertParse<OP> parse{};
+    Buf tb;
+    if (OP == P_BOOL && true_string) {
+      parse.tlen = (int)strlen(true_string);
+      tb = dev_alloc((size_t)parse.tlen + 1, s);
+      CS_HIP(hipMemcpyAsync(tb->p, true_string, (size_t)parse.tlen + 1, hipMemcpyHostToDevice, s));
+      parse.tstr = ptr<const uint8_t>(tb);
+    }
+    const int64_t n = csparse::run_parse(col, parse, results, on_device, s);
     if (count) *count = n;
   });
 }
@@ -235,9 +93,6 @@ struct FormatArgs {
   const uint8_t* tf;  // from_bools: the true string, then the false string
   int tlen, flen;
 };
-__device__ __forceinline__ bool value_valid(const uint8_t* nulls, int64_t r) {
-  return nulls == nullptr || ((nulls[r >> 3] >> (r & 7)) & 1);
-}
 // writes row r's text (at most kMaxNumWidth bytes for the numeric formats) to `buf`, returns its length
 template <int OP>
 __device__ __forceinline__ int format_row(const FormatArgs& a, int64_t r, char* buf) {
@@ -252,7 +107,7 @@ template <int OP>
 __global__ void k_format_len(FormatArgs a, int32_t* __restrict__ lens) {
   for (int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x; r < a.rows; r += (int64_t)gridDim.x * kBlock) {
     int n = -1;
-    if (value_valid(a.nulls, r)) {
+    if (csparse::value_valid(a.nulls, r)) {
       if constexpr (OP == F_BOOLS) {
         n = static_cast<const uint8_t*>(a.values)[r] ? a.tlen : a.flen;
       } else {
@@ -266,7 +121,7 @@ __global__ void k_format_len(FormatArgs a, int32_t* __restrict__ lens) {
 template <int OP>
 __global__ void k_format_write(FormatArgs a, const int64_t* __restrict__ off, uint8_t* __restrict__ chars) {
   for (int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x; r < a.rows; r += (int64_t)gridDim.x * kBlock) {
-    if (!value_valid(a.nulls, r)) continue;
+    if (!csparse::value_valid(a.nulls, r)) continue;
     uint8_t* dst = chars + off[r];
     if constexpr (OP == F_BOOLS) {
       const bool t = static_cast<const uint8_t*>(a.values)[r] != 0;

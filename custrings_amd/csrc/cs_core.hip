@@ -765,6 +765,14 @@ int64_t max_span_rows(const cs_column* c, int per, hipStream_t s) {
   CS_HIP(hipStreamSynchronize(s));
   return host[0];
 }
+TilePlan plan_row_tiles(const cs_column* c, int slack, hipStream_t s, bool outliers) {
+  for (int r : {64, 32, 16}) {
+    const int64_t span = max_span_rows(c, r, s);
+    if (span + slack <= cstile::kPfBytes) return {r, span};
+  }
+  if (outliers && !cs::cfg("CS_NO_OUTLIER_TILES")) return {64, cstile::kPfBytes - 64};
+  return {0, 0};
+}
 // How many 64-row tiles span more than `limit` bytes: a column whose LARGEST tile does not fit a tile kernel's staging
 // buffer may still have all but a few that do (one long row among millions of short ones) -- the tile kernels then take
 // the column and handle the oversize tiles a thread per row themselves, instead of the whole column going row-wise.

@@ -3,11 +3,7 @@
 // tests/test_datetime_cpu.py; the format program is compiled once per call on the host and passed by value in the
 // kernel arguments, the units are a template parameter (every divisor a compile-time constant).
 //
-// Parse (string -> int64 per row), the two routes of the conversions (cs_convert.hip):
-//  - tile: a wave stages the bytes of R = 64 / 32 / 16 consecutive rows in LDS with one coalesced prefetch
-//    (cstile::issue_chars / stage_chars) and each lane parses its row out of LDS;
-//  - rows: a thread per row reading its bytes from memory (columns no tile size fits, and CS_CONVERT_ROWWISE=1).
-//  Both count the non-zero results with one atomic per workgroup.
+// Parse (string -> int64 per row): the tile and row-wise routes of parse_route.h, with csdt::parse_ts_row.
 // Format (int64 -> string): every non-null row is W bytes, W a function of the format and the units alone, so there is
 // no length pass.  Without nulls row r starts at r x W; with nulls at the scan of W x (valid rows per 64-row word) plus
 // W x the valid rows in front of it in its word.  A wave formats its 64 rows -- one contiguous span of the output --
@@ -24,6 +20,7 @@
 #include "cs_internal.h"
 #include "datetime_ops.h"
 #include "device_utils.h"
+#include "parse_route.h"
 #include "tile_utils.h"
 
 using namespace cs;
@@ -34,113 +31,15 @@ namespace {
 
 constexpr int kTsLdsMaxWidth = 256;  // widest row the LDS writer takes: 4 waves x 64 rows x 256 B = 64 KB per workgroup
 
-struct TsParseArgs {
-  ColView in;
-  int64_t* out;
-  unsigned long long* nonzero;
-  int rows_per_tile, cap;  // tile route
-  long long ntiles;
+template <int U>
+struct TsParse {
+  using T = int64_t;
   TsProgram prog;
+  // (the row's bytes end at n: parse_ts_row reads nothing of the neighbour's bytes staged behind it)
+  __device__ __forceinline__ int64_t operator()(const uint8_t* p, int n, bool valid) const {
+    return valid ? csdt::parse_ts_row<U>(p, n, prog) : 0;
+  }
 };
-
-template <int U>
-__global__ void __launch_bounds__(256) k_ts_parse_rows(TsParseArgs a) {
-  long long v = 0;
-  for (int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x; r < a.in.rows; r += (int64_t)gridDim.x * kBlock) {
-    const bool ok = row_is_valid(a.in.validity, r);
-    const int64_t o0 = a.in.offsets[r];
-    const int64_t x = ok ? csdt::parse_ts_row<U>(a.in.chars + o0, (int)(a.in.offsets[r + 1] - o0), a.prog) : 0;
-    a.out[r] = x;
-    v += x != 0;
-  }
-  const long long t = block_reduce_sum_ll(v);
-  if (threadIdx.x == 0 && t) atomicAdd(a.nonzero, (unsigned long long)t);
-}
-
-// A wave per R-row tile, persistent over a contiguous run of tiles, the next tile's bytes in flight while the current
-// one is parsed out of LDS (the staging of k_convert_tile, cs_convert.hip).
-template <int U>
-__global__ void __launch_bounds__(256) k_ts_parse_tile(TsParseArgs a) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-  uint8_t* lds_in = reinterpret_cast<uint8_t*>(smem) + (size_t)wv * a.cap;
-  const ColView& in = a.in;
-  const int R = a.rows_per_tile;
-  const long long waves = (long long)gridDim.x * 4;
-  const long long per = (a.ntiles + waves - 1) / waves;
-  long long tile = ((long long)blockIdx.x * 4 + wv) * per;
-  const long long tile_end = min(a.ntiles, tile + per);
-  long long v = 0;
-  if (tile < tile_end) {
-    auto load_offs = [&](long long t) {
-      const long long r0 = t * R;
-      const int nrows = (int)min((long long)R, in.rows - r0);
-      cstile::TileOffs o;
-      o.o0 = in.offsets[r0 + min(lane, nrows)];
-      o.o1 = in.offsets[r0 + min(lane + 1, nrows)];
-      return o;
-    };
-    cstile::TileOffs cur = load_offs(tile);
-    cstile::TileChars pf;
-#pragma unroll
-    for (int j = 0; j < cstile::kPfChunks; ++j) pf.v[j] = make_uint4(0, 0, 0, 0);
-    cstile::issue_chars(in.chars, cstile::rl64(cur.o0, 0), cstile::rl64(cur.o1, 63), lane, pf);
-    for (;;) {
-      const long long r0 = tile * R;
-      const int nrows = (int)min((long long)R, in.rows - r0);
-      const long long g0 = cstile::rl64(cur.o0, 0), g1 = cstile::rl64(cur.o1, 63);
-      const int lead = (int)((uintptr_t)(in.chars + g0) & 15);
-      const int want = (int)(g1 - g0) + lead;  // <= cap: every tile's span fits (checked by the host)
-      cstile::stage_chars(lds_in, want, lane, pf);
-      const bool in_tile = lane < nrows;
-      const bool ok = in_tile && row_is_valid(in.validity, r0 + lane);
-      const int rbeg = (int)(cur.o0 - g0) + lead;
-      const int n = ok ? (int)(cur.o1 - cur.o0) : 0;
-      const bool more = tile + 1 < tile_end;
-      if (more) {
-        cur = load_offs(tile + 1);
-        cstile::issue_chars(in.chars, cstile::rl64(cur.o0, 0), cstile::rl64(cur.o1, 63), lane, pf);
-      }
-      cstile::wave_lds_fence();
-      if (in_tile) {
-        // (the row's bytes end at n: parse_ts_row reads nothing of the neighbour's bytes staged behind it)
-        const int64_t x = ok ? csdt::parse_ts_row<U>(lds_in + rbeg, n, a.prog) : 0;
-        a.out[r0 + lane] = x;
-        v += x != 0;
-      }
-      cstile::wave_lds_fence();
-      if (!more) break;
-      ++tile;
-    }
-  }
-  const long long t = block_reduce_sum_ll(v);
-  if (threadIdx.x == 0 && t) atomicAdd(a.nonzero, (unsigned long long)t);
-}
-
-template <int U>
-bool ts_parse_tiles(const cs_column* col, TsParseArgs& a, hipStream_t s) {
-  if (cs::cfg("CS_CONVERT_ROWWISE")) return false;
-  int R = 0;
-  for (int r : {64, 32, 16}) {
-    if (max_span_rows(col, r, s) + 32 <= cstile::kPfBytes) {
-      R = r;
-      break;
-    }
-  }
-  if (!R) return false;
-  a.rows_per_tile = R;
-  a.cap = (int)((max_span_rows(col, R, s) + 48 + 15) & ~(int64_t)15);
-  a.ntiles = (col->rows + R - 1) / R;
-  const size_t lds = (size_t)a.cap * 4;
-  if (lds > 150 * 1024) return false;
-  auto kern = &k_ts_parse_tile<U>;
-  if (lds > 48 * 1024)
-    CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const unsigned g = resident_grid(reinterpret_cast<const void*>(kern), lds, (a.ntiles + 3) / 4);
-  hipLaunchKernelGGL(kern, dim3(g), dim3(256), lds, s, a);
-  CS_HIP(hipGetLastError());
-  return true;
-}
 
 void compile_or_fail(const char* format, int units, TsProgram* prog, const char* what) {
   switch (csdt::compile_ts_format(format, units, prog)) {
@@ -153,35 +52,9 @@ void compile_or_fail(const char* format, int units, TsProgram* prog, const char*
 }
 
 int64_t run_ts_parse(const cs_column* col, const TsProgram& prog, int64_t* results, int on_device, hipStream_t s) {
-  const int64_t rows = col->rows;
-  Buf tmp;
-  int64_t* d_out = results;
-  if (!on_device) {
-    tmp = dev_alloc(sizeof(int64_t) * (size_t)rows, s);
-    d_out = ptr<int64_t>(tmp);
-  }
-  Buf acc = dev_alloc(8, s);
-  CS_HIP(hipMemsetAsync(acc->p, 0, 8, s));
-  TsParseArgs a{};
-  a.in = view_of(col);
-  a.out = d_out;
-  a.nonzero = ptr<unsigned long long>(acc);
-  a.prog = prog;
-  csdt::ts_dispatch(prog.units, [&](auto u) {
-    constexpr int U = decltype(u)::value;
-    if (ts_parse_tiles<U>(col, a, s)) {
-      note_route("tile");
-    } else {
-      note_route("rows");
-      hipLaunchKernelGGL(k_ts_parse_rows<U>, dim3(std::min(blocks_for(rows), 8192u)), dim3(kBlock), 0, s, a);
-      CS_HIP(hipGetLastError());
-    }
-  });
-  if (!on_device) CS_HIP(hipMemcpyAsync(results, d_out, sizeof(int64_t) * (size_t)rows, hipMemcpyDeviceToHost, s));
-  int64_t* host = (int64_t*)pinned_scratch(8);
-  CS_HIP(hipMemcpyAsync(host, acc->p, 8, hipMemcpyDeviceToHost, s));
-  CS_HIP(hipStreamSynchronize(s));
-  return host[0];
+  int64_t n = 0;
+  csdt::ts_dispatch(prog.units, [&](auto u) { n = csparse::run_parse(col, TsParse<decltype(u)::value>{prog}, results, on_device, s); });
+  return n;
 }
 
 // ---- format ------------------------------------------------------------------------------------------------------------
@@ -195,10 +68,6 @@ struct TsFormatArgs {
   int lds_stride;             // LDS writer: bytes per wave
   TsProgram prog;
 };
-
-__device__ __forceinline__ bool ts_value_valid(const uint8_t* nulls, int64_t r) {
-  return nulls == nullptr || ((nulls[r >> 3] >> (r & 7)) & 1);
-}
 
 // W x the valid rows of every 64-row word (the caller's mask is (rows + 7) / 8 bytes: nothing past it is read)
 __global__ void k_ts_word_bytes(const uint8_t* __restrict__ nulls, int64_t rows, int width, int32_t* __restrict__ out) {
@@ -225,7 +94,7 @@ __global__ void __launch_bounds__(256) k_ts_format(TsFormatArgs a, Off* __restri
   for (int64_t w = (int64_t)blockIdx.x * 4 + wv; w < words; w += (int64_t)gridDim.x * 4) {
     const int64_t r = w * 64 + lane;
     const bool in = r < a.rows;
-    const bool valid = in && ts_value_valid(a.nulls, r);
+    const bool valid = in && csparse::value_valid(a.nulls, r);
     const uint64_t mask = __ballot(valid);
     const int rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
     const int64_t base = a.word_base ? a.word_base[w] : w * 64 * W;

@@ -190,6 +190,26 @@ bool few_spans64_over(const cs_column* c, int64_t limit, hipStream_t s);  // all
 // Workgroups (256 threads, `lds` dynamic bytes) of `kern` resident at once on the device,
 // capped by `wanted`: grid size of the persistent tile kernels.
 unsigned resident_grid(const void* kern, size_t lds, int64_t wanted);
+// Launches a persistent kernel (256 threads, `lds` dynamic bytes -- above 48 KB the kernel's limit is raised) on the
+// grid resident_grid gives it; returns that grid.
+template <class... P, class... A>
+unsigned launch_resident(void (*kern)(P...), size_t lds, int64_t wanted, hipStream_t s, const A&... args) {
+  const void* k = reinterpret_cast<const void*>(kern);
+  if (lds > 48 * 1024) CS_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const unsigned grid = resident_grid(k, lds, wanted);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, args...);
+  CS_HIP(hipGetLastError());
+  return grid;
+}
+// Rows per tile of the row-tile kernels: the largest R of 64 / 32 / 16 whose widest R-row tile, plus `slack` bytes, fits
+// the prefetch registers (cstile::kPfBytes), and that tile's span; R = 0 when none fits.  With `outliers` a column no R
+// fits still gets 64-row tiles sized for all but a few (the kernel takes a tile beyond the staging size straight from
+// memory), unless CS_NO_OUTLIER_TILES is set.
+struct TilePlan {
+  int R;
+  int64_t span;
+};
+TilePlan plan_row_tiles(const cs_column* c, int slack, hipStream_t s, bool outliers = false);
 }  // namespace cs
 namespace csrow {
 struct CharSet;

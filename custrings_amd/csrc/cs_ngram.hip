@@ -299,15 +299,10 @@ bool ngrams_fast(const cs_column* tokens, int n, const unsigned char* sep, int s
   const size_t rel_bytes = ((size_t)(64 * M + n + 1) * 4 + 15) & ~(size_t)15;
   const size_t lds = 288 + (rel_bytes + (size_t)a.cap_in + (size_t)a.cap_out) * 4;
   if (lds > 150 * 1024) return false;
-  if (lds > 48 * 1024)
-    CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ngram_tile), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)lds));
   {
-    const unsigned g = resident_grid(reinterpret_cast<const void*>(&k_ngram_tile), lds, (a.ntiles + 3) / 4);
     ProfScope ps("k_ngram_write", s);
-    hipLaunchKernelGGL(k_ngram_tile, dim3(g), dim3(256), lds, s, a);
+    launch_resident(&k_ngram_tile, lds, (a.ntiles + 3) / 4, s, a);
   }
-  CS_HIP(hipGetLastError());
   unsigned* h = (unsigned*)pinned_scratch(sizeof(unsigned));
   CS_HIP(hipMemcpyAsync(h, err->p, sizeof(unsigned), hipMemcpyDeviceToHost, s));
   CS_HIP(hipStreamSynchronize(s));

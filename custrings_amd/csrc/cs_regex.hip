@@ -3148,9 +3148,6 @@ void scan(const cs_column* col, cs_regex* re, uint8_t* out8, int32_t* out32, int
       if (bits_form) kern = chain_global ? &k_tdfa_scan_stream<MODE == 2 ? 2 : 0, false, false, true, true, true> : &k_tdfa_scan_stream<MODE == 2 ? 2 : 0, true, false, true, true, true>;
       note_route(bits_form ? "bits" : wide ? "wide" : chain_scan ? "chain" : units ? "units" : "plain");
       if (wide) kern = tc.lng ? &k_tdfa_scan_stream<MODE + 7, true, true> : &k_tdfa_scan_stream<MODE + 7, true, false>;
-      if (lds > 48 * 1024)
-        CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      const unsigned grid = resident_grid(reinterpret_cast<const void*>(kern), lds, (sa.nsub + 3) / 4);
       Buf later, nlater;
       if (put_off) {
         sa.deferred_cap = (unsigned)std::min<int64_t>(col->rows, col->rows / 8 + 4096);
@@ -3162,7 +3159,7 @@ void scan(const cs_column* col, cs_regex* re, uint8_t* out8, int32_t* out32, int
       }
       {
         ProfScope ps(name, s);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, sa);
+        launch_resident(kern, lds, (sa.nsub + 3) / 4, s, sa);
       }
       streamed = true;
       if (put_off) {
@@ -3662,13 +3659,6 @@ int cs_replace_re(const cs_column* col, const cs_regex* cre, const char* repl, i
                         : &k_tdfa_replace_stream<true, false, false, true, false, true, cstile::kPfChunks, false, false, false, false, false, false>;
         note_route(bits_form ? "bits" : bchain ? "brefs-chain" : brefs ? "brefs" : literal ? "literal" : wide_stream ? "wide" : units ? (((re->tdfa[30] >> 16) & 15) != 0 ? "chain" : "units") : "plain");
         if (with_holes) note_route_put_off();
-        if (lds1 > 48 * 1024)
-          CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)lds1));
-        const unsigned grid = resident_grid(reinterpret_cast<const void*>(kern), lds1, (nsub1 + 3) / 4);
-        if (cs::cfg("CS_STREAM_INFO"))
-          fprintf(stderr, "replace stream: grid %u lds %zu (tables %zu, tile %d + %d) rows/tile %d units %d chain %d wide %d brefs %d roomy %d growth %d rb %d\n", grid, lds1, tbl_lds + gt_bytes, cap, cap_out,
-                  tc.R, (int)units, bchain ? 3 : chain_form ? (chain_global ? 2 : 1) : 0, (int)wide_stream, (int)brefs, (int)roomy, (int)growth, rb);
 #if defined(CS_PHASE_PROF)
         Buf tracebuf;
         const long long ntrace = (nsub1 >> 10) + 1;
@@ -3682,11 +3672,14 @@ int cs_replace_re(const cs_column* col, const cs_regex* cre, const char* repl, i
           CS_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(cstile::g_tile_trace), &tp_, sizeof(tp_), 0, hipMemcpyHostToDevice, s));
         }
 #endif
+        unsigned grid;
         {
           ProfScope ps("k_replace_re", s);
-          hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds1, s, sa);
+          grid = launch_resident(kern, lds1, (nsub1 + 3) / 4, s, sa);
         }
-        CS_HIP(hipGetLastError());
+        if (cs::cfg("CS_STREAM_INFO"))
+          fprintf(stderr, "replace stream: grid %u lds %zu (tables %zu, tile %d + %d) rows/tile %d units %d chain %d wide %d brefs %d roomy %d growth %d rb %d\n", grid, lds1, tbl_lds + gt_bytes, cap, cap_out,
+                  tc.R, (int)units, bchain ? 3 : chain_form ? (chain_global ? 2 : 1) : 0, (int)wide_stream, (int)brefs, (int)roomy, (int)growth, rb);
         int64_t* host = (int64_t*)pinned_scratch(24);
         CS_HIP(hipMemcpyAsync(host, ptr<int64_t>(out_off) + rows, 8, hipMemcpyDeviceToHost, s));
         CS_HIP(hipMemcpyAsync(host + 1, sa.error, 4, hipMemcpyDeviceToHost, s));
@@ -4008,11 +4001,8 @@ int cs_extract(const cs_column* col, const cs_regex* cre, cs_stream stream, cs_c
         sa.gtags = ptr<const int32_t>(re->d_gtags);
         auto kern = tc.lng ? &k_tdfa_scan_stream<4, true, true> : &k_tdfa_scan_stream<4, true, false>;
         if (chain_form) kern = chain_mem ? &k_tdfa_scan_stream<4, false, false, true, true> : &k_tdfa_scan_stream<4, true, false, true, true>;
-        if (lds > 48 * 1024)
-          CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        const unsigned sgrid = resident_grid(reinterpret_cast<const void*>(kern), lds, (sa.nsub + 3) / 4);
         ProfScope ps("k_extract_spans", s);
-        hipLaunchKernelGGL(kern, dim3(sgrid), dim3(256), lds, s, sa);
+        launch_resident(kern, lds, (sa.nsub + 3) / 4, s, sa);
         streamed = true;
       }
     }
@@ -4161,9 +4151,6 @@ int cs_findall(const cs_column* col, const cs_regex* cre, cs_stream stream, cs_c
         if (units) kern = &k_tdfa_scan_stream<3, true, false, true>;
         if (chain_scan) kern = &k_tdfa_scan_stream<3, true, false, true, true>;  // (a chain pattern on a column whose sample is plain ASCII)
         if (chain_global) kern = &k_tdfa_scan_stream<3, false, false, true, true>;
-        if (lds > 48 * 1024)
-          CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        const unsigned grid = resident_grid(reinterpret_cast<const void*>(kern), lds, (sa.nsub + 3) / 4);
         int width = kProvisional;
         for (int pass = 0; pass < 2; ++pass) {
           // (the provisional pass on 64-row tiles leaves packed spans and tile totals: k_spans_write_tile2 needs no pass
@@ -4184,9 +4171,8 @@ int cs_findall(const cs_column* col, const cs_regex* cre, cs_stream stream, cs_c
           sa.ncols = width;
           {
             ProfScope ps("k_findall_spans", s);
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, sa);
+            launch_resident(kern, lds, (sa.nsub + 3) / 4, s, sa);
           }
-          CS_HIP(hipGetLastError());
           ncols = read_max();
           if (ncols <= width) break;
           width = ncols;  // busier rows than provisioned for: once more, exactly
@@ -4365,7 +4351,6 @@ int cs_replace_with_backrefs(const cs_column* col, const cs_regex* cre, const ch
     ScanStreamArgs sa{};
     Buf d_tmpl;
     size_t slds = 0;
-    unsigned sgrid = 0;
     bool lng = false, stream = false;
     if (dfa && a.TL.in_lds && !cs::cfg("CS_REGEX_ROWWISE")) {
       const TileChoice tc = choose_tile(col, s);
@@ -4396,12 +4381,9 @@ int cs_replace_with_backrefs(const cs_column* col, const cs_regex* cre, const ch
         CS_HIP(hipMemsetAsync(scnt->p, 0, 8, s));
         sa.found = ptr<unsigned long long>(scnt);
       }
-      const void* kern = write ? (lng ? (const void*)&k_tdfa_scan_stream<6, true, true> : (const void*)&k_tdfa_scan_stream<6, true, false>)
-                               : (lng ? (const void*)&k_tdfa_scan_stream<5, true, true> : (const void*)&k_tdfa_scan_stream<5, true, false>);
-      if (slds > 48 * 1024) CS_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)slds));
-      sgrid = resident_grid(kern, slds, (sa.nsub + 3) / 4);
-      void* args[] = {&sa};
-      CS_HIP(hipLaunchKernel(kern, dim3(sgrid), dim3(256), args, slds, s));
+      auto kern = write ? (lng ? &k_tdfa_scan_stream<6, true, true> : &k_tdfa_scan_stream<6, true, false>)
+                        : (lng ? &k_tdfa_scan_stream<5, true, true> : &k_tdfa_scan_stream<5, true, false>);
+      launch_resident(kern, slds, (sa.nsub + 3) / 4, s, sa);
     };
     auto o = std::make_unique<cs_column>();
     o->rows = rows;

@@ -40,48 +40,21 @@ __global__ void __launch_bounds__(256) k_strip_tile(StripTileArgs a) {
   uint8_t* lds_in = reinterpret_cast<uint8_t*>(smem) + (size_t)wv * 2 * a.cap;
   uint8_t* lds_out = lds_in + a.cap;
   const ColView& in = a.in;
-  const int R = a.rows_per_tile;
-  const long long waves = (long long)gridDim.x * 4;
-  const long long per = (a.ntiles + waves - 1) / waves;
-  long long tile = ((long long)blockIdx.x * 4 + wv) * per;
-  const long long tile_end = min(a.ntiles, tile + per);
-  if (tile >= tile_end) return;
-  auto load_offs = [&](long long t) {
-    const long long r0 = t * R;
-    const int nrows = (int)min((long long)R, in.rows - r0);
-    cstile::TileOffs o;
-    o.o0 = in.offsets[r0 + min(lane, nrows)];
-    o.o1 = in.offsets[r0 + min(lane + 1, nrows)];
-    return o;
-  };
-  cstile::TileOffs cur = load_offs(tile);
-  cstile::TileOffs nxt = cur;
-  if (tile + 1 < tile_end) nxt = load_offs(tile + 1);
-  cstile::TileChars pf;
-#pragma unroll
-  for (int j = 0; j < cstile::kPfChunks; ++j) pf.v[j] = make_uint4(0, 0, 0, 0);
-  cstile::issue_chars(in.chars, cstile::rl64(cur.o0, 0), cstile::rl64(cur.o1, 63), lane, pf);
+  cstile::RowTileWalk walk(in, a.rows_per_tile, a.ntiles, wv, lane);
+  if (walk.done()) return;
   for (;;) {
-    const long long r0 = tile * R;
-    const int nrows = (int)min((long long)R, in.rows - r0);
-    const long long g0 = cstile::rl64(cur.o0, 0), g1 = cstile::rl64(cur.o1, 63);
-    const bool live = lane < nrows && row_is_valid(in.validity, r0 + lane);
-    const int rbeg = (int)(cur.o0 - g0);
-    const int n = live ? (int)(cur.o1 - cur.o0) : 0;
-    const int lead = (int)((uintptr_t)(in.chars + g0) & 15);
-    const long long want64 = g1 - g0 + lead;
+    const cstile::RowTile cur = walk.current();
+    const long long r0 = cur.r0, g0 = cur.g0;
+    const int nrows = cur.nrows, rbeg = cur.rbeg, n = cur.n, lead = cur.lead;
+    const bool live = cur.live;
+    const long long want64 = cur.g1 - g0 + lead;
     const bool oversize = want64 + 48 > a.cap;  // (the host sized the buffers for all but a few tiles: a long row among short ones)
     const int want = oversize ? 0 : (int)want64;
-    cstile::stage_chars(lds_in, want, lane, pf);
+    cstile::stage_chars(lds_in, want, lane, walk.pf);
     // output extents of the tile's rows (the size pass and the scan already ran)
     const long long oo0 = a.out_off[r0 + min(lane, nrows)];
     const long long oo1 = a.out_off[r0 + min(lane + 1, nrows)];
-    const bool has_next = tile + 1 < tile_end;
-    if (has_next) {
-      cur = nxt;
-      cstile::issue_chars(in.chars, cstile::rl64(cur.o0, 0), cstile::rl64(cur.o1, 63), lane, pf);
-      if (tile + 2 < tile_end) nxt = load_offs(tile + 2);
-    }
+    const bool has_next = walk.advance();
     cstile::wave_lds_fence();
     if (oversize) {
       // straight from memory: a short row by its lane, a long one by the whole wave (a byte a lane)
@@ -99,7 +72,6 @@ __global__ void __launch_bounds__(256) k_strip_tile(StripTileArgs a) {
         for (int i = lane; i < L; i += 64) a.out_chars[dst + i] = in.chars[src + i];
       }
       if (!has_next) break;
-      ++tile;
       continue;
     }
     const long long ob = cstile::rl64(oo0, 0), oe = cstile::rl64(oo1, 63);
@@ -112,7 +84,6 @@ __global__ void __launch_bounds__(256) k_strip_tile(StripTileArgs a) {
     cstile::wave_flush_shift(a.out_chars + ob, (int)(oe - ob), lds_out, lane);
     cstile::wave_lds_fence();
     if (!has_next) break;
-    ++tile;
   }
 }
 
@@ -147,42 +118,20 @@ __global__ void __launch_bounds__(256) k_find_tile(FindTileArgs a) {
   uint32_t* bm_first = reinterpret_cast<uint32_t*>(lds_in + a.cap);                 // byte == needle[0]
   uint32_t* bm_cont = reinterpret_cast<uint32_t*>(lds_in + a.cap + kBitmapBytes);   // byte is 10xxxxxx
   const ColView& in = a.in;
-  const int R = a.rows_per_tile;
-  const long long waves = (long long)gridDim.x * 4;
-  const long long per = (a.ntiles + waves - 1) / waves;
-  long long tile = ((long long)blockIdx.x * 4 + wv) * per;
-  const long long tile_end = min(a.ntiles, tile + per);
-  if (tile >= tile_end) return;
-  auto load_offs = [&](long long t) {
-    const long long r0 = t * R;
-    const int nrows = (int)min((long long)R, in.rows - r0);
-    cstile::TileOffs o;
-    o.o0 = in.offsets[r0 + min(lane, nrows)];
-    o.o1 = in.offsets[r0 + min(lane + 1, nrows)];
-    return o;
-  };
-  cstile::TileOffs cur = load_offs(tile);
-  cstile::TileOffs nxt = cur;
-  if (tile + 1 < tile_end) nxt = load_offs(tile + 1);
-  cstile::TileChars pf;
-#pragma unroll
-  for (int j = 0; j < cstile::kPfChunks; ++j) pf.v[j] = make_uint4(0, 0, 0, 0);
-  cstile::issue_chars(in.chars, cstile::rl64(cur.o0, 0), cstile::rl64(cur.o1, 63), lane, pf);
+  cstile::RowTileWalk walk(in, a.rows_per_tile, a.ntiles, wv, lane);
+  if (walk.done()) return;
   const uint32_t first4 = (uint32_t)a.needle[0] * 0x01010101u;
   // bits 0..3: which bytes of w are zero (exact, no borrow between bytes)
   auto zero4 = [](uint32_t w) { return cstile::gather_bit7(~(((w & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | w) & 0x80808080u); };
   auto cont4 = [](uint32_t w) { return cstile::gather_bit7(w & ~(w << 1) & 0x80808080u); };
   int hits = 0;
   for (;;) {
-    const long long r0 = tile * R;
-    const int nrows = (int)min((long long)R, in.rows - r0);
-    const long long g0 = cstile::rl64(cur.o0, 0), g1 = cstile::rl64(cur.o1, 63);
-    const bool in_tile = lane < nrows;
-    const bool live = in_tile && row_is_valid(in.validity, r0 + lane);
-    const int rbeg = (int)(cur.o0 - g0);
-    const int n = live ? (int)(cur.o1 - cur.o0) : 0;
-    const int lead = (int)((uintptr_t)(in.chars + g0) & 15);
-    const int want = (int)(g1 - g0) + lead;
+    const cstile::RowTile cur = walk.current();
+    const long long r0 = cur.r0;
+    const int rbeg = cur.rbeg, n = cur.n, lead = cur.lead;
+    const bool in_tile = cur.in_tile, live = cur.live;
+    const int want = (int)(cur.g1 - cur.g0) + lead;
+    const cstile::TileChars& pf = walk.pf;
     cstile::stage_chars(lds_in, want, lane, pf);
     // (a search over a character window is a search over a byte window when the tile is ASCII)
     bool by_bits = a.nb > 0 && !__any(n > 96);
@@ -210,12 +159,7 @@ __global__ void __launch_bounds__(256) k_find_tile(FindTileArgs a) {
           }
         }
     }
-    const bool has_next = tile + 1 < tile_end;
-    if (has_next) {
-      cur = nxt;
-      cstile::issue_chars(in.chars, cstile::rl64(cur.o0, 0), cstile::rl64(cur.o1, 63), lane, pf);
-      if (tile + 2 < tile_end) nxt = load_offs(tile + 2);
-    }
+    const bool has_next = walk.advance();
     cstile::wave_lds_fence();
     const uint8_t* p = lds_in + lead + rbeg;
     int at = -1;  // byte offset of the first occurrence (by_bits)
@@ -273,7 +217,6 @@ __global__ void __launch_bounds__(256) k_find_tile(FindTileArgs a) {
     }
     cstile::wave_lds_fence();
     if (!has_next) break;
-    ++tile;
   }
   const int t = wave_reduce_sum(hits);
   if (lane == 0 && t) atomicAdd(a.found, (unsigned long long)t);
@@ -328,25 +271,17 @@ __global__ void __launch_bounds__(256) k_strip_stream(StripStreamArgs a) {
     return t;
   };
   auto tile_of = [&](unsigned long long t) -> long long { return cstile::rl64((long long)t, 0) * K + key; };
-  auto load_offs = [&](long long t) {
-    const long long r0 = t * 64;
-    const int nrows = (int)min(64ll, in.rows - r0);
-    cstile::TileOffs o;
-    o.o0 = in.offsets[r0 + min(lane, nrows)];
-    o.o1 = in.offsets[r0 + min(lane + 1, nrows)];
-    return o;
-  };
   // (the first tickets a round trip apart: drawn back to back they are consecutive, and a wave's second and third tile
   // would lie in front of its neighbour's first -- cs_regex.hip, the replace stream kernel)
   long long tile = tile_of(take());
   if (tile >= a.ntiles) return;
-  cstile::TileOffs cur = load_offs(tile);
+  cstile::TileOffs cur = cstile::load_tile_offsets(in.offsets, in.rows, tile, lane);
   cstile::TileChars pf;
 #pragma unroll
   for (int j = 0; j < cstile::kPfChunks; ++j) pf.v[j] = make_uint4(0, 0, 0, 0);
   cstile::issue_chars(in.chars, cstile::rl64(cur.o0, 0), cstile::rl64(cur.o1, 63), lane, pf);
   long long t_nxt = tile_of(take());
-  cstile::TileOffs nxt = load_offs(t_nxt < a.ntiles ? t_nxt : a.ntiles - 1);
+  cstile::TileOffs nxt = cstile::load_tile_offsets(in.offsets, in.rows, t_nxt < a.ntiles ? t_nxt : a.ntiles - 1, lane);
   unsigned long long pending = take();
   // the tile before: assembled in the out tile, finished (offsets, flush) one iteration later -- when its prefix has had
   // this tile's staging and sizing to arrive in
@@ -396,7 +331,7 @@ __global__ void __launch_bounds__(256) k_strip_stream(StripStreamArgs a) {
     // (assigned unconditionally, handed to the loop-carried variables at the bottom: cs_regex.hip on why)
     const long long t_nn = tile_of(pending);
     const unsigned long long pending_new = take();
-    const cstile::TileOffs nn = load_offs(t_nn < a.ntiles ? t_nn : a.ntiles - 1);
+    const cstile::TileOffs nn = cstile::load_tile_offsets(in.offsets, in.rows, t_nn < a.ntiles ? t_nn : a.ntiles - 1, lane);
     const bool has_next = t_nxt < a.ntiles;
     const uint8_t* gp = in.chars + (g0 + rbeg);
     if (has_next) {
@@ -462,13 +397,8 @@ namespace cs {
 bool find_tiles(const cs_column* in, const unsigned char* needle, int nb, int mode, int start, int end, int32_t* out32,
                 uint8_t* out8, unsigned long long* found, hipStream_t s) {
   if (in->rows == 0 || nb > 64 || cs::cfg("CS_FIND_ROWWISE")) return false;
-  int R = 0;
-  for (int r : {64, 32, 16}) {
-    if (max_span_rows(in, r, s) + 32 <= cstile::kPfBytes) {
-      R = r;
-      break;
-    }
-  }
+  const TilePlan tp = plan_row_tiles(in, 32, s);
+  const int R = tp.R;
   if (!R) return false;
   FindTileArgs a{};
   a.in = view_of(in);
@@ -477,7 +407,7 @@ bool find_tiles(const cs_column* in, const unsigned char* needle, int nb, int mo
   a.start = start;
   a.end = end;
   a.rows_per_tile = R;
-  a.cap = (int)((max_span_rows(in, R, s) + 48 + 15) & ~(int64_t)15);
+  a.cap = (int)((tp.span + 48 + 15) & ~(int64_t)15);
   a.ntiles = (in->rows + R - 1) / R;
   a.out32 = out32;
   a.out8 = out8;
@@ -485,52 +415,31 @@ bool find_tiles(const cs_column* in, const unsigned char* needle, int nb, int mo
   a.whole = mode != 0 || (start <= 0 && end - (start < 0 ? 0 : start) < 0);
   const size_t lds = ((size_t)a.cap + 2 * (cstile::kPfBytes / 8 + 32)) * 4;
   if (lds > 150 * 1024) return false;
-  auto launch = [&](auto kern) {
-    if (lds > 48 * 1024)
-      CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const unsigned g = resident_grid(reinterpret_cast<const void*>(kern), lds, (a.ntiles + 3) / 4);
-    hipLaunchKernelGGL(kern, dim3(g), dim3(256), lds, s, a);
-  };
-  if (mode == 0) launch(&k_find_tile<0>);
-  else launch(&k_find_tile<1>);
-  CS_HIP(hipGetLastError());
+  launch_resident(mode == 0 ? &k_find_tile<0> : &k_find_tile<1>, lds, (a.ntiles + 3) / 4, s, a);
   return true;
 }
 
 bool strip_write_tiles(const cs_column* in, const CharSet& set, int side, const int64_t* out_off, uint8_t* out_chars,
                        hipStream_t s) {
   if (in->rows == 0 || cs::cfg("CS_STRIP_ROWWISE")) return false;
-  int R = 0;
-  for (int r : {64, 32, 16}) {
-    if (max_span_rows(in, r, s) + 32 <= cstile::kPfBytes) {
-      R = r;
-      break;
-    }
-  }
-  int64_t span = R ? max_span_rows(in, R, s) : 0;
-  if (!R && !cs::cfg("CS_NO_OUTLIER_TILES")) {
-    R = 64;  // no tile size fits every tile: the kernel copies the rows of a tile beyond the staging size straight from memory, long rows by the whole wave
-    span = cstile::kPfBytes - 64;
-  }
+  // (no tile size fits every tile: the kernel copies the rows of a tile beyond the staging size straight from memory, long
+  // rows by the whole wave)
+  const TilePlan tp = plan_row_tiles(in, 32, s, true);
+  const int R = tp.R;
   if (!R) return false;
   StripTileArgs a{};
   a.in = view_of(in);
   a.set = set;
   a.side = side;
   a.rows_per_tile = R;
-  a.cap = (int)((span + 48 + 15) & ~(int64_t)15);
+  a.cap = (int)((tp.span + 48 + 15) & ~(int64_t)15);
   a.ntiles = (in->rows + R - 1) / R;
   a.out_off = out_off;
   a.out_chars = out_chars;
   const size_t lds = (size_t)a.cap * 2 * 4;
   if (lds > 150 * 1024) return false;
-  if (lds > 48 * 1024)
-    CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_strip_tile), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)lds));
-  const unsigned g = resident_grid(reinterpret_cast<const void*>(&k_strip_tile), lds, (a.ntiles + 3) / 4);
   ProfScope ps("k_strip_write", s);
-  hipLaunchKernelGGL(k_strip_tile, dim3(g), dim3(256), lds, s, a);
-  CS_HIP(hipGetLastError());
+  launch_resident(&k_strip_tile, lds, (a.ntiles + 3) / 4, s, a);
   return true;
 }
 

@@ -88,44 +88,18 @@ __global__ void __launch_bounds__(256) k_runs_tile(RunsArgs a) {
   }
   __syncthreads();
   const ColView& in = a.in;
-  const int R = a.rows_per_tile, rb = a.rb;
-  const long long waves = (long long)gridDim.x * 4;
-  const long long per = (a.ntiles + waves - 1) / waves;
-  long long tile = ((long long)blockIdx.x * 4 + wv) * per;
-  const long long tile_end = min(a.ntiles, tile + per);
-  if (tile >= tile_end) return;
-  auto load_offs = [&](long long t) {
-    const long long r0 = t * R;
-    const int nrows = (int)min((long long)R, in.rows - r0);
-    cstile::TileOffs o;
-    o.o0 = in.offsets[r0 + min(lane, nrows)];
-    o.o1 = in.offsets[r0 + min(lane + 1, nrows)];
-    return o;
-  };
-  cstile::TileOffs cur = load_offs(tile);
-  cstile::TileOffs nxt = cur;
-  if (tile + 1 < tile_end) nxt = load_offs(tile + 1);
-  cstile::TileChars pf;
-#pragma unroll
-  for (int j = 0; j < cstile::kPfChunks; ++j) pf.v[j] = make_uint4(0, 0, 0, 0);
-  cstile::issue_chars(in.chars, cstile::rl64(cur.o0, 0), cstile::rl64(cur.o1, 63), lane, pf);
+  const int rb = a.rb;
+  cstile::RowTileWalk walk(in, a.rows_per_tile, a.ntiles, wv, lane);
+  if (walk.done()) return;
   int most = 0, hit_rows = 0;
   for (;;) {
-    const long long r0 = tile * R;
-    const int nrows = (int)min((long long)R, in.rows - r0);
-    const long long g0 = cstile::rl64(cur.o0, 0), g1 = cstile::rl64(cur.o1, 63);
-    const bool live = lane < nrows && row_is_valid(in.validity, r0 + lane);
-    const int rbeg = (int)(cur.o0 - g0);
-    const int n = live ? (int)(cur.o1 - cur.o0) : 0;
-    const int lead = (int)((uintptr_t)(in.chars + g0) & 15);
-    const int want = (int)(g1 - g0) + lead;  // (the host sized R so that every tile fits the prefetch registers)
-    const cstile::TileChars q = pf;
-    const bool has_next = tile + 1 < tile_end;
-    if (has_next) {
-      cur = nxt;
-      cstile::issue_chars(in.chars, cstile::rl64(cur.o0, 0), cstile::rl64(cur.o1, 63), lane, pf);
-      if (tile + 2 < tile_end) nxt = load_offs(tile + 2);
-    }
+    const cstile::RowTile cur = walk.current();
+    const long long r0 = cur.r0, g0 = cur.g0;
+    const int nrows = cur.nrows, rbeg = cur.rbeg, n = cur.n, lead = cur.lead;
+    const bool live = cur.live;
+    const int want = (int)(cur.g1 - g0) + lead;  // (the host sized R so that every tile fits the prefetch registers)
+    const cstile::TileChars q = walk.pf;
+    const bool has_next = walk.advance();
     // row-start bitmap: one bit per byte of the staged span, set by the row lanes
     for (int i = lane * 16; i < kBitmapBytes; i += 64 * 16) *reinterpret_cast<uint4*>(base + i) = make_uint4(0, 0, 0, 0);
     cstile::wave_lds_fence();
@@ -265,7 +239,6 @@ __global__ void __launch_bounds__(256) k_runs_tile(RunsArgs a) {
       if (PASS == 0 && lane < nrows) a.lens[r0 + lane] = len;
       cstile::wave_lds_fence();
       if (!has_next) break;
-      ++tile;
       continue;
     }
     if (lane == 0) {  // the position one past the staged span (a row that ends there reads it)
@@ -310,7 +283,6 @@ __global__ void __launch_bounds__(256) k_runs_tile(RunsArgs a) {
     }
     cstile::wave_lds_fence();  // the next tile reuses the tables
     if (!has_next) break;
-    ++tile;
   }
   if (PASS == 0 && lane == 0 && most > __hip_atomic_load(a.maxima, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(a.maxima, most);
   if (PASS == 0 && lane == 0 && hit_rows) atomicAdd(a.maxima + 1, hit_rows);
@@ -323,13 +295,7 @@ namespace cs {
 // what both entry points share: the tile size the column's spans allow, the class description out of the bit program
 static bool runs_setup(const cs_column* col, const int32_t* d_bits, const std::vector<int32_t>& bits, hipStream_t s, RunsArgs& a) {
   const int64_t rows = col->rows;
-  int R = 0;
-  for (int r : {64, 32, 16}) {
-    if (max_span_rows(col, r, s) + 16 <= cstile::kPfBytes) {
-      R = r;
-      break;
-    }
-  }
+  const int R = plan_row_tiles(col, 16, s).R;
   if (!R) return false;
   a.in = view_of(col);
   a.rows_per_tile = R;
@@ -359,11 +325,9 @@ bool count_class_runs(const cs_column* col, const int32_t* d_bits, const std::ve
   a.maxima = ptr<int>(maxima);
   const size_t lds0 = 512 + kRunsWave0 * 4;
   {
-    const unsigned g0 = resident_grid(reinterpret_cast<const void*>(&k_runs_tile<0>), lds0, (a.ntiles + 3) / 4);
     ProfScope ps("k_runs_count", s);
-    hipLaunchKernelGGL(k_runs_tile<0>, dim3(g0), dim3(256), lds0, s, a);
+    launch_resident(&k_runs_tile<0>, lds0, (a.ntiles + 3) / 4, s, a);
   }
-  CS_HIP(hipGetLastError());
   int* host = (int*)pinned_scratch(2 * sizeof(int));
   CS_HIP(hipMemcpyAsync(host, maxima->p, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
   CS_HIP(hipStreamSynchronize(s));
@@ -386,11 +350,9 @@ bool replace_class_runs(const cs_column* col, const int32_t* d_bits, const std::
   a.maxima = ptr<int>(maxima);
   {
     const size_t lds0 = 512 + kRunsWave0 * 4;
-    const unsigned g0 = resident_grid(reinterpret_cast<const void*>(&k_runs_tile<0>), lds0, (a.ntiles + 3) / 4);
     ProfScope ps("k_runs_size", s);
-    hipLaunchKernelGGL(k_runs_tile<0>, dim3(g0), dim3(256), lds0, s, a);
+    launch_resident(&k_runs_tile<0>, lds0, (a.ntiles + 3) / 4, s, a);
   }
-  CS_HIP(hipGetLastError());
   // the largest output tile decides whether the write pass fits the LDS -- known right after the size pass: a column that
   // does not fit (a 16-byte replacement for `.` on dense rows) leaves HERE, before the offsets scan and before its
   // output is allocated (it used to find out after both)
@@ -415,13 +377,10 @@ bool replace_class_runs(const cs_column* col, const int32_t* d_bits, const std::
   o->chars = dev_alloc((size_t)o->nbytes, s);
   a.out_off = o->d_offsets();
   a.out_chars = ptr<uint8_t>(o->chars);
-  if (lds1 > 48 * 1024) CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_runs_tile<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
   {
-    const unsigned g1 = resident_grid(reinterpret_cast<const void*>(&k_runs_tile<1>), lds1, (a.ntiles + 3) / 4);
     ProfScope ps("k_runs_write", s);
-    hipLaunchKernelGGL(k_runs_tile<1>, dim3(g1), dim3(256), lds1, s, a);
+    launch_resident(&k_runs_tile<1>, lds1, (a.ntiles + 3) / 4, s, a);
   }
-  CS_HIP(hipGetLastError());
   CS_HIP(hipStreamSynchronize(s));
   *out = o.release();
   return true;

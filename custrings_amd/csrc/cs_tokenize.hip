@@ -89,52 +89,23 @@ __global__ void __launch_bounds__(256) k_tok_tile(TokTileArgs a) {
   uint8_t* lds_out = base + kBitmapBytes;
   uint16_t* lds_tok = reinterpret_cast<uint16_t*>(lds_out + (PASS ? a.cap_out : 0));
   const ColView& in = a.in;
-  const int R = a.rows_per_tile;
-  const long long waves = (long long)gridDim.x * 4;
-  const long long per = (a.ntiles + waves - 1) / waves;
-  long long tile = ((long long)blockIdx.x * 4 + wv) * per;
-  const long long tile_end = min(a.ntiles, tile + per);
-  if (tile >= tile_end) return;
-
-  auto load_offs = [&](long long t) {
-    const long long r0 = t * R;
-    const int nrows = (int)min((long long)R, in.rows - r0);
-    cstile::TileOffs o;
-    o.o0 = in.offsets[r0 + min(lane, nrows)];
-    o.o1 = in.offsets[r0 + min(lane + 1, nrows)];
-    return o;
-  };
-  cstile::TileOffs cur = load_offs(tile);
-  cstile::TileOffs nxt = cur;
-  if (tile + 1 < tile_end) nxt = load_offs(tile + 1);
-  cstile::TileChars pf;
-#pragma unroll
-  for (int j = 0; j < cstile::kPfChunks; ++j) pf.v[j] = make_uint4(0, 0, 0, 0);
-  cstile::issue_chars(in.chars, cstile::rl64(cur.o0, 0), cstile::rl64(cur.o1, 63), lane, pf);
+  cstile::RowTileWalk walk(in, a.rows_per_tile, a.ntiles, wv, lane);
+  if (walk.done()) return;
   int most_bytes = 0, most_tokens = 0;
   bool malformed = false;
   for (;;) {
-    const long long r0 = tile * R;
-    const int nrows = (int)min((long long)R, in.rows - r0);
-    const long long g0 = cstile::rl64(cur.o0, 0), g1 = cstile::rl64(cur.o1, 63);
-    const bool live = lane < nrows && row_is_valid(in.validity, r0 + lane);
-    const int rbeg = (int)(cur.o0 - g0);
-    const int n = live ? (int)(cur.o1 - cur.o0) : 0;
-    const int lead = (int)((uintptr_t)(in.chars + g0) & 15);
-    const long long want64 = g1 - g0 + lead;
+    const cstile::RowTile cur = walk.current();
+    const long long tile = cur.tile, g0 = cur.g0;
+    const int rbeg = cur.rbeg, n = cur.n, lead = cur.lead;
+    const long long want64 = cur.g1 - g0 + lead;
     // A tile is taken in SEGMENTS of at most kPfBytes staged bytes: one for the tiles the host sized the kernel for (out of
     // the prefetch registers); a tile beyond that -- a long row among short ones -- is walked segment by segment straight
     // from memory, the keep / row-start state and the running totals carried across (all of it is wave-uniform), so a
     // single long row is still tokenized by the whole wave, sixteen bytes a lane.
     constexpr int kSeg = cstile::kPfChunks * 1024;
     const int nseg = SEGS ? (int)((want64 + kSeg - 1) / kSeg) : 1;
-    const cstile::TileChars q0 = pf;
-    const bool has_next = tile + 1 < tile_end;
-    if (has_next) {
-      cur = nxt;
-      cstile::issue_chars(in.chars, cstile::rl64(cur.o0, 0), cstile::rl64(cur.o1, 63), lane, pf);
-      if (tile + 2 < tile_end) nxt = load_offs(tile + 2);
-    }
+    const cstile::TileChars q0 = walk.pf;
+    const bool has_next = walk.advance();
     long long tile_b = 0, tile_t = 0;  // kept bytes / tokens of the segments before this one
     uint32_t carry_keep = 0;           // was the last byte of the previous chunk row kept?
     uint32_t carry_expect = 0;         // continuation bytes announced into the next chunk row (set mode check)
@@ -243,7 +214,6 @@ __global__ void __launch_bounds__(256) k_tok_tile(TokTileArgs a) {
       }
     }
     if (!has_next) break;
-    ++tile;
   }
   if (PASS == 0 && __any(malformed) && lane == 0) atomicOr(reinterpret_cast<unsigned*>(a.maxima + 2), 1u);
   if (PASS == 0 && lane == 0) {
@@ -261,14 +231,7 @@ bool tokenize_fast(const cs_column* col, const unsigned char* delims, int ndel, 
   if (rows == 0 || ndel > 4 || cs::cfg("CS_TOKENIZE_ROWWISE")) return false;
   for (int k = 0; k < ndel; ++k)
     if (delims[k] == 0 || delims[k] >= 128) return false;
-  // rows per tile: the largest of 64 / 32 / 16 whose widest tile fits the prefetch registers
-  int R = 0;
-  for (int r : {64, 32, 16}) {
-    if (max_span_rows(col, r, s) + 16 <= cstile::kPfBytes) {
-      R = r;
-      break;
-    }
-  }
+  int R = plan_row_tiles(col, 16, s).R;
   // (no tile size fits every tile: 64-row tiles, the oversize ones taken in segments by the kernel -- byte-parallel still)
   bool segs = false;
   if (!R && max_span64(col, s) < ((int64_t)1 << 30) && !cs::cfg("CS_NO_OUTLIER_TILES")) {
@@ -291,12 +254,9 @@ bool tokenize_fast(const cs_column* col, const unsigned char* delims, int ndel, 
   constexpr size_t kBitmapBytes = cstile::kPfBytes / 8 + 32;
   {
     const size_t lds0 = kBitmapBytes * 4;
-    auto k0 = segs ? &k_tok_tile<0, true> : &k_tok_tile<0, false>;
-    const unsigned g0 = resident_grid(reinterpret_cast<const void*>(k0), lds0, (a.ntiles + 3) / 4);
     ProfScope ps("k_tok_count", s);
-    hipLaunchKernelGGL(k0, dim3(g0), dim3(256), lds0, s, a);
+    launch_resident(segs ? &k_tok_tile<0, true> : &k_tok_tile<0, false>, lds0, (a.ntiles + 3) / 4, s, a);
   }
-  CS_HIP(hipGetLastError());
   // per-tile positions in the output chars and in the token sequence
   Buf bases = dev_alloc(sizeof(int64_t) * 2 * (a.ntiles + 1), s);
   int64_t totals[2];
@@ -326,14 +286,10 @@ bool tokenize_fast(const cs_column* col, const unsigned char* delims, int ndel, 
   a.cap_tok = (hmax[1] + 8 + 7) & ~7;
   const size_t lds1 = (kBitmapBytes + (size_t)a.cap_out + 2 * (size_t)a.cap_tok) * 4;
   if (lds1 > 150 * 1024) return false;
-  auto k1 = segs ? &k_tok_tile<1, true> : &k_tok_tile<1, false>;
-  if (lds1 > 48 * 1024) CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k1), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
   {
-    const unsigned g1 = resident_grid(reinterpret_cast<const void*>(k1), lds1, (a.ntiles + 3) / 4);
     ProfScope ps("k_tok_write", s);
-    hipLaunchKernelGGL(k1, dim3(g1), dim3(256), lds1, s, a);
+    launch_resident(segs ? &k_tok_tile<1, true> : &k_tok_tile<1, false>, lds1, (a.ntiles + 3) / 4, s, a);
   }
-  CS_HIP(hipGetLastError());
   // closing offset
   CS_HIP(hipMemcpyAsync(ptr<int64_t>(c->offsets) + ntok, &totals[0], sizeof(int64_t), hipMemcpyHostToDevice, s));
   CS_HIP(hipStreamSynchronize(s));

@@ -365,6 +365,70 @@ __device__ __forceinline__ void wave_lds_fence() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// ---- a wave's walk over R-row tiles (R <= 64) -------------------------------------------
+// The row-tile kernels are persistent: wave w of W = gridDim.x * 4 takes the contiguous tiles
+// [w * per, min(ntiles, (w + 1) * per)), per = ceil(ntiles / W).  While it works on one tile
+// the next tile's chars are in flight in `pf` and the offsets of the one after that are being
+// fetched (the schedule above kPfChunks).  A kernel reads the current tile's bytes out of `pf`
+// (stage_chars, or a copy) BEFORE advance(), which issues the next tile's loads into it.
+struct RowTile {
+  long long tile, r0;  // the tile and its first row
+  int nrows;           // its rows (<= R)
+  long long g0, g1;    // its bytes: chars[g0, g1)
+  int lead;            // (chars + g0) & 15: `pf` holds the bytes from g0 - lead on
+  int rbeg, n;         // this lane's row: chars[g0 + rbeg, g0 + rbeg + n) (n = 0: no row, or a null one)
+  bool in_tile, live;  // lane < nrows; and the row is not null
+};
+struct RowTileWalk {
+  const uint8_t* chars;
+  const int64_t* offsets;
+  const uint8_t* validity;
+  long long rows, tile, tile_end;
+  int R, lane;
+  TileOffs cur, nxt;
+  TileChars pf;
+  // `in`: a column view (chars, offsets, validity, rows); wv: the wave in the workgroup
+  template <class Col>
+  __device__ __forceinline__ RowTileWalk(const Col& in, int rows_per_tile, long long ntiles, int wv, int lane_)
+      : chars(in.chars), offsets(in.offsets), validity(in.validity), rows(in.rows), R(rows_per_tile), lane(lane_) {
+    const long long waves = (long long)gridDim.x * 4;
+    const long long per = (ntiles + waves - 1) / waves;
+    tile = ((long long)blockIdx.x * 4 + wv) * per;
+    tile_end = min(ntiles, tile + per);
+    if (tile >= tile_end) return;
+    cur = load_tile_offsets_r(offsets, rows, tile, R, lane);
+    nxt = cur;
+    if (tile + 1 < tile_end) nxt = load_tile_offsets_r(offsets, rows, tile + 1, R, lane);
+#pragma unroll
+    for (int j = 0; j < kPfChunks; ++j) pf.v[j] = make_uint4(0, 0, 0, 0);
+    issue_chars(chars, rl64(cur.o0, 0), rl64(cur.o1, 63), lane, pf);
+  }
+  __device__ __forceinline__ bool done() const { return tile >= tile_end; }
+  __device__ __forceinline__ RowTile current() const {
+    RowTile t;
+    t.tile = tile;
+    t.r0 = tile * R;
+    t.nrows = (int)min((long long)R, rows - t.r0);
+    t.g0 = rl64(cur.o0, 0);
+    t.g1 = rl64(cur.o1, 63);
+    t.lead = (int)((uintptr_t)(chars + t.g0) & 15);
+    t.in_tile = lane < t.nrows;
+    t.live = t.in_tile && csdev::row_is_valid(validity, t.r0 + lane);
+    t.rbeg = (int)(cur.o0 - t.g0);
+    t.n = t.live ? (int)(cur.o1 - cur.o0) : 0;
+    return t;
+  }
+  // moves to the next tile (false: the wave's run is done): issues its chars, fetches the offsets of the one after
+  __device__ __forceinline__ bool advance() {
+    if (tile + 1 >= tile_end) return false;
+    ++tile;
+    cur = nxt;
+    issue_chars(chars, rl64(cur.o0, 0), rl64(cur.o1, 63), lane, pf);
+    if (tile + 1 < tile_end) nxt = load_tile_offsets_r(offsets, rows, tile + 1, R, lane);
+    return true;
+  }
+};
+
 // Decoupled look-back in two halves so that independent work (assembling the output
 // rows in LDS) runs between publishing this sub-tile's aggregate and needing the
 // predecessors': lookback_begin publishes and issues the first poll, lookback_end
