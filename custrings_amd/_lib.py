@@ -142,6 +142,15 @@ _PROTOS = {
     # timestamps (datetime.cu)
     "cs_timestamp2long": (i32, [vp, cp, i32, vp, i32, vp, P(i64)]),
     "cs_long2timestamp": (i32, [vp, i64, i32, cp, vp, i32, vp, P(vp)]),
+    # substrings / padding / wrapping (substr.cu, pad.cu, modify.cu)
+    "cs_slice": (i32, [vp, i32, i32, i32, vp, P(vp)]),
+    "cs_slice_from": (i32, [vp, vp, vp, i32, vp, P(vp)]),
+    "cs_slice_replace": (i32, [vp, cp, i32, i32, vp, P(vp)]),
+    "cs_insert": (i32, [vp, cp, i32, vp, P(vp)]),
+    "cs_repeat": (i32, [vp, C.c_uint, vp, P(vp)]),
+    "cs_pad": (i32, [vp, C.c_uint, i32, cp, vp, P(vp)]),
+    "cs_zfill": (i32, [vp, C.c_uint, vp, P(vp)]),
+    "cs_wrap": (i32, [vp, C.c_uint, vp, P(vp)]),
     "cs_replace_re": (i32, [vp, vp, cp, i32, vp, P(vp)]),
     "cs_replace_with_backrefs": (i32, [vp, vp, cp, vp, P(vp)]),
     "cs_extract": (i32, [vp, vp, vp, P(P(vp)), P(i32)]),

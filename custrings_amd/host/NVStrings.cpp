@@ -570,3 +570,35 @@ NVStrings* NVStrings::long2timestamp(const unsigned long* values, unsigned int c
   check(cs_long2timestamp(reinterpret_cast<const int64_t*>(values), count, (int)units, format, nullbitmask, devmem ? 1 : 0, nullptr, &c));
   return adopt(c);
 }
+
+// ---- substrings / padding / wrapping (substr.cu, pad.cu, modify.cu:35-106,494-552) --------------------------------------
+static_assert(NVStrings::left == 0 && NVStrings::right == 1 && NVStrings::both == 2, "padside is cs_pad's side");
+template <class F>
+static NVStrings* made(F&& f) {
+  cs_column* c = nullptr;
+  NVStrings::check(f(&c));
+  return NVStrings::adopt(c);
+}
+NVStrings* NVStrings::repeat(unsigned int count) { return made([&](cs_column** c) { return cs_repeat(m_col, count, nullptr, c); }); }
+NVStrings* NVStrings::pad(unsigned int width, padside side, const char* fillchar) {  // pad.cu:87-96 (an unknown side pads left)
+  const int sd = side == right ? 1 : side == both ? 2 : 0;
+  return made([&](cs_column** c) { return cs_pad(m_col, width, sd, fillchar, nullptr, c); });
+}
+NVStrings* NVStrings::ljust(unsigned int width, const char* fillchar) { return pad(width, right, fillchar); }
+NVStrings* NVStrings::center(unsigned int width, const char* fillchar) { return pad(width, both, fillchar); }
+NVStrings* NVStrings::rjust(unsigned int width, const char* fillchar) { return pad(width, left, fillchar); }
+NVStrings* NVStrings::zfill(unsigned int width) { return made([&](cs_column** c) { return cs_zfill(m_col, width, nullptr, c); }); }
+NVStrings* NVStrings::wrap(unsigned int width) { return made([&](cs_column** c) { return cs_wrap(m_col, width, nullptr, c); }); }
+NVStrings* NVStrings::get(unsigned int pos) { return slice((int)pos, (int)(pos + 1), 1); }  // substr.cu:32-35
+NVStrings* NVStrings::slice(int start, int stop, int step) {
+  return made([&](cs_column** c) { return cs_slice(m_col, start, stop, step, nullptr, c); });
+}
+NVStrings* NVStrings::slice_from(const int* starts, const int* ends) {
+  return made([&](cs_column** c) { return cs_slice_from(m_col, starts, ends, 1, nullptr, c); });
+}
+NVStrings* NVStrings::slice_replace(const char* repl, int start, int stop) {
+  return made([&](cs_column** c) { return cs_slice_replace(m_col, repl, start, stop, nullptr, c); });
+}
+NVStrings* NVStrings::insert(const char* repl, int pos) {
+  return made([&](cs_column** c) { return cs_insert(m_col, repl, pos, nullptr, c); });
+}

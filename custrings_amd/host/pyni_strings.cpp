@@ -722,6 +722,83 @@ static PyObject* n_createFromTimestamp(PyObject*, PyObject* args) {  // (values,
   });
 }
 
+// ---- substrings / padding / wrapping (pystrings.cpp:1671-1899, 2053-2072; substr.cu, pad.cu, modify.cu) -------------
+static PyObject* n_get(PyObject*, PyObject* args) {  // (self, position)
+  NVStrings* s = SELF(args);
+  const unsigned pos = (unsigned)int_arg(args, 1, 0);
+  return make_instance([&] { return s->get(pos); });
+}
+static PyObject* n_repeat(PyObject*, PyObject* args) {  // (self, count)
+  NVStrings* s = SELF(args);
+  const unsigned count = (unsigned)int_arg(args, 1, 0);
+  return make_instance([&] { return s->repeat(count); });
+}
+// the fill character of the pad family: None is the default (" "), an empty string a ValueError
+static bool fill_arg(PyObject* args, int i, const char** fill) {
+  *fill = str_arg(args, i);
+  if (PyErr_Occurred()) return false;
+  if (*fill && !**fill) {
+    PyErr_SetString(PyExc_ValueError, "fillchar cannot be empty");
+    return false;
+  }
+  return true;
+}
+static PyObject* n_pad(PyObject*, PyObject* args) {  // (self, width, side, fillchar): side "left" / "right" / "both"
+  NVStrings* s = SELF(args);
+  const unsigned width = (unsigned)int_arg(args, 1, 0);
+  const char* side = str_arg(args, 2);
+  const char* fill = nullptr;
+  if (!fill_arg(args, 3, &fill)) return nullptr;
+  NVStrings::padside ps = NVStrings::left;
+  if (side && !strcmp(side, "right")) ps = NVStrings::right;
+  else if (side && !strcmp(side, "both")) ps = NVStrings::both;
+  return make_instance([&] { return s->pad(width, ps, fill); });
+}
+#define JUST_FN(NAME, CALL)                                          \
+  static PyObject* NAME(PyObject*, PyObject* args) { /* (self, width, fillchar) */ \
+    NVStrings* s = SELF(args);                                       \
+    const unsigned width = (unsigned)int_arg(args, 1, 0);            \
+    const char* fill = nullptr;                                      \
+    if (!fill_arg(args, 2, &fill)) return nullptr;                   \
+    return make_instance([&] { return s->CALL(width, fill); });      \
+  }
+JUST_FN(n_ljust, ljust)
+JUST_FN(n_center, center)
+JUST_FN(n_rjust, rjust)
+static PyObject* n_zfill(PyObject*, PyObject* args) {  // (self, width)
+  NVStrings* s = SELF(args);
+  const unsigned width = (unsigned)int_arg(args, 1, 0);
+  return make_instance([&] { return s->zfill(width); });
+}
+static PyObject* n_wrap(PyObject*, PyObject* args) {  // (self, width)
+  NVStrings* s = SELF(args);
+  const unsigned width = (unsigned)int_arg(args, 1, 0);
+  return make_instance([&] { return s->wrap(width); });
+}
+static PyObject* n_slice(PyObject*, PyObject* args) {  // (self, start, stop, step): stop None = -1, step None = 1
+  NVStrings* s = SELF(args);
+  const int start = (int)int_arg(args, 1, 0), stop = (int)int_arg(args, 2, -1), step = (int)int_arg(args, 3, 1);
+  return make_instance([&] { return s->slice(start, stop, step); });
+}
+static PyObject* n_slice_from(PyObject*, PyObject* args) {  // (self, starts, stops): device addresses, 0 / None = none
+  NVStrings* s = SELF(args);
+  const int* starts = ptr_arg<const int>(args, 1);
+  const int* stops = ptr_arg<const int>(args, 2);
+  return make_instance([&] { return s->slice_from(starts, stops); });
+}
+static PyObject* n_slice_replace(PyObject*, PyObject* args) {  // (self, start, stop, repl): None = 0 / -1 / null
+  NVStrings* s = SELF(args);
+  const int start = (int)int_arg(args, 1, 0), stop = (int)int_arg(args, 2, -1);
+  const char* repl = str_arg(args, 3);
+  return make_instance([&] { return s->slice_replace(repl, start, stop); });
+}
+static PyObject* n_insert(PyObject*, PyObject* args) {  // (self, start, repl)
+  NVStrings* s = SELF(args);
+  const int start = (int)int_arg(args, 1, 0);
+  const char* repl = str_arg(args, 2);
+  return make_instance([&] { return s->insert(repl, start); });
+}
+
 static PyMethodDef s_Methods[] = {
 #define M(n) {#n, n, METH_VARARGS, ""}
     M(n_dropWrapper), M(n_getIPCData), M(n_createFromIPC),
@@ -734,6 +811,8 @@ static PyMethodDef s_Methods[] = {
     M(n_hash), M(n_stoi), M(n_stol), M(n_stof), M(n_stod), M(n_htoi), M(n_ip2int), M(n_to_bools), M(n_createFromInt32s),
     M(n_createFromInt64s), M(n_createFromFloat32s), M(n_createFromFloat64s), M(n_createFromIPv4Integers), M(n_createFromBools),
     M(n_timestamp2int), M(n_createFromTimestamp),
+    M(n_get), M(n_slice), M(n_slice_from), M(n_slice_replace), M(n_insert), M(n_repeat), M(n_pad), M(n_ljust), M(n_center),
+    M(n_rjust), M(n_zfill), M(n_wrap),
 #undef M
     {NULL, NULL, 0, NULL}};
 static struct PyModuleDef s_Module = {PyModuleDef_HEAD_INIT, "pyniNVStrings", "CPython glue of nvstrings over the MI355X back-end", -1, s_Methods};

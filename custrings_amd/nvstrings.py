@@ -110,8 +110,7 @@ def bind_cpointer(cptr, own=True):
 
 _NOT_BUILT = (
     "compare "
-    "get repeat pad ljust center rjust zfill wrap slice slice_from "
-    "slice_replace insert fillna capitalize swapcase title index rindex "
+    "fillna capitalize swapcase title index rindex "
     "find_from rfind match_strings startswith endswith isalnum "
     "isalpha isdigit isspace isdecimal isnumeric islower isupper is_empty translate "
     "find_multiple url_encode url_decode get_ipc_data"
@@ -877,6 +876,95 @@ class nvstrings:
         """nvstrings.py:804-825 -- True where the row equals `true`; a null row is None in the host list
         (on the device: 1 when `true` is None, else 0)."""
         return self._convert(lambda p, d, f: lib.cs_to_bools(self.m_cptr, b(true), p, d, None, f), np.uint8, devptr, bool)
+
+    # ---- substrings / padding / wrapping (nvstrings.py:1129-1460; substr.cu, pad.cu, modify.cu) ----------------
+    def _made(self, fn):
+        out = C.c_void_p()
+        check(fn(C.byref(out)))
+        return nvstrings(out.value)
+
+    def get(self, i):
+        """nvstrings.py:1129-1151 -- the character at position i of every row (an empty row past the end)."""
+        return self.slice(i & 0xFFFFFFFF, (i + 1) & 0xFFFFFFFF)
+
+    def repeat(self, repeats):
+        """nvstrings.py:1153-1175 -- every row repeated; a count of 0 or 1 gives a copy."""
+        return self._made(lambda o: lib.cs_repeat(self.m_cptr, repeats & 0xFFFFFFFF, None, o))
+
+    def _pad(self, width, side, fillchar):
+        if fillchar is not None and len(fillchar) == 0:
+            raise ValueError("fillchar cannot be empty")
+        return self._made(lambda o: lib.cs_pad(self.m_cptr, width & 0xFFFFFFFF, side, b(fillchar), None, o))
+
+    def pad(self, width, side="left", fillchar=" "):
+        """nvstrings.py:1177-1205 -- fill rows shorter than width characters; side 'left', 'right' or 'both'."""
+        return self._pad(width, {"right": 1, "both": 2}.get(side, 0), fillchar)
+
+    def ljust(self, width, fillchar=" "):
+        """nvstrings.py:1207-1233 -- fill on the right to width characters."""
+        return self._pad(width, 1, fillchar)
+
+    def center(self, width, fillchar=" "):
+        """nvstrings.py:1235-1261 -- fill on both sides to width characters (the odd one on the right)."""
+        return self._pad(width, 2, fillchar)
+
+    def rjust(self, width, fillchar=" "):
+        """nvstrings.py:1263-1289 -- fill on the left to width characters."""
+        return self._pad(width, 0, fillchar)
+
+    def zfill(self, width):
+        """nvstrings.py:1291-1315 -- '0' fill on the left to width characters, after a leading sign."""
+        return self._made(lambda o: lib.cs_zfill(self.m_cptr, width & 0xFFFFFFFF, None, o))
+
+    def wrap(self, width):
+        """nvstrings.py:1317-1340 -- lines of about width characters: whitespace becomes ' ', some of it '\\n'."""
+        return self._made(lambda o: lib.cs_wrap(self.m_cptr, width & 0xFFFFFFFF, None, o))
+
+    def slice(self, start, stop=None, step=None):
+        """nvstrings.py:1342-1369 -- characters [start, stop) of every row (stop None or <= 0: to the end), every
+        step-th one.  start > stop > 0 is a ValueError."""
+        stop = -1 if stop is None else stop
+        step = 1 if step is None else step
+        return self._made(lambda o: lib.cs_slice(self.m_cptr, start, stop, step, None, o))
+
+    def slice_from(self, starts=0, stops=0):
+        """nvstrings.py:1371-1403 -- slice with a start and a stop per row: int32 device addresses (0 = none: 0 / -1),
+        device tensors, or host lists / numpy arrays."""
+        def arr(v):
+            if v is None or (isinstance(v, int) and v == 0):
+                return None, 0, None
+            if isinstance(v, int):
+                return v, 1, None
+            if hasattr(v, "data_ptr"):
+                if v.dtype.itemsize != 4 or v.dtype.is_floating_point:
+                    raise TypeError("nvstrings.slice_from(): starts / stops must be int32")
+                if v.numel() < self.size():
+                    raise ValueError("nvstrings.slice_from(): starts / stops need size() values")
+                return v.data_ptr(), 1 if v.is_cuda else 0, v
+            a = np.ascontiguousarray(v, dtype=np.int32)
+            if a.size < self.size():
+                raise ValueError("nvstrings.slice_from(): starts / stops need size() values")
+            return a.ctypes.data, 0, a
+        ps, ds, k1 = arr(starts)
+        pe, de, k2 = arr(stops)
+        if ps and pe and ds != de:  # (one on the host, the other on the device: both to the host)
+            raise ValueError("nvstrings.slice_from(): starts and stops must both be on the host or both on the device")
+        dev = ds or de
+        r = self._made(lambda o: lib.cs_slice_from(self.m_cptr, ps, pe, dev, None, o))
+        del k1, k2
+        return r
+
+    def slice_replace(self, start=None, stop=None, repl=None):
+        """nvstrings.py:1405-1432 -- characters [start, stop) replaced with repl (start None = 0, stop None = the end); a
+        start past the end appends."""
+        start = 0 if start is None else start
+        stop = -1 if stop is None else stop
+        return self._made(lambda o: lib.cs_slice_replace(self.m_cptr, b(repl), start, stop, None, o))
+
+    def insert(self, start=0, repl=None):
+        """nvstrings.py:1434-1460 -- repl inserted at character position start (-1 = the end)."""
+        start = 0 if start is None else start
+        return self._made(lambda o: lib.cs_insert(self.m_cptr, b(repl), start, None, o))
 
     def timestamp2int(self, format=None, units="s", devptr=0):
         """

@@ -579,6 +579,39 @@ int cs_timestamp2long(const cs_column* col, const char* format, int units, int64
 int cs_long2timestamp(const int64_t* values, int64_t count, int units, const char* format, const uint8_t* nulls, int on_device,
                       cs_stream stream, cs_column** out);
 
+/* ---- substrings, padding, wrapping (reference: cpp/src/strings/substr.cu, pad.cu, modify.cu:35-106,494-552;
+ * per-row logic in custrings_amd/csrc/pad_ops.h) -------------------------------------------------------------
+ * Null rows stay null (the output shares the input's validity).  Character positions are unsigned as in the
+ * reference: a negative start is past the end of every row.  An output row of 2^31 bytes or more is
+ * CS_ERR_RANGE. */
+/* NVStrings::slice / get (NVStrings.h:650-658; substr.cu:32-83): characters [start, stop) of every row,
+ * stop <= 0 meaning the row's end; step > 1 takes characters start, start + step, ... below stop.
+ * stop > 0 && start > stop: CS_ERR_INVALID_ARG (std::invalid_argument). */
+int cs_slice(const cs_column* col, int start, int stop, int step, cs_stream stream, cs_column** out);
+/* NVStrings::slice_from (NVStrings.h:671; substr.cu:85-130): slice with one int32 start / stop per row
+ * (device memory when on_device, else host); a NULL array means 0 / -1 for every row. */
+int cs_slice_from(const cs_column* col, const int32_t* starts, const int32_t* stops, int on_device, cs_stream stream,
+                  cs_column** out);
+/* NVStrings::slice_replace (NVStrings.h:704; modify.cu:35-106): characters [start, stop) replaced with
+ * `repl`, stop < 0 meaning the row's end; a start at or past the character count (a negative one included)
+ * appends.  repl NULL: CS_ERR_INVALID_ARG. */
+int cs_slice_replace(const cs_column* col, const char* repl, int start, int stop, cs_stream stream, cs_column** out);
+/* NVStrings::insert (NVStrings.h:754; modify.cu:494-552): `repl` inserted at character position `start`
+ * (-1 = the end; a row with fewer characters than `start` is left as it is).  repl NULL: CS_ERR_INVALID_ARG. */
+int cs_insert(const cs_column* col, const char* repl, int start, cs_stream stream, cs_column** out);
+/* NVStrings::repeat (NVStrings.h:561; pad.cu:28-85): every row repeated max(count, 1) times. */
+int cs_repeat(const cs_column* col, unsigned count, cs_stream stream, cs_column** out);
+/* NVStrings::pad / rjust / ljust / center (NVStrings.h:566-620; pad.cu:87-287): rows shorter than `width`
+ * characters filled to it with the first UTF-8 character of `fillchar` (NULL or empty = " ").
+ * side: 0 fill on the left (rjust), 1 on the right (ljust), 2 both (center: the odd one on the right). */
+int cs_pad(const cs_column* col, unsigned width, int side, const char* fillchar, cs_stream stream, cs_column** out);
+/* NVStrings::zfill (NVStrings.h:630; pad.cu:290-353): '0' fill to `width` characters after a leading '+' / '-'
+ * (every row, numeric or not). */
+int cs_zfill(const cs_column* col, unsigned width, cs_stream stream, cs_column** out);
+/* NVStrings::wrap (NVStrings.h:640; pad.cu:355-436): every character <= ' ' becomes ' ' and some become '\n',
+ * so that lines hold about `width` characters.  The output has the input's extents. */
+int cs_wrap(const cs_column* col, unsigned width, cs_stream stream, cs_column** out);
+
 #ifdef __cplusplus
 }
 #endif

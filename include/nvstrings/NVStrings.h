@@ -100,6 +100,27 @@ class NVStrings {
   NVStrings* lower();
   NVStrings* upper();
 
+  /* ---- substrings, padding, wrapping (NVStrings.h:561-754; substr.cu, pad.cu, modify.cu).  padside's enumerators and
+   * their order are the reference's: they are part of the mangled names.  slice with stop > 0 && start > stop, a null
+   * repl and an output row of 2^31 bytes or more throw std::invalid_argument. ---- */
+  NVStrings* repeat(unsigned int count);
+  enum padside {
+    left,   ///< Add padding to the left.
+    right,  ///< Add padding to the right.
+    both    ///< Add padding equally to the right and left.
+  };
+  NVStrings* pad(unsigned int width, padside side, const char* fillchar = nullptr);
+  NVStrings* ljust(unsigned int width, const char* fillchar = nullptr);
+  NVStrings* center(unsigned int width, const char* fillchar = nullptr);
+  NVStrings* rjust(unsigned int width, const char* fillchar = nullptr);
+  NVStrings* zfill(unsigned int width);
+  NVStrings* wrap(unsigned int width);
+  NVStrings* get(unsigned int pos);
+  NVStrings* slice(int start = 0, int stop = -1, int step = 1);
+  NVStrings* slice_from(const int* starts = nullptr, const int* ends = nullptr);  // device memory, size() values each
+  NVStrings* slice_replace(const char* repl, int start = 0, int stop = -1);
+  NVStrings* insert(const char* repl, int pos = 0);
+
   /* ---- search (NVStrings.h:861-981) ---- */
   unsigned int find(const char* str, int start, int end, int* results, bool devmem = true);
   int contains(const char* str, bool* results, bool devmem = true);

@@ -61,7 +61,7 @@ def report(config, op, rows, in_bytes, alg_bytes, dt):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scale", type=float, default=1.0, help="row-count multiplier (1.0 = BASELINE.json single-GPU sizes)")
-    ap.add_argument("--only", default="C2,C3,C4,C5", help="comma-separated configs to run (CONV: the conversion ops, TS: the timestamp ones)")
+    ap.add_argument("--only", default="C2,C3,C4,C5", help="comma-separated configs to run (CONV: the conversion ops, TS: the timestamp ones, PAD: substring / padding / wrapping)")
     a = ap.parse_args()
     only = set(a.only.split(","))
     ov = 8.125  # native offset + validity bytes per row
@@ -78,6 +78,8 @@ def main():
         run_conv(a, ov)
     if "TS" in only:
         run_ts(a)
+    if "PAD" in only:
+        run_pad(a)
 
 
 def run_c2(a, ov):
@@ -294,6 +296,30 @@ def run_ts(a):
                 report(cfg, "int2timestamp(%s)" % units, rows, 8 * rows, 8 * rows + (0.125 * rows if nl is not None else 0) + b + col_ov(res) * rows, dt)
                 del res
     L.cs_config_set(b"CS_CONVERT_ROWWISE", None)
+
+
+def run_pad(a):
+    # ---- the substring / padding / wrapping ops (substr.cu, pad.cu, modify.cu) on 100M rows of C3 and C2, on both routes (the
+    # default and CS_PAD_ROWWISE=1).  Algorithmic bytes: the chars + the offsets + the validity read, the chars + the offsets
+    # written (wrap shares the extents: its chars only).
+    rows = int(100_000_000 * a.scale)
+    ops = [("slice(2,12)", lambda c: c.slice(2, 12)), ("get(0)", lambda c: c.get(0)), ("ljust(100)", lambda c: c.ljust(100)),
+           ("zfill(20)", lambda c: c.zfill(20)), ("repeat(2)", lambda c: c.repeat(2)), ("wrap(20)", lambda c: c.wrap(20)),
+           ("slice_replace(2,5,'<>')", lambda c: c.slice_replace(2, 5, "<>"))]
+    for kind, name in ((3, "C3"), (2, "C2")):
+        col = synth(kind, rows)
+        b = nbytes(col)
+        for route in ("default", "rowwise"):
+            L.cs_config_set(b"CS_PAD_ROWWISE", b"1" if route == "rowwise" else None)
+            for op, fn in ops:
+                res = fn(col)
+                got_route = L.cs_debug_last_route().decode()
+                w = nbytes(res) + (0 if op.startswith("wrap") else 8 * rows)
+                dt = timed(lambda: fn(col), reps=3)
+                report("PAD %s 100M [%s]" % (name, got_route), op, rows, b, b + 8.125 * rows + w, dt)
+                del res
+        del col
+    L.cs_config_set(b"CS_PAD_ROWWISE", None)
 
 
 if __name__ == "__main__":
