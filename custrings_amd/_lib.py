@@ -151,6 +151,19 @@ _PROTOS = {
     "cs_pad": (i32, [vp, C.c_uint, i32, cp, vp, P(vp)]),
     "cs_zfill": (i32, [vp, C.c_uint, vp, P(vp)]),
     "cs_wrap": (i32, [vp, C.c_uint, vp, P(vp)]),
+    "cs_chartype": (i32, [vp, i32, vp, i32, vp, P(i64)]),
+    "cs_isalnum": (i32, [vp, vp, i32, vp, P(i64)]),
+    "cs_isalpha": (i32, [vp, vp, i32, vp, P(i64)]),
+    "cs_isdigit": (i32, [vp, vp, i32, vp, P(i64)]),
+    "cs_isspace": (i32, [vp, vp, i32, vp, P(i64)]),
+    "cs_isdecimal": (i32, [vp, vp, i32, vp, P(i64)]),
+    "cs_isnumeric": (i32, [vp, vp, i32, vp, P(i64)]),
+    "cs_islower": (i32, [vp, vp, i32, vp, P(i64)]),
+    "cs_isupper": (i32, [vp, vp, i32, vp, P(i64)]),
+    "cs_is_empty": (i32, [vp, vp, i32, vp, P(i64)]),
+    "cs_swapcase": (i32, [vp, vp, P(vp)]),
+    "cs_capitalize": (i32, [vp, vp, P(vp)]),
+    "cs_title": (i32, [vp, vp, P(vp)]),
     "cs_replace_re": (i32, [vp, vp, cp, i32, vp, P(vp)]),
     "cs_replace_with_backrefs": (i32, [vp, vp, cp, vp, P(vp)]),
     "cs_extract": (i32, [vp, vp, vp, P(P(vp)), P(i32)]),

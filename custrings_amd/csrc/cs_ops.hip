@@ -9,6 +9,7 @@
 
 #include "cs_internal.h"
 #include "device_utils.h"
+#include "chartype_ops.h"
 #include "row_ops.h"
 
 using namespace cs;
@@ -17,6 +18,7 @@ using namespace csdev;
 namespace cs {
 bool tokenize_fast(const cs_column* col, const unsigned char* delims, int ndel, hipStream_t s, cs_column** out);
 bool change_case_fast(const cs_column* col, unsigned bit, bool ascii_rule_ok, hipStream_t s, cs_column** out);
+bool case_modes_fast(const cs_column* col, int op, bool ascii_ok, hipStream_t s, cs_column** out);  // cs_casemodes.hip
 bool ngrams_fast(const cs_column* tokens, int n, const unsigned char* sep, int sepn, hipStream_t s, cs_column** out);
 }
 namespace cs {
@@ -141,6 +143,18 @@ struct CaseWrite {
   const uint16_t* cases;
   unsigned bit;
   __device__ void operator()(const uint8_t* p, int n, int64_t, uint8_t* o) const { row_case_write(p, n, flags, cases, bit, o); }
+};
+struct CaseModeSize {  // swapcase / capitalize / title (chartype_ops.h)
+  const uint8_t* flags;
+  const uint16_t* cases;
+  int op;
+  __device__ int operator()(const uint8_t* p, int n, int64_t) const { return cschr::case_size(p, n, flags, cases, op); }
+};
+struct CaseModeWrite {
+  const uint8_t* flags;
+  const uint16_t* cases;
+  int op;
+  __device__ void operator()(const uint8_t* p, int n, int64_t, uint8_t* o) const { cschr::case_write(p, n, flags, cases, op, o); }
 };
 struct StripSize {
   CharSet set;
@@ -426,6 +440,32 @@ static int change_case(const cs_column* col, unsigned bit, cs_stream stream, cs_
 }
 int cs_lower(const cs_column* col, cs_stream stream, cs_column** out) { return change_case(col, 32, stream, out, "k_lower_write"); }
 int cs_upper(const cs_column* col, cs_stream stream, cs_column** out) { return change_case(col, 64, stream, out, "k_upper_write"); }
+
+// NVStrings::swapcase / capitalize / title -- case.cu:169-235 / :238-311 / :314-397
+static int case_mode(const cs_column* col, int op, cs_stream stream, cs_column** out, const char* size_name, const char* write_name) {
+  return guard([&] {
+    if (!col || !out) fail(CS_ERR_INVALID_ARG, "null argument");
+    require_device();
+    // tile kernel (cs_casemodes.hip) when the tables' ASCII half is the plain one: A-Z <-> a-z, the only alphabetic bytes
+    static const bool ascii_ok = cschr::ascii_plain(h_unicode_flags(), h_charcases());
+    if (case_modes_fast(col, op, ascii_ok, S(stream), out)) {
+      note_route("tile");
+      return;
+    }
+    note_route("rows");
+    *out = two_pass(col, CaseModeSize{d_unicode_flags(), d_charcases(), op}, CaseModeWrite{d_unicode_flags(), d_charcases(), op},
+                    S(stream), size_name, write_name);
+  });
+}
+int cs_swapcase(const cs_column* col, cs_stream stream, cs_column** out) {
+  return case_mode(col, cschr::OP_SWAPCASE, stream, out, "k_swapcase_size", "k_swapcase_write");
+}
+int cs_capitalize(const cs_column* col, cs_stream stream, cs_column** out) {
+  return case_mode(col, cschr::OP_CAPITALIZE, stream, out, "k_capitalize_size", "k_capitalize_write");
+}
+int cs_title(const cs_column* col, cs_stream stream, cs_column** out) {
+  return case_mode(col, cschr::OP_TITLE, stream, out, "k_title_size", "k_title_write");
+}
 
 // NVStrings::strip family -- strip.cu:30-199
 int cs_strip(const cs_column* col, const char* to_strip, int side, cs_stream stream, cs_column** out) {

@@ -602,3 +602,22 @@ NVStrings* NVStrings::slice_replace(const char* repl, int start, int stop) {
 NVStrings* NVStrings::insert(const char* repl, int pos) {
   return made([&](cs_column** c) { return cs_insert(m_col, repl, pos, nullptr, c); });
 }
+
+// ---- character types (attrs.cu:115-438) and swapcase / capitalize / title (case.cu:169-397) -------------------------------
+static unsigned int chartype(cs_column* col, int pred, bool* results, bool devmem) {
+  int64_t n = 0;
+  NVStrings::check(cs_chartype(col, pred, reinterpret_cast<uint8_t*>(results), devmem ? 1 : 0, nullptr, &n));
+  return (unsigned int)n;
+}
+unsigned int NVStrings::isalnum(bool* results, bool devmem) { return chartype(m_col, CS_IS_ALNUM, results, devmem); }
+unsigned int NVStrings::isalpha(bool* results, bool devmem) { return chartype(m_col, CS_IS_ALPHA, results, devmem); }
+unsigned int NVStrings::isdigit(bool* results, bool devmem) { return chartype(m_col, CS_IS_DIGIT, results, devmem); }
+unsigned int NVStrings::isspace(bool* results, bool devmem) { return chartype(m_col, CS_IS_SPACE, results, devmem); }
+unsigned int NVStrings::isdecimal(bool* results, bool devmem) { return chartype(m_col, CS_IS_DECIMAL, results, devmem); }
+unsigned int NVStrings::isnumeric(bool* results, bool devmem) { return chartype(m_col, CS_IS_NUMERIC, results, devmem); }
+unsigned int NVStrings::islower(bool* results, bool devmem) { return chartype(m_col, CS_IS_LOWER, results, devmem); }
+unsigned int NVStrings::isupper(bool* results, bool devmem) { return chartype(m_col, CS_IS_UPPER, results, devmem); }
+unsigned int NVStrings::is_empty(bool* results, bool devmem) { return chartype(m_col, CS_IS_EMPTY, results, devmem); }
+NVStrings* NVStrings::swapcase() { return made([&](cs_column** c) { return cs_swapcase(m_col, nullptr, c); }); }
+NVStrings* NVStrings::capitalize() { return made([&](cs_column** c) { return cs_capitalize(m_col, nullptr, c); }); }
+NVStrings* NVStrings::title() { return made([&](cs_column** c) { return cs_title(m_col, nullptr, c); }); }

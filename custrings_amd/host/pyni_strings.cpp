@@ -799,6 +799,32 @@ static PyObject* n_insert(PyObject*, PyObject* args) {  // (self, start, repl)
   return make_instance([&] { return s->insert(repl, start); });
 }
 
+// ---- character types and swapcase / capitalize / title (pystrings.cpp:3419-3456 and its eight siblings) -------------------
+// (self, devptr): with a device address the bools are written there and the address comes back; without, a list in
+// which null rows are None -- for is_empty as well
+#define CHARTYPE_FN(NAME, CALL)                                                                                      \
+  static PyObject* NAME(PyObject*, PyObject* args) {                                                                 \
+    NVStrings* s = SELF(args);                                                                                       \
+    return bool_results(s, ptr_arg<bool>(args, 1), [&](bool* out, bool dev) { return (int)s->CALL(out, dev); });     \
+  }
+CHARTYPE_FN(n_isalnum, isalnum)
+CHARTYPE_FN(n_isalpha, isalpha)
+CHARTYPE_FN(n_isdigit, isdigit)
+CHARTYPE_FN(n_isspace, isspace)
+CHARTYPE_FN(n_isdecimal, isdecimal)
+CHARTYPE_FN(n_isnumeric, isnumeric)
+CHARTYPE_FN(n_islower, islower)
+CHARTYPE_FN(n_isupper, isupper)
+CHARTYPE_FN(n_is_empty, is_empty)
+#define CASE_FN(NAME, CALL)                            \
+  static PyObject* NAME(PyObject*, PyObject* args) {   \
+    NVStrings* s = SELF(args);                         \
+    return make_instance([&] { return s->CALL(); });   \
+  }
+CASE_FN(n_swapcase, swapcase)
+CASE_FN(n_capitalize, capitalize)
+CASE_FN(n_title, title)
+
 static PyMethodDef s_Methods[] = {
 #define M(n) {#n, n, METH_VARARGS, ""}
     M(n_dropWrapper), M(n_getIPCData), M(n_createFromIPC),
@@ -813,6 +839,8 @@ static PyMethodDef s_Methods[] = {
     M(n_timestamp2int), M(n_createFromTimestamp),
     M(n_get), M(n_slice), M(n_slice_from), M(n_slice_replace), M(n_insert), M(n_repeat), M(n_pad), M(n_ljust), M(n_center),
     M(n_rjust), M(n_zfill), M(n_wrap),
+    M(n_isalnum), M(n_isalpha), M(n_isdigit), M(n_isspace), M(n_isdecimal), M(n_isnumeric), M(n_islower), M(n_isupper), M(n_is_empty),
+    M(n_swapcase), M(n_capitalize), M(n_title),
 #undef M
     {NULL, NULL, 0, NULL}};
 static struct PyModuleDef s_Module = {PyModuleDef_HEAD_INIT, "pyniNVStrings", "CPython glue of nvstrings over the MI355X back-end", -1, s_Methods};

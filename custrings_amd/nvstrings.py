@@ -108,13 +108,7 @@ def bind_cpointer(cptr, own=True):
     return nvstrings(cptr, own)
 
 
-_NOT_BUILT = (
-    "compare "
-    "fillna capitalize swapcase title index rindex "
-    "find_from rfind match_strings startswith endswith isalnum "
-    "isalpha isdigit isspace isdecimal isnumeric islower isupper is_empty translate "
-    "find_multiple url_encode url_decode get_ipc_data"
-).split()
+_NOT_BUILT = "fillna index rindex translate url_encode url_decode".split()
 
 
 # ---- numbers / booleans -> strings (nvstrings.py:153-340; convert.cu) ---------------------------------------------------
@@ -965,6 +959,59 @@ class nvstrings:
         """nvstrings.py:1434-1460 -- repl inserted at character position start (-1 = the end)."""
         start = 0 if start is None else start
         return self._made(lambda o: lib.cs_insert(self.m_cptr, b(repl), start, None, o))
+
+    # ---- character types (attrs.cu:115-438) and swapcase / capitalize / title (case.cu:169-397) ----------------------
+    def _chartype(self, pred, devptr):
+        return self._bools(lambda out, dev, f: lib.cs_chartype(self.m_cptr, pred, out, dev, None, f), devptr)
+
+    def isalnum(self, devptr=0):
+        """True where the row is not empty and every character is a letter or a digit of any kind (decimal, digit,
+        numeric); a null row is None in the host list, False on the device."""
+        return self._chartype(0, devptr)
+
+    def isalpha(self, devptr=0):
+        """True where the row is not empty and every character is alphabetic."""
+        return self._chartype(1, devptr)
+
+    def isdigit(self, devptr=0):
+        """True where the row is not empty and every character is a digit (superscripts included)."""
+        return self._chartype(2, devptr)
+
+    def isspace(self, devptr=0):
+        """True where the row is not empty and every character is white space."""
+        return self._chartype(3, devptr)
+
+    def isdecimal(self, devptr=0):
+        """True where the row is not empty and every character is a decimal digit."""
+        return self._chartype(4, devptr)
+
+    def isnumeric(self, devptr=0):
+        """True where the row is not empty and every character is numeric (fractions included)."""
+        return self._chartype(5, devptr)
+
+    def islower(self, devptr=0):
+        """True where the row is not empty and none of its alphabetic characters is upper case ("123" is True)."""
+        return self._chartype(6, devptr)
+
+    def isupper(self, devptr=0):
+        """True where the row is not empty and none of its alphabetic characters is lower case ("123" is True)."""
+        return self._chartype(7, devptr)
+
+    def is_empty(self, devptr=0):
+        """True where the row has no bytes; a null row is None in the host list, True on the device."""
+        return self._chartype(8, devptr)
+
+    def swapcase(self):
+        """Every cased character becomes its opposite-case one."""
+        return self._made(lambda o: lib.cs_swapcase(self.m_cptr, None, o))
+
+    def capitalize(self):
+        """The first character to upper, the others to lower case (characters up to U+0FFF only, as the reference)."""
+        return self._made(lambda o: lib.cs_capitalize(self.m_cptr, None, o))
+
+    def title(self):
+        """A letter after a non-letter (or at the start) to upper, a letter after a letter to lower case."""
+        return self._made(lambda o: lib.cs_title(self.m_cptr, None, o))
 
     def timestamp2int(self, format=None, units="s", devptr=0):
         """

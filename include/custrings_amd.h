@@ -612,6 +612,46 @@ int cs_zfill(const cs_column* col, unsigned width, cs_stream stream, cs_column**
  * so that lines hold about `width` characters.  The output has the input's extents. */
 int cs_wrap(const cs_column* col, unsigned width, cs_stream stream, cs_column** out);
 
+/* ---- character types and the other case ops (reference: cpp/src/strings/attrs.cu:115-438, case.cu:169-397; per-row
+ * logic in custrings_amd/csrc/chartype_ops.h) -----------------------------------------------------------------
+ * Predicates: one byte per row (1 / 0) into `results` (rows entries; device memory when on_device); `count`
+ * receives the number of true rows.  A column of no rows or a NULL `results`: count 0, nothing written.
+ * Flag bits of the Unicode table: decimal 1, numeric 2, digit 4, alpha 8, space 16, upper 32, lower 64; a
+ * character above U+FFFF has none.
+ *   isalnum (bits 15), isalpha (8), isdigit (4), isspace (16), isdecimal (1), isnumeric (2): the row is not
+ *     empty and every character has one of the bits; a null row is false
+ *   islower / isupper: the row is not empty and every character is not alphabetic, or lower / upper
+ *   is_empty: the row is null or has no bytes */
+typedef enum cs_chartype_pred {
+  CS_IS_ALNUM = 0,
+  CS_IS_ALPHA = 1,
+  CS_IS_DIGIT = 2,
+  CS_IS_SPACE = 3,
+  CS_IS_DECIMAL = 4,
+  CS_IS_NUMERIC = 5,
+  CS_IS_LOWER = 6,
+  CS_IS_UPPER = 7,
+  CS_IS_EMPTY = 8
+} cs_chartype_pred;
+int cs_chartype(const cs_column* col, int pred, uint8_t* results, int on_device, cs_stream stream, int64_t* count);
+int cs_isalnum(const cs_column* col, uint8_t* results, int on_device, cs_stream stream, int64_t* count);   /* NVStrings::isalnum, attrs.cu:115 */
+int cs_isalpha(const cs_column* col, uint8_t* results, int on_device, cs_stream stream, int64_t* count);   /* NVStrings::isalpha, attrs.cu:152 */
+int cs_isdigit(const cs_column* col, uint8_t* results, int on_device, cs_stream stream, int64_t* count);   /* NVStrings::isdigit, attrs.cu:190 */
+int cs_isspace(const cs_column* col, uint8_t* results, int on_device, cs_stream stream, int64_t* count);   /* NVStrings::isspace, attrs.cu:227 */
+int cs_isdecimal(const cs_column* col, uint8_t* results, int on_device, cs_stream stream, int64_t* count); /* NVStrings::isdecimal, attrs.cu:264 */
+int cs_isnumeric(const cs_column* col, uint8_t* results, int on_device, cs_stream stream, int64_t* count); /* NVStrings::isnumeric, attrs.cu:301 */
+int cs_islower(const cs_column* col, uint8_t* results, int on_device, cs_stream stream, int64_t* count);   /* NVStrings::islower, attrs.cu:338 */
+int cs_isupper(const cs_column* col, uint8_t* results, int on_device, cs_stream stream, int64_t* count);   /* NVStrings::isupper, attrs.cu:375 */
+int cs_is_empty(const cs_column* col, uint8_t* results, int on_device, cs_stream stream, int64_t* count);  /* NVStrings::is_empty, attrs.cu:412 */
+/* NVStrings::swapcase (case.cu:169): every cased character becomes its opposite-case one.
+ * NVStrings::capitalize (case.cu:238): the first character to upper, the others to lower case -- only
+ * characters up to U+0FFF are mapped (the reference's bound); later cased ones pass through.
+ * NVStrings::title (case.cu:314): a letter that follows a non-letter (or starts the row) to upper, a letter
+ * that follows a letter to lower case.  Null rows stay null. */
+int cs_swapcase(const cs_column* col, cs_stream stream, cs_column** out);
+int cs_capitalize(const cs_column* col, cs_stream stream, cs_column** out);
+int cs_title(const cs_column* col, cs_stream stream, cs_column** out);
+
 #ifdef __cplusplus
 }
 #endif

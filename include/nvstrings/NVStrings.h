@@ -99,6 +99,24 @@ class NVStrings {
   NVStrings* rstrip(const char* to_strip);
   NVStrings* lower();
   NVStrings* upper();
+  /* swapcase / capitalize / title (NVStrings.h:825-835; case.cu:169-397).  capitalize maps only characters up to U+0FFF
+   * (the reference's bound); title treats every non-letter as a word break. */
+  NVStrings* capitalize();
+  NVStrings* swapcase();
+  NVStrings* title();
+
+  /* ---- character types (NVStrings.h:362-427; attrs.cu:115-438): one bool per row, the count of true rows returned
+   * (0 for an empty instance or a null `results`).  A null row is false (true for is_empty); an empty row is false
+   * (true for is_empty).  islower / isupper look at alphabetic characters only. ---- */
+  unsigned int isalnum(bool* results, bool devmem = true);
+  unsigned int isalpha(bool* results, bool devmem = true);
+  unsigned int isdigit(bool* results, bool devmem = true);
+  unsigned int isspace(bool* results, bool devmem = true);
+  unsigned int isdecimal(bool* results, bool devmem = true);
+  unsigned int isnumeric(bool* results, bool devmem = true);
+  unsigned int islower(bool* results, bool devmem = true);
+  unsigned int isupper(bool* results, bool devmem = true);
+  unsigned int is_empty(bool* results, bool devmem = true);
 
   /* ---- substrings, padding, wrapping (NVStrings.h:561-754; substr.cu, pad.cu, modify.cu).  padside's enumerators and
    * their order are the reference's: they are part of the mangled names.  slice with stop > 0 && start > stop, a null

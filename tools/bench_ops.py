@@ -61,7 +61,7 @@ def report(config, op, rows, in_bytes, alg_bytes, dt):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scale", type=float, default=1.0, help="row-count multiplier (1.0 = BASELINE.json single-GPU sizes)")
-    ap.add_argument("--only", default="C2,C3,C4,C5", help="comma-separated configs to run (CONV: the conversion ops, TS: the timestamp ones, PAD: substring / padding / wrapping)")
+    ap.add_argument("--only", default="C2,C3,C4,C5", help="comma-separated configs to run (CONV: the conversion ops, TS: the timestamp ones, PAD: substring / padding / wrapping, CHR: character types and swapcase / capitalize / title)")
     a = ap.parse_args()
     only = set(a.only.split(","))
     ov = 8.125  # native offset + validity bytes per row
@@ -80,6 +80,8 @@ def main():
         run_ts(a)
     if "PAD" in only:
         run_pad(a)
+    if "CHR" in only:
+        run_chr(a)
 
 
 def run_c2(a, ov):
@@ -320,6 +322,48 @@ def run_pad(a):
                 del res
         del col
     L.cs_config_set(b"CS_PAD_ROWWISE", None)
+
+
+def run_chr(a):
+    # ---- the character-type predicates (attrs.cu) and swapcase / capitalize / title (case.cu) on 100M rows, on both routes
+    # (the default, then CS_CONVERT_ROWWISE=1 for the predicates and CS_CASE_ROWWISE=1 for the case ops).  Algorithmic bytes:
+    # predicates L + 8.125 read and 1 written a row (is_empty: 8.125 read, 1 written); case ops L + 8.125 read and L written
+    # (the extents are shared).  `hash` (same staging, every byte walked) and `lower` (same bytes moved) run beside them.
+    rows = int(100_000_000 * a.scale)
+    gen = torch.Generator(device="cuda").manual_seed(SEED)
+    i32 = torch.randint(0, (1 << 31) - 1, (rows,), dtype=torch.int32, device="cuda", generator=gen)
+    out8 = torch.empty(rows, dtype=torch.uint8, device="cuda")
+    out32 = torch.empty(rows, dtype=torch.int32, device="cuda")
+    preds = ["isalnum", "isalpha", "isdigit", "isspace", "isdecimal", "isnumeric", "islower", "isupper", "is_empty"]
+    cols = (("C3", synth(3, rows), preds), ("C4", synth(4, rows, 1000), ["isalpha", "isalnum", "islower"]),
+            ("itos output", nvstrings.itos(i32, bdevmem=True), ["isdigit", "isdecimal"]))
+    del i32
+    for route in ("default", "rowwise"):
+        L.cs_config_set(b"CS_CONVERT_ROWWISE", b"1" if route == "rowwise" else None)
+        for cfg, col, ops in cols:
+            b = nbytes(col)
+            for op in ops + ["hash"]:
+                fn = getattr(col, op)
+                o, w = (out32, 4) if op == "hash" else (out8, 1)
+                dt = timed(lambda: fn(devptr=o.data_ptr()))
+                n = o.count_nonzero().item() if op != "hash" else -1
+                alg = (0 if op == "is_empty" else b) + 8.125 * rows + w * rows
+                report("CHR %s 100M [%s] true=%d" % (cfg, L.cs_debug_last_route().decode(), n), op, rows, b, alg, dt)
+    L.cs_config_set(b"CS_CONVERT_ROWWISE", None)
+    del cols
+    for kind, name in ((3, "C3"), (2, "C2")):
+        col = synth(kind, rows)
+        b = nbytes(col)
+        for route in ("default", "rowwise"):
+            L.cs_config_set(b"CS_CASE_ROWWISE", b"1" if route == "rowwise" else None)
+            for op in ("lower", "swapcase", "capitalize", "title"):
+                fn = getattr(col, op)
+                dt = timed(fn, reps=3)
+                got_route = L.cs_debug_last_route().decode() if op != "lower" else ("rows" if route == "rowwise" else "tile")
+                wr = (8 * rows) if route == "rowwise" else 0  # (the two-pass kernels write offsets of their own)
+                report("CHR %s 100M [%s]" % (name, got_route), op, rows, b, 2 * b + 8.125 * rows + wr, dt)
+        del col
+    L.cs_config_set(b"CS_CASE_ROWWISE", None)
 
 
 if __name__ == "__main__":

@@ -18,7 +18,7 @@ from custrings_amd import nvtext, nvcategory, _lib  # noqa: E402
 LIB = _lib.lib
 
 TOGGLES = ("CS_REGEX_TWO_PASS", "CS_REGEX_ROWWISE", "CS_SPLIT_GENERIC", "CS_TOKENIZE_ROWWISE", "CS_STRIP_ROWWISE",
-           "CS_FIND_ROWWISE", "CS_REPLACE_ROWWISE", "CS_CASE_ROWWISE", "CS_NGRAM_ROWWISE",
+           "CS_FIND_ROWWISE", "CS_REPLACE_ROWWISE", "CS_CASE_ROWWISE", "CS_NGRAM_ROWWISE", "CS_CONVERT_ROWWISE",
            "CS_NO_CLASS_RUNS")  # (the byte-parallel class route is a fast path too: off in the witness -- it sat on both sides until round 5's last soak)
 PATS = [(r"\d+\.\d+\.\d+\.\d+", "<IP>"), (r"\d", "#"), (r"[a-c]+", "xyz__"), (r"\s+", " "), (r"\w+", "<w>"), (r"b|ab", ""),
         (r"\bx", "YY"), (r"[0-9]+", "<number-here>"), (r"a", "aa"), (r"(a|b)c", "-"),
@@ -130,6 +130,13 @@ def snapshot(g, rows, rng_seed, pats=None, regex_only=False):
     out["strip set"] = gpuutil.to_col(g.strip("ab é"))
     out["lower"] = gpuutil.to_col(g.lower())
     out["upper"] = gpuutil.to_col(g.upper())
+    for op in ("swapcase", "capitalize", "title"):  # (tile kernel against the two-pass kernels: CS_CASE_ROWWISE)
+        out[op] = gpuutil.to_col(getattr(g, op)())
+    for k, op in enumerate(("isalnum", "isalpha", "isdigit", "isspace", "isdecimal", "isnumeric", "islower", "isupper", "is_empty")):
+        f = np.zeros(max(rows, 1), dtype=np.uint8)  # (tile parser against the row-wise one: CS_CONVERT_ROWWISE)
+        found = C.c_int64()
+        L.check(L.lib.cs_chartype(g.m_cptr, k, f.ctypes.data, 0, None, C.byref(found)))
+        out[op] = (f[:rows], found.value)
     for sub in ("3.4", "é", "ab"):
         f = np.zeros(max(rows, 1), dtype=np.int32)
         found = C.c_int64()
