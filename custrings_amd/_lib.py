@@ -99,6 +99,12 @@ _PROTOS = {
     "cs_token_count": (i32, [vp, cp, vp, i32, vp]),
     "cs_unique_tokens": (i32, [vp, cp, vp, P(vp)]),
     "cs_tokens_counts": (i32, [vp, vp, cp, vp, i32, vp]),
+    "cs_contains_strings": (i32, [vp, vp, vp, i32, vp]),
+    "cs_strings_counts": (i32, [vp, vp, vp, i32, vp]),
+    "cs_edit_distance": (i32, [vp, cp, i32, vp, i32, vp]),
+    "cs_edit_distance_column": (i32, [vp, vp, i32, vp, i32, vp]),
+    "cs_porter_stemmer_measure": (i32, [vp, cp, cp, vp, i32, vp]),
+    "cs_scatter_count": (i32, [vp, vp, i32, vp, P(vp)]),
     "cs_replace_tokens": (i32, [vp, vp, vp, cp, vp, P(vp)]),
     "cs_normalize_spaces": (i32, [vp, vp, P(vp)]),
     "cs_lower": (i32, [vp, vp, P(vp)]),

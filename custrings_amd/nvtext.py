@@ -1,5 +1,4 @@
-"""`nvtext` -- host-side mirror of /root/reference/python/nvtext.py for the hot path
-(tokenize + n-grams), over the C ABI."""
+"""`nvtext` -- host-side mirror of /root/reference/python/nvtext.py over the C ABI."""
 import ctypes as C
 
 import numpy as np
@@ -7,7 +6,8 @@ import numpy as np
 from . import nvstrings as _nvs
 from ._lib import lib, check, b
 
-__all__ = ["tokenize", "ngrams", "unique_tokens", "token_count", "tokens_counts", "replace_tokens", "normalize_spaces"]
+__all__ = ["tokenize", "ngrams", "unique_tokens", "token_count", "tokens_counts", "replace_tokens", "normalize_spaces",
+           "contains_strings", "strings_counts", "edit_distance", "scatter_count", "porter_stemmer_measure"]
 
 
 def tokenize(strs, delimiter=None):
@@ -82,7 +82,80 @@ def normalize_spaces(strs):
     return _nvs.nvstrings(out.value) if out.value else None
 
 
-def __getattr__(name):
-    if name in ("contains_strings", "strings_counts", "edit_distance", "scatter_count"):
-        raise NotImplementedError("nvtext.%s is outside the accelerated hot path (SURVEY.md section 8)" % name)
-    raise AttributeError(name)
+def _targets(tgts, what):
+    """pytext.cpp:179-207 -- a list or an nvstrings, not empty"""
+    if tgts is None:
+        raise ValueError("%s argument must be specified" % what)
+    if isinstance(tgts, list):
+        tgts = _nvs.to_device(tgts)
+    if not isinstance(tgts, _nvs.nvstrings):
+        raise ValueError("invalid %s parameter" % what)
+    return tgts
+
+
+def _matrix(fn, dtype, strs, tgts, devptr, item):
+    tgts = _targets(tgts, "tgts")
+    rows, tc = strs.size(), tgts.size()
+    if tc == 0:
+        raise ValueError("tgts argument is empty")
+    if devptr:
+        check(fn(strs.m_cptr, tgts.m_cptr, devptr, 1, None))
+        return devptr
+    res = np.zeros(max(rows * tc, 1), dtype=dtype)
+    check(fn(strs.m_cptr, tgts.m_cptr, res.ctypes.data, 0, None))
+    return [[item(v) for v in res[r * tc : (r + 1) * tc]] for r in range(rows)]
+
+
+def contains_strings(strs, tgts, devptr=0):
+    """nvtext.py:104-130 -- per row, whether each of tgts occurs in it (a list of bools per row)."""
+    return _matrix(lib.cs_contains_strings, np.uint8, strs, tgts, devptr, bool)
+
+
+def strings_counts(strs, tgts, devptr=0):
+    """nvtext.py:133-159 -- per row, how often each of tgts occurs in it (a list of ints per row)."""
+    return _matrix(lib.cs_strings_counts, np.uint32, strs, tgts, devptr, int)
+
+
+def edit_distance(strs, tgt, algo=0, devptr=0):
+    """nvtext.py:261-287 -- the Levenshtein distance of every row to `tgt` (a str), or row by row to a list / nvstrings
+    of the same size; algo 0 is the only one."""
+    if tgt is None:
+        raise ValueError("tgt argument must be specified")
+    if algo not in (0, None):
+        raise ValueError("unrecognized edit-distance algorithm")
+    rows = strs.size()
+    res = None if devptr else np.zeros(max(rows, 1), dtype=np.uint32)
+    out = devptr if devptr else res.ctypes.data
+    if isinstance(tgt, str):
+        check(lib.cs_edit_distance(strs.m_cptr, b(tgt), 0, out, 1 if devptr else 0, None))
+    else:
+        tgts = _targets(tgt, "tgt")
+        if tgts.size() != rows:
+            raise ValueError("strs and tgt must have the same number of strings")
+        check(lib.cs_edit_distance_column(strs.m_cptr, tgts.m_cptr, 0, out, 1 if devptr else 0, None))
+    return None if devptr else [int(v) for v in res[:rows]]
+
+
+def porter_stemmer_measure(strs, vowels="aeiou", y_char="y", devptr=0):
+    """NVText::porter_stemmer_measure (NVText.h:164; the reference's Python module has no such function) -- the
+    vowel-run -> consonant transitions of every row; 0 for a null row."""
+    rows = strs.size()
+    if devptr:
+        check(lib.cs_porter_stemmer_measure(strs.m_cptr, b(vowels), b(y_char), devptr, 1, None))
+        return devptr
+    res = np.zeros(max(rows, 1), dtype=np.uint32)
+    check(lib.cs_porter_stemmer_measure(strs.m_cptr, b(vowels), b(y_char), res.ctypes.data, 0, None))
+    return [int(v) for v in res[:rows]]
+
+
+def scatter_count(strs, counts):
+    """nvtext.py:322-346 -- row i repeated counts[i] times (a list, None = 0, or a device pointer to uint32 values)."""
+    out = C.c_void_p()
+    if isinstance(counts, int):
+        check(lib.cs_scatter_count(strs.m_cptr, counts, 1, None, C.byref(out)))
+    else:
+        vals = np.array([0 if c is None else int(c) for c in counts], dtype=np.uint32)
+        if len(vals) != strs.size():
+            raise ValueError("counts must have one entry per string")
+        check(lib.cs_scatter_count(strs.m_cptr, vals.ctypes.data if len(vals) else None, 0, None, C.byref(out)))
+    return _nvs.nvstrings(out.value) if out.value else None

@@ -652,6 +652,32 @@ int cs_swapcase(const cs_column* col, cs_stream stream, cs_column** out);
 int cs_capitalize(const cs_column* col, cs_stream stream, cs_column** out);
 int cs_title(const cs_column* col, cs_stream stream, cs_column** out);
 
+/* ---- the rest of NVText: string matches, edit distance, stemmer measure, scatter (per-row logic in
+ * custrings_amd/csrc/text_ops.h; kernels cs_textops.hip) ---------------------------------------------
+ * Matrix results are row-major: results[r * targets_rows + j] (device memory when on_device).  A column of no rows, no
+ * targets or a NULL `results` writes nothing. */
+/* NVText::contains_strings (NVText.cu:32): 1 when target j occurs in row r -- bytes compared at every byte offset.  A null
+ * row, a null target and an empty target give 0. */
+int cs_contains_strings(const cs_column* col, const cs_column* targets, uint8_t* results, int on_device, cs_stream stream);
+/* NVText::strings_counts (NVText.cu:77): occurrences of target j in row r, each search starting chars(target) characters
+ * behind the character position of the last match. */
+int cs_strings_counts(const cs_column* col, const cs_column* targets, uint32_t* results, int on_device, cs_stream stream);
+typedef enum cs_distance_type { CS_LEVENSHTEIN = 0 } cs_distance_type; /* NVText::distance_type, NVText.h:121 */
+/* NVText::edit_distance (edit_distance.cu:119): the Levenshtein distance, in characters, of every row to `target`.  A null
+ * or empty row gives chars(target).  algo != CS_LEVENSHTEIN, target NULL or results NULL: CS_ERR_INVALID_ARG.  A row or a
+ * target of more than 32767 characters: CS_ERR_RANGE (the reference's 16-bit table wraps there). */
+int cs_edit_distance(const cs_column* col, const char* target, int algo, uint32_t* results, int on_device, cs_stream stream);
+/* NVText::edit_distance (edit_distance.cu:172): row r of `col` against row r of `targets`; a null or empty side gives the
+ * other side's characters (0 when both are).  Columns of different sizes: CS_ERR_INVALID_ARG. */
+int cs_edit_distance_column(const cs_column* col, const cs_column* targets, int algo, uint32_t* results, int on_device, cs_stream stream);
+/* NVText::porter_stemmer_measure (stemmer.cu:69): vowel-run -> consonant transitions per row; vowels NULL = "aeiou",
+ * y_char NULL = "y" (its first character).  A null row gives 0 (the reference leaves its entry unwritten). */
+int cs_porter_stemmer_measure(const cs_column* col, const char* vowels, const char* y_char, uint32_t* results, int on_device, cs_stream stream);
+/* NVText::scatter_count (NVText.cu:126): row i repeated counts[i] times, in order (counts: rows entries, device memory when
+ * on_device); null rows stay null.  *out = NULL for a column of no rows or NULL counts; a total of 0 gives an empty column;
+ * a total of 2^31 or more: CS_ERR_RANGE. */
+int cs_scatter_count(const cs_column* col, const uint32_t* counts, int on_device, cs_stream stream, cs_column** out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,7 +61,7 @@ def report(config, op, rows, in_bytes, alg_bytes, dt):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scale", type=float, default=1.0, help="row-count multiplier (1.0 = BASELINE.json single-GPU sizes)")
-    ap.add_argument("--only", default="C2,C3,C4,C5", help="comma-separated configs to run (CONV: the conversion ops, TS: the timestamp ones, PAD: substring / padding / wrapping, CHR: character types and swapcase / capitalize / title)")
+    ap.add_argument("--only", default="C2,C3,C4,C5", help="comma-separated configs to run (CONV: the conversion ops, TS: the timestamp ones, PAD: substring / padding / wrapping, CHR: character types and swapcase / capitalize / title, TXT: the NVText matches, edit distance, stemmer measure and scatter_count)")
     a = ap.parse_args()
     only = set(a.only.split(","))
     ov = 8.125  # native offset + validity bytes per row
@@ -82,6 +82,8 @@ def main():
         run_pad(a)
     if "CHR" in only:
         run_chr(a)
+    if "TXT" in only:
+        run_txt(a)
 
 
 def run_c2(a, ov):
@@ -364,6 +366,53 @@ def run_chr(a):
                 report("CHR %s 100M [%s]" % (name, got_route), op, rows, b, 2 * b + 8.125 * rows + wr, dt)
         del col
     L.cs_config_set(b"CS_CASE_ROWWISE", None)
+
+
+def run_txt(a):
+    # ---- contains_strings / strings_counts / edit_distance / porter_stemmer_measure / scatter_count (NVText.cu, edit_distance.cu,
+    # stemmer.cu) on the C3 and C2 columns at 10M rows, on both routes (the default, then CS_TEXT_ROWWISE=1); `hash` beside them as
+    # the bandwidth-bound neighbour.  Algorithmic bytes: L + 8.125 read a row and the results written (M values a row for the
+    # matches; scatter_count: the gather's bytes).  The scalar edit_distance at targets of 8, 64 and 65 characters: 65 takes the
+    # dynamic program on either route.
+    rows = int(10_000_000 * a.scale)
+    words = ["the", "er", "a", "GET", "in", "10", "e ", "on", ".1", "st", "al", "to", "ng", "0 ", "ha", "it"]
+    t2, t32 = nvstrings.to_device(words[:2]), nvstrings.to_device(words + [w + "x" for w in words])
+    text = "GET /index.html HTTP/1.1 200 the quick brown fox jumps over the lazy dog again"
+    out8 = torch.empty(rows * 32, dtype=torch.uint8, device="cuda")
+    out32 = torch.empty(rows * 32, dtype=torch.int32, device="cuda")
+    cnt = (torch.arange(rows, dtype=torch.int32, device="cuda") % 3).contiguous()
+    for kind, name in ((3, "C3"), (2, "C2")):
+        col = synth(kind, rows)
+        b = nbytes(col)
+        for route in ("default", "rowwise"):
+            L.cs_config_set(b"CS_TEXT_ROWWISE", b"1" if route == "rowwise" else None)
+
+            def line(op, call, written, reps=3):
+                dt = timed(call, reps=reps)
+                report("TXT %s 10M [%s]" % (name, L.cs_debug_last_route().decode()), op, rows, b, b + 8.125 * rows + written, dt)
+
+            if route == "default":
+                dt = timed(lambda: col.hash(devptr=out32.data_ptr()))
+                report("TXT %s 10M [%s]" % (name, L.cs_debug_last_route().decode()), "hash", rows, b, b + 12.125 * rows, dt)
+            for tg, M in ((t2, 2), (t32, 32)):
+                line("contains_strings M=%d" % M, lambda: _lib.check(L.cs_contains_strings(col.m_cptr, tg.m_cptr, out8.data_ptr(), 1, None)), M * rows)
+                line("strings_counts M=%d" % M, lambda: _lib.check(L.cs_strings_counts(col.m_cptr, tg.m_cptr, out32.data_ptr(), 1, None)), 4 * M * rows)
+            for chars in (8, 64, 65):
+                target = text[:chars].encode()
+                line("edit_distance target=%d" % chars, lambda: _lib.check(L.cs_edit_distance(col.m_cptr, target, 0, out32.data_ptr(), 1, None)),
+                     4 * rows, reps=1)
+            line("edit_distance_column (self)", lambda: _lib.check(L.cs_edit_distance_column(col.m_cptr, col.m_cptr, 0, out32.data_ptr(), 1, None)),
+                 b + 8.125 * rows + 4 * rows, reps=1)
+            line("porter_stemmer_measure", lambda: _lib.check(L.cs_porter_stemmer_measure(col.m_cptr, None, None, out32.data_ptr(), 1, None)), 4 * rows)
+            if route == "default":
+                def scatter():
+                    o = C.c_void_p()
+                    _lib.check(L.cs_scatter_count(col.m_cptr, cnt.data_ptr(), 1, None, C.byref(o)))
+                    return nvstrings.nvstrings(o.value)
+
+                line("scatter_count (0/1/2)", scatter, 4 * rows + b + 2 * 8.125 * rows)
+        del col
+    L.cs_config_set(b"CS_TEXT_ROWWISE", None)
 
 
 if __name__ == "__main__":

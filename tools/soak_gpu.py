@@ -13,13 +13,13 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import cpulibs  # noqa: E402
 import gpuutil  # noqa: E402
-from custrings_amd import nvtext, nvcategory, _lib  # noqa: E402
+from custrings_amd import nvstrings, nvtext, nvcategory, _lib  # noqa: E402
 
 LIB = _lib.lib
 
 TOGGLES = ("CS_REGEX_TWO_PASS", "CS_REGEX_ROWWISE", "CS_SPLIT_GENERIC", "CS_TOKENIZE_ROWWISE", "CS_STRIP_ROWWISE",
            "CS_FIND_ROWWISE", "CS_REPLACE_ROWWISE", "CS_CASE_ROWWISE", "CS_NGRAM_ROWWISE", "CS_CONVERT_ROWWISE",
-           "CS_NO_CLASS_RUNS")  # (the byte-parallel class route is a fast path too: off in the witness -- it sat on both sides until round 5's last soak)
+           "CS_TEXT_ROWWISE", "CS_NO_CLASS_RUNS")  # (the byte-parallel class route is a fast path too: off in the witness -- it sat on both sides until round 5's last soak)
 PATS = [(r"\d+\.\d+\.\d+\.\d+", "<IP>"), (r"\d", "#"), (r"[a-c]+", "xyz__"), (r"\s+", " "), (r"\w+", "<w>"), (r"b|ab", ""),
         (r"\bx", "YY"), (r"[0-9]+", "<number-here>"), (r"a", "aa"), (r"(a|b)c", "-"),
         (r"\d+\.\d+ ", "<n>"), (r"[a-c]+=>", ""), (r"\d+ab", "#"),  # (chains with a literal suffix)
@@ -137,6 +137,24 @@ def snapshot(g, rows, rng_seed, pats=None, regex_only=False):
         found = C.c_int64()
         L.check(L.lib.cs_chartype(g.m_cptr, k, f.ctypes.data, 0, None, C.byref(found)))
         out[op] = (f[:rows], found.value)
+    # the NVText matches, edit distance, stemmer measure and scatter_count (tile route against the row-wise one: CS_TEXT_ROWWISE)
+    tg = nvstrings.to_device(["a", "ab", "é", "3.4", " ", None, ""])
+    f = np.zeros(max(rows * 7, 1), dtype=np.uint8)
+    L.check(L.lib.cs_contains_strings(g.m_cptr, tg.m_cptr, f.ctypes.data, 0, None))
+    out["contains_strings"] = (f, 0)
+    f = np.zeros(max(rows * 7, 1), dtype=np.uint32)
+    L.check(L.lib.cs_strings_counts(g.m_cptr, tg.m_cptr, f.ctypes.data, 0, None))
+    out["strings_counts"] = (f, 0)
+    for target in ("ab 3.4", "é" * 64, "x" * 65):
+        f = np.zeros(max(rows, 1), dtype=np.uint32)
+        L.check(L.lib.cs_edit_distance(g.m_cptr, target.encode(), 0, f.ctypes.data, 0, None))
+        out["edit_distance %d" % len(target)] = (f, 0)
+    f = np.zeros(max(rows, 1), dtype=np.uint32)
+    L.check(L.lib.cs_porter_stemmer_measure(g.m_cptr, "aeioué".encode(), b"y", f.ctypes.data, 0, None))
+    out["porter_stemmer_measure"] = (f, 0)
+    sc = nvtext.scatter_count(g, [i % 3 for i in range(rows)]) if rows else None
+    if sc is not None:
+        out["scatter_count"] = gpuutil.to_col(sc)
     for sub in ("3.4", "é", "ab"):
         f = np.zeros(max(rows, 1), dtype=np.int32)
         found = C.c_int64()
