@@ -42,24 +42,14 @@ __global__ void __launch_bounds__(256) k_is_empty(ColView in, uint8_t* __restric
 }
 
 int64_t run_is_empty(const cs_column* col, uint8_t* results, int on_device, hipStream_t s) {
-  const int64_t rows = col->rows;
-  Buf tmp;
-  uint8_t* d_out = results;
-  if (!on_device) {
-    tmp = dev_alloc((size_t)rows, s);
-    d_out = ptr<uint8_t>(tmp);
-  }
-  Buf acc = dev_alloc(8, s);
-  CS_HIP(hipMemsetAsync(acc->p, 0, 8, s));
-  hipLaunchKernelGGL(k_is_empty, dim3(std::min(blocks_for(rows), 8192u)), dim3(kBlock), 0, s, view_of(col), d_out,
-                     ptr<unsigned long long>(acc));
+  const ResultsOut res(results, (size_t)col->rows, on_device, s);
+  const Buf acc = zeroed_count(s);
+  hipLaunchKernelGGL(k_is_empty, dim3(std::min(blocks_for(col->rows), 8192u)), dim3(kBlock), 0, s, view_of(col),
+                     static_cast<uint8_t*>(res.dev), ptr<unsigned long long>(acc));
   CS_HIP(hipGetLastError());
   note_route("rows");
-  if (!on_device) CS_HIP(hipMemcpyAsync(results, d_out, (size_t)rows, hipMemcpyDeviceToHost, s));
-  int64_t* host = (int64_t*)pinned_scratch(8);
-  CS_HIP(hipMemcpyAsync(host, acc->p, 8, hipMemcpyDeviceToHost, s));
-  CS_HIP(hipStreamSynchronize(s));
-  return host[0];
+  res.copy_back(s);
+  return read_count(acc, s);
 }
 
 }  // namespace
@@ -75,7 +65,8 @@ int cs_chartype(const cs_column* col, int pred, uint8_t* results, int on_device,
     const hipStream_t s = S(stream);
     int64_t n;
     if (pred == cschr::P_EMPTY) n = run_is_empty(col, results, on_device, s);
-    else n = csparse::run_parse(col, PredParse{cschr::make_pred(pred, h_unicode_flags(), d_unicode_flags())}, results, on_device, s);
+    else n = csparse::run_parse(col, PredParse{cschr::make_pred(pred, h_unicode_flags(), d_unicode_flags())}, results, on_device,
+                                   !cfg("CS_CONVERT_ROWWISE"), s);
     if (count) *count = n;
   });
 }

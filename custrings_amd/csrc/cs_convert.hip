@@ -71,7 +71,7 @@ int parse_entry(const cs_column* col, void* results, int on_device, const char* 
       CS_HIP(hipMemcpyAsync(tb->p, true_string, (size_t)parse.tlen + 1, hipMemcpyHostToDevice, s));
       parse.tstr = ptr<const uint8_t>(tb);
     }
-    const int64_t n = csparse::run_parse(col, parse, results, on_device, s);
+    const int64_t n = csparse::run_parse(col, parse, results, on_device, !cfg("CS_CONVERT_ROWWISE"), s);
     if (count) *count = n;
   });
 }

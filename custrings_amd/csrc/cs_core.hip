@@ -773,6 +773,30 @@ TilePlan plan_row_tiles(const cs_column* c, int slack, hipStream_t s, bool outli
   if (outliers && !cs::cfg("CS_NO_OUTLIER_TILES")) return {64, cstile::kPfBytes - 64};
   return {0, 0};
 }
+StagedTiles plan_staged_tiles(const cs_column* c, int slack, bool outliers, WaveLds w, hipStream_t s) {
+  StagedTiles t;
+  const TilePlan tp = plan_row_tiles(c, 32, s, outliers);
+  const int cap = (int)((tp.span + slack + 15) & ~(int64_t)15);
+  const size_t lds = ((size_t)w.bufs * cap + w.extra) * 4;
+  if (!tp.R || lds > w.ceiling) return t;
+  t.R = tp.R;
+  t.cap = cap;
+  t.ntiles = (c->rows + tp.R - 1) / tp.R;
+  t.grid = (t.ntiles + 3) / 4;
+  t.lds = lds;
+  return t;
+}
+Buf zeroed_count(hipStream_t s) {
+  Buf acc = dev_alloc(8, s);
+  CS_HIP(hipMemsetAsync(acc->p, 0, 8, s));
+  return acc;
+}
+int64_t read_count(const Buf& acc, hipStream_t s) {
+  int64_t* host = (int64_t*)pinned_scratch(8);
+  CS_HIP(hipMemcpyAsync(host, acc->p, 8, hipMemcpyDeviceToHost, s));
+  CS_HIP(hipStreamSynchronize(s));
+  return host[0];
+}
 // How many 64-row tiles span more than `limit` bytes: a column whose LARGEST tile does not fit a tile kernel's staging
 // buffer may still have all but a few that do (one long row among millions of short ones) -- the tile kernels then take
 // the column and handle the oversize tiles a thread per row themselves, instead of the whole column going row-wise.

@@ -53,7 +53,7 @@ void compile_or_fail(const char* format, int units, TsProgram* prog, const char*
 
 int64_t run_ts_parse(const cs_column* col, const TsProgram& prog, int64_t* results, int on_device, hipStream_t s) {
   int64_t n = 0;
-  csdt::ts_dispatch(prog.units, [&](auto u) { n = csparse::run_parse(col, TsParse<decltype(u)::value>{prog}, results, on_device, s); });
+  csdt::ts_dispatch(prog.units, [&](auto u) { n = csparse::run_parse(col, TsParse<decltype(u)::value>{prog}, results, on_device, !cfg("CS_CONVERT_ROWWISE"), s); });
   return n;
 }
 

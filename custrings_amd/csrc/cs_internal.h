@@ -210,6 +210,44 @@ struct TilePlan {
   int64_t span;
 };
 TilePlan plan_row_tiles(const cs_column* c, int slack, hipStream_t s, bool outliers = false);
+// What a kernel that stages its tiles in LDS is launched with, from plan_row_tiles: a wave's staging buffer holds `cap`
+// bytes (the widest tile and `slack`, 32 at least, rounded up to 16), a wave takes a tile at a time and a workgroup has
+// four waves.
+// A wave's LDS is `bufs` buffers of `cap` bytes and `extra` bytes more; R = 0 as well when four of them exceed `ceiling`.
+struct WaveLds {
+  int bufs;
+  size_t extra, ceiling;
+};
+struct StagedTiles {
+  int R = 0, cap = 0;
+  long long ntiles = 0;
+  int64_t grid = 0;  // workgroups wanted (launch_resident caps them)
+  size_t lds = 0;    // dynamic LDS of a workgroup
+};
+StagedTiles plan_staged_tiles(const cs_column* c, int slack, bool outliers, WaveLds w, hipStream_t s);
+
+// Results to the caller's buffer, device or host: the kernels write to `dev` (a temporary for a host caller).
+struct ResultsOut {
+  Buf tmp;
+  void* caller;
+  void* dev;
+  size_t bytes;
+  ResultsOut(void* results, size_t nbytes, int on_device, hipStream_t s) : caller(results), dev(results), bytes(nbytes) {
+    if (on_device) return;
+    tmp = dev_alloc(bytes ? bytes : 1, s);
+    dev = tmp->p;
+  }
+  void copy_back(hipStream_t s) const {  // (nothing waits: finish, read_count or the caller synchronises)
+    if (tmp) CS_HIP(hipMemcpyAsync(caller, dev, bytes, hipMemcpyDeviceToHost, s));
+  }
+  void finish(hipStream_t s) const {
+    copy_back(s);
+    CS_HIP(hipStreamSynchronize(s));
+  }
+};
+// A 64-bit count the kernels add to: zeroed on the device; read_count brings it back (synchronises `s`).
+Buf zeroed_count(hipStream_t s);
+int64_t read_count(const Buf& acc, hipStream_t s);
 }  // namespace cs
 namespace csrow {
 struct CharSet;

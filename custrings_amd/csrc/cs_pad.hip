@@ -62,20 +62,20 @@ __device__ __forceinline__ int32_t size_or_flag(const PadArgs& a, int64_t sz) {
 }
 
 // ---- size pass ---------------------------------------------------------------------------------------------------------
+// the size of row r, its n bytes at p (memory or LDS); -1 for a null row
+__device__ __forceinline__ void size_row(const PadArgs& a, const Params& P, int64_t r, const uint8_t* p, int n, bool valid) {
+  int32_t len = -1;
+  if (valid) {
+    const Pieces pc = cspad::plan_row(P, p, n, row_start(a, r), row_stop(a, r));
+    len = size_or_flag(a, cspad::out_size(P, pc, p));
+  }
+  a.lens[r] = len;
+}
+
 template <int OP>
 __global__ void __launch_bounds__(256) k_pad_size_rows(PadArgs a) {
   const Params P = params_of<OP>(a);
-  for (int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x; r < a.in.rows; r += (int64_t)gridDim.x * kBlock) {
-    int32_t len = -1;
-    if (row_is_valid(a.in.validity, r)) {
-      const int64_t o0 = a.in.offsets[r];
-      const uint8_t* p = a.in.chars + o0;
-      const int n = (int)(a.in.offsets[r + 1] - o0);
-      const Pieces pc = cspad::plan_row(P, p, n, row_start(a, r), row_stop(a, r));
-      len = size_or_flag(a, cspad::out_size(P, pc, p));
-    }
-    a.lens[r] = len;
-  }
+  for_each_row(a.in, [&](int64_t r, const uint8_t* p, int n, bool valid) { size_row(a, P, r, p, n, valid); });
 }
 
 template <int OP>
@@ -84,28 +84,11 @@ __global__ void __launch_bounds__(256) k_pad_size_tile(PadArgs a) {
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
   uint8_t* lds_in = reinterpret_cast<uint8_t*>(smem) + (size_t)wv * a.cap;
   const Params P = params_of<OP>(a);
-  cstile::RowTileWalk walk(a.in, a.rows_per_tile, a.ntiles, wv, lane);
-  if (walk.done()) return;
-  for (;;) {
-    const cstile::RowTile cur = walk.current();
-    const long long want64 = cur.g1 - cur.g0 + cur.lead;
-    const bool oversize = want64 + 48 > a.cap;  // (read from memory: a long row among short ones)
-    cstile::stage_chars(lds_in, oversize ? 0 : (int)want64, lane, walk.pf);
-    const bool more = walk.advance();
-    cstile::wave_lds_fence();
-    if (cur.in_tile) {
-      const int64_t r = cur.r0 + lane;
-      int32_t len = -1;
-      if (cur.live) {
-        const uint8_t* p = oversize ? a.in.chars + (cur.g0 + cur.rbeg) : lds_in + cur.lead + cur.rbeg;
-        const Pieces pc = cspad::plan_row(P, p, cur.n, row_start(a, r), row_stop(a, r));
-        len = size_or_flag(a, cspad::out_size(P, pc, p));
-      }
-      a.lens[r] = len;
-    }
-    cstile::wave_lds_fence();  // (the LDS is restaged next round)
-    if (!more) break;
-  }
+  // (a tile beyond the staging buffer -- a long row among short ones -- is read from memory)
+  cstile::walk_staged_tiles<cstile::Oversize::kFromMemory>(a.in, a.rows_per_tile, a.ntiles, lds_in, a.cap, wv, lane,
+                                                           [&](const cstile::RowTile& cur, const uint8_t* p) {
+    if (cur.in_tile) size_row(a, P, cur.r0 + lane, p, cur.n, cur.live);
+  });
 }
 
 // ---- write pass --------------------------------------------------------------------------------------------------------
@@ -245,13 +228,12 @@ cs_column* run_pad_op(const cs_column* col, PadArgs a, hipStream_t s) {
   a.in = view_of(col);
   // the tile plan: R rows whose bytes fit the prefetch (a column with a few longer tiles still gets it: those tiles go from
   // memory); the staging buffers of four waves must fit the LDS
-  TilePlan tp{0, 0};
-  if (!cs::cfg("CS_PAD_ROWWISE")) tp = plan_row_tiles(col, 32, s, true);
-  a.cap = (int)((tp.span + 48 + 15) & ~(int64_t)15);
-  if ((size_t)a.cap * 4 > 100 * 1024) tp.R = 0;
-  const bool tile = tp.R != 0;
-  a.rows_per_tile = tp.R;
-  a.ntiles = tile ? (rows + tp.R - 1) / tp.R : 0;
+  StagedTiles t;
+  if (!cs::cfg("CS_PAD_ROWWISE")) t = plan_staged_tiles(col, cstile::kStageSlack, true, {1, 0, 100 * 1024}, s);
+  const bool tile = t.R != 0;
+  a.rows_per_tile = t.R;
+  a.cap = t.cap;
+  a.ntiles = t.ntiles;
   const unsigned row_grid = std::min(blocks_for(rows), 65536u);
   if (OP == cspad::OP_WRAP) {
     col->share_extents_with(o.get());
@@ -268,7 +250,7 @@ cs_column* run_pad_op(const cs_column* col, PadArgs a, hipStream_t s) {
       ProfScope ps("k_pad_size", s);
       // (repeat's sizes need the offsets only: staging its bytes made the tile form 5x slower than the row-wise one)
       if (tile && OP != cspad::OP_REPEAT) {
-        launch_resident(&k_pad_size_tile<OP>, (size_t)a.cap * 4, (a.ntiles + 3) / 4, s, a);
+        launch_resident(&k_pad_size_tile<OP>, t.lds, t.grid, s, a);
       } else {
         hipLaunchKernelGGL(k_pad_size_rows<OP>, dim3(row_grid), dim3(kBlock), 0, s, a);
         CS_HIP(hipGetLastError());
@@ -291,7 +273,7 @@ cs_column* run_pad_op(const cs_column* col, PadArgs a, hipStream_t s) {
       // the out-tile: the widest 64-row span of the output (an R-row tile lies inside one), capped
       const int64_t span = o->max_span64 >= 0 ? o->max_span64 : max_span64(o.get(), s);
       a.out_cap = (int)((std::min<int64_t>(span, kOutCapMax) + 16 + 15) & ~(int64_t)15);
-      launch_resident(&k_pad_write_tile<OP>, (size_t)(a.cap + a.out_cap) * 4, (a.ntiles + 3) / 4, s, a);
+      launch_resident(&k_pad_write_tile<OP>, t.lds + (size_t)a.out_cap * 4, t.grid, s, a);
     } else {
       hipLaunchKernelGGL(k_pad_write_rows<OP>, dim3(row_grid), dim3(kBlock), 0, s, a);
       CS_HIP(hipGetLastError());

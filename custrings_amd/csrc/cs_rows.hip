@@ -397,25 +397,22 @@ namespace cs {
 bool find_tiles(const cs_column* in, const unsigned char* needle, int nb, int mode, int start, int end, int32_t* out32,
                 uint8_t* out8, unsigned long long* found, hipStream_t s) {
   if (in->rows == 0 || nb > 64 || cs::cfg("CS_FIND_ROWWISE")) return false;
-  const TilePlan tp = plan_row_tiles(in, 32, s);
-  const int R = tp.R;
-  if (!R) return false;
+  const StagedTiles t = plan_staged_tiles(in, cstile::kStageSlack, false, {1, 2 * (cstile::kPfBytes / 8 + 32), 150 * 1024}, s);
+  if (!t.R) return false;
   FindTileArgs a{};
   a.in = view_of(in);
   for (int i = 0; i < nb; ++i) a.needle[i] = needle[i];
   a.nb = nb;
   a.start = start;
   a.end = end;
-  a.rows_per_tile = R;
-  a.cap = (int)((tp.span + 48 + 15) & ~(int64_t)15);
-  a.ntiles = (in->rows + R - 1) / R;
+  a.rows_per_tile = t.R;
+  a.cap = t.cap;
+  a.ntiles = t.ntiles;
   a.out32 = out32;
   a.out8 = out8;
   a.found = found;
   a.whole = mode != 0 || (start <= 0 && end - (start < 0 ? 0 : start) < 0);
-  const size_t lds = ((size_t)a.cap + 2 * (cstile::kPfBytes / 8 + 32)) * 4;
-  if (lds > 150 * 1024) return false;
-  launch_resident(mode == 0 ? &k_find_tile<0> : &k_find_tile<1>, lds, (a.ntiles + 3) / 4, s, a);
+  launch_resident(mode == 0 ? &k_find_tile<0> : &k_find_tile<1>, t.lds, t.grid, s, a);
   return true;
 }
 
@@ -424,22 +421,19 @@ bool strip_write_tiles(const cs_column* in, const CharSet& set, int side, const 
   if (in->rows == 0 || cs::cfg("CS_STRIP_ROWWISE")) return false;
   // (no tile size fits every tile: the kernel copies the rows of a tile beyond the staging size straight from memory, long
   // rows by the whole wave)
-  const TilePlan tp = plan_row_tiles(in, 32, s, true);
-  const int R = tp.R;
-  if (!R) return false;
+  const StagedTiles t = plan_staged_tiles(in, cstile::kStageSlack, true, {2, 0, 150 * 1024}, s);
+  if (!t.R) return false;
   StripTileArgs a{};
   a.in = view_of(in);
   a.set = set;
   a.side = side;
-  a.rows_per_tile = R;
-  a.cap = (int)((tp.span + 48 + 15) & ~(int64_t)15);
-  a.ntiles = (in->rows + R - 1) / R;
+  a.rows_per_tile = t.R;
+  a.cap = t.cap;
+  a.ntiles = t.ntiles;
   a.out_off = out_off;
   a.out_chars = out_chars;
-  const size_t lds = (size_t)a.cap * 2 * 4;
-  if (lds > 150 * 1024) return false;
   ProfScope ps("k_strip_write", s);
-  launch_resident(&k_strip_tile, lds, (a.ntiles + 3) / 4, s, a);
+  launch_resident(&k_strip_tile, t.lds, t.grid, s, a);
   return true;
 }
 

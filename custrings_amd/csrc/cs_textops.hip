@@ -2,7 +2,8 @@
 // (reference: cpp/src/text/NVText.cu:32-172, edit_distance.cu:33-228, stemmer.cu:29-104).  The per-row logic is
 // text_ops.h, shared with the CPU harness of tests/text_model.py.
 //
-// Two routes, as parse_route.h has them, under a switch of their own (CS_TEXT_ROWWISE=1 takes the row-wise one):
+// Two routes, those of parse_route.h, under a switch of their own (CS_TEXT_ROWWISE=1 takes the row-wise one); the ops of one
+// value a row (porter_stemmer_measure, edit_distance against a short target) are parsers of that header:
 //  - tile: a wave stages the bytes of R = 64 / 32 / 16 consecutive rows in LDS (cstile::RowTileWalk: the next tile's bytes
 //    in flight while this one is worked on) and each lane runs its row out of LDS.  What every row needs beside its bytes
 //    is copied into LDS once per workgroup: the bit-vector table of edit_distance (1792 bytes), the target column of
@@ -22,6 +23,7 @@
 
 #include "cs_internal.h"
 #include "device_utils.h"
+#include "parse_route.h"
 #include "text_ops.h"
 #include "tile_utils.h"
 
@@ -36,113 +38,24 @@ constexpr int kOutTileBytes = 4096;  // a wave's assembled block of match result
 
 bool rowwise() { return cfg("CS_TEXT_ROWWISE") != nullptr && std::strcmp(cfg("CS_TEXT_ROWWISE"), "0") != 0; }
 
-struct Tiles {
-  int R = 0, cap = 0;
-  long long ntiles = 0;
-};
-Tiles plan(const cs_column* col, hipStream_t s) {
-  Tiles t;
-  if (rowwise()) return t;
-  const TilePlan tp = plan_row_tiles(col, 32, s);
-  if (!tp.R) return t;
-  t.R = tp.R;
-  t.cap = (int)((tp.span + 48 + 15) & ~(int64_t)15);
-  t.ntiles = (col->rows + tp.R - 1) / tp.R;
-  return t;
+StagedTiles plan(const cs_column* col, hipStream_t s) {
+  return rowwise() ? StagedTiles{} : plan_staged_tiles(col, cstile::kStageSlack, false, {1, 0, 150 * 1024}, s);
 }
 
-// results to the caller's buffer (device or host)
-struct Results {
-  Buf tmp;
-  void* caller;
-  void* dev;
-  size_t bytes;
-  bool on_device;
-  Results(void* results, size_t nbytes, int on_dev, hipStream_t s) : caller(results), dev(results), bytes(nbytes), on_device(on_dev != 0) {
-    if (!on_device) {
-      tmp = dev_alloc(bytes ? bytes : 1, s);
-      dev = tmp->p;
-    }
-  }
-  void finish(hipStream_t s) {
-    if (!on_device) CS_HIP(hipMemcpyAsync(caller, dev, bytes, hipMemcpyDeviceToHost, s));
-    CS_HIP(hipStreamSynchronize(s));
-  }
-};
-
-// ---- one value a row ---------------------------------------------------------------------------------------------------
-// A parser P: `T operator()(p, n, valid, shared)` over the row's bytes; `shared_bytes` of LDS filled once per workgroup
-// by `stage(lds, tid)` (nullptr on the row-wise route).
-template <class P>
-struct ValueArgs {
-  ColView in;
-  typename P::T* out;
-  int rows_per_tile, cap, shared;
-  long long ntiles;
-  P parse;
-};
-template <class P>
-__global__ void __launch_bounds__(256) k_value_rows(ValueArgs<P> a) {
-  for (int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x; r < a.in.rows; r += (int64_t)gridDim.x * kBlock) {
-    const bool ok = row_is_valid(a.in.validity, r);
-    const int64_t o0 = a.in.offsets[r];
-    a.out[r] = a.parse(a.in.chars + o0, ok ? (int)(a.in.offsets[r + 1] - o0) : 0, ok, nullptr);
-  }
-}
-template <class P>
-__global__ void __launch_bounds__(256) k_value_tile(ValueArgs<P> a) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-  uint8_t* shared = reinterpret_cast<uint8_t*>(smem);
-  uint8_t* lds_in = shared + a.shared + (size_t)wv * a.cap;
-  a.parse.stage(shared, (int)threadIdx.x);
-  __syncthreads();
-  cstile::RowTileWalk walk(a.in, a.rows_per_tile, a.ntiles, wv, lane);
-  if (walk.done()) return;
-  for (;;) {
-    const cstile::RowTile cur = walk.current();
-    cstile::stage_chars(lds_in, (int)(cur.g1 - cur.g0) + cur.lead, lane, walk.pf);  // (lead + span <= cap: checked by the host)
-    const bool more = walk.advance();
-    cstile::wave_lds_fence();
-    if (cur.in_tile) a.out[cur.r0 + lane] = a.parse(lds_in + cur.lead + cur.rbeg, cur.n, cur.live, shared);
-    cstile::wave_lds_fence();
-    if (!more) break;
-  }
-}
-// returns true when the tile route ran
-template <class P>
-bool run_value(const cs_column* col, const P& parse, int shared_bytes, bool tiles_allowed, typename P::T* d_out, hipStream_t s) {
-  ValueArgs<P> a{};
-  a.in = view_of(col);
-  a.out = d_out;
-  a.parse = parse;
-  const Tiles t = tiles_allowed ? plan(col, s) : Tiles{};
-  if (t.R) {
-    a.rows_per_tile = t.R;
-    a.cap = t.cap;
-    a.ntiles = t.ntiles;
-    a.shared = (shared_bytes + 15) & ~15;
-    launch_resident(&k_value_tile<P>, (size_t)a.shared + (size_t)a.cap * 4, (t.ntiles + 3) / 4, s, a);
-    note_route("tile");
-    return true;
-  }
-  hipLaunchKernelGGL(k_value_rows<P>, dim3(std::min(blocks_for(col->rows), 8192u)), dim3(kBlock), 0, s, a);
-  CS_HIP(hipGetLastError());
-  note_route("rows");
-  return false;
-}
-
+// ---- one value a row: parsers of parse_route.h, not counted -----------------------------------------------------------------
 struct MeasureParse {
   using T = uint32_t;
+  static constexpr bool kCounted = false;
   cstxt::VowelSpec spec;
-  __device__ __forceinline__ void stage(uint8_t*, int) const {}
-  __device__ __forceinline__ T operator()(const uint8_t* p, int n, bool, const uint8_t*) const { return cstxt::measure_row(p, n, spec); }
+  __device__ __forceinline__ T operator()(const uint8_t* p, int n, bool) const { return cstxt::measure_row(p, n, spec); }
 };
 
 // the bit-vector table in LDS: ascii[128] (uint64), mask[64] (uint64), ch[64] (uint32)
 constexpr int kPeqBytes = 128 * 8 + cstxt::kBitTargetChars * 8 + cstxt::kBitTargetChars * 4;
 struct EditBitsParse {
   using T = uint32_t;
+  static constexpr bool kCounted = false;
+  static constexpr int kSharedBytes = kPeqBytes;
   const uint32_t* table;  // the same layout in device memory
   int nlist, m;
   __device__ __forceinline__ void stage(uint8_t* lds, int tid) const {
@@ -256,8 +169,7 @@ void run_edit_scalar(const cs_column* col, const char* target, uint32_t* d_out, 
   refuse_long_rows(col, s);
   cstxt::PeqTable q;
   cstxt::build_peq(t, tn, q);
-  const Tiles tl = q.m ? plan(col, s) : Tiles{};
-  if (!tl.R) return run_edit_dp(col, nullptr, target, d_out, s);
+  if (!q.m || !plan(col, s).R) return run_edit_dp(col, nullptr, target, d_out, s);
   uint32_t* host = (uint32_t*)pinned_scratch(kPeqBytes);
   std::memcpy(host, q.ascii, 128 * 8);
   std::memcpy(host + 256, q.mask, cstxt::kBitTargetChars * 8);
@@ -265,7 +177,7 @@ void run_edit_scalar(const cs_column* col, const char* target, uint32_t* d_out, 
   Buf table = dev_alloc(kPeqBytes, s);
   CS_HIP(hipMemcpyAsync(table->p, host, kPeqBytes, hipMemcpyHostToDevice, s));
   CS_HIP(hipStreamSynchronize(s));  // (the pinned scratch is free again)
-  run_value(col, EditBitsParse{ptr<const uint32_t>(table), q.nlist, q.m}, kPeqBytes, true, d_out, s);
+  csparse::launch_parse(col, EditBitsParse{ptr<const uint32_t>(table), q.nlist, q.m}, d_out, nullptr, true, s);
   CS_HIP(hipStreamSynchronize(s));
 }
 
@@ -306,11 +218,7 @@ __device__ __forceinline__ void match_row(const uint8_t* p, int n, bool live, co
 template <class T, bool COUNT>
 __global__ void __launch_bounds__(256) k_match_rows(MatchArgs<T> a) {
   const TargetsInMemory tg{a.tg};
-  for (int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x; r < a.in.rows; r += (int64_t)gridDim.x * kBlock) {
-    const bool ok = row_is_valid(a.in.validity, r);
-    const int64_t o0 = a.in.offsets[r];
-    match_row<T, COUNT>(a.in.chars + o0, ok ? (int)(a.in.offsets[r + 1] - o0) : 0, ok, tg, a.M, a.out + r * a.M);
-  }
+  for_each_row(a.in, [&](int64_t r, const uint8_t* p, int n, bool ok) { match_row<T, COUNT>(p, n, ok, tg, a.M, a.out + r * a.M); });
 }
 template <class T, bool COUNT, bool STAGED>
 __global__ void __launch_bounds__(256) k_match_tile(MatchArgs<T> a) {
@@ -333,28 +241,21 @@ __global__ void __launch_bounds__(256) k_match_tile(MatchArgs<T> a) {
     }
     __syncthreads();
   }
-  cstile::RowTileWalk walk(a.in, a.rows_per_tile, a.ntiles, wv, lane);
-  if (walk.done()) return;
-  for (;;) {
-    const cstile::RowTile cur = walk.current();
-    cstile::stage_chars(lds_in, (int)(cur.g1 - cur.g0) + cur.lead, lane, walk.pf);  // (lead + span <= cap: checked by the host)
-    const bool more = walk.advance();
-    cstile::wave_lds_fence();
-    const uint8_t* p = lds_in + cur.lead + cur.rbeg;
+  // (every tile's span fits the staging buffer: checked by the host)
+  cstile::walk_staged_tiles<cstile::Oversize::kHostChecked>(a.in, a.rows_per_tile, a.ntiles, lds_in, a.cap, wv, lane,
+                                                            [&](const cstile::RowTile& cur, const uint8_t* p) {
     T* o = a.out_cap ? lds_out + (size_t)lane * a.M : a.out + (cur.r0 + lane) * a.M;
     if (cur.in_tile) {
       if (STAGED) match_row<T, COUNT>(p, cur.n, cur.live, TargetsInLds{tg_bytes, tg_ext}, a.M, o);
       else match_row<T, COUNT>(p, cur.n, cur.live, TargetsInMemory{a.tg}, a.M, o);
     }
-    cstile::wave_lds_fence();
     if (a.out_cap) {  // the wave's nrows x M results lie side by side in memory
+      cstile::wave_lds_fence();
       T* g = a.out + cur.r0 * a.M;
       const int total = cur.nrows * a.M;
       for (int i = lane; i < total; i += 64) g[i] = lds_out[i];
-      cstile::wave_lds_fence();
     }
-    if (!more) break;
-  }
+  });
 }
 template <class T, bool COUNT>
 void run_match(const cs_column* col, const cs_column* targets, T* d_out, hipStream_t s) {
@@ -363,7 +264,7 @@ void run_match(const cs_column* col, const cs_column* targets, T* d_out, hipStre
   a.tg = view_of(targets);
   a.out = d_out;
   a.M = (int)targets->rows;
-  const Tiles t = plan(col, s);
+  const StagedTiles t = plan(col, s);
   if (!t.R) {
     hipLaunchKernelGGL((k_match_rows<T, COUNT>), dim3(std::min(blocks_for(col->rows), 8192u)), dim3(kBlock), 0, s, a);
     CS_HIP(hipGetLastError());
@@ -377,10 +278,9 @@ void run_match(const cs_column* col, const cs_column* targets, T* d_out, hipStre
   a.tg_bytes = staged ? (int)((targets->nbytes + 15) & ~(int64_t)15) : 0;
   const size_t block = sizeof(T) * (size_t)t.R * (size_t)a.M;
   a.out_cap = block <= (size_t)kOutTileBytes ? (int)((block + 15) & ~(size_t)15) : 0;
-  const size_t lds = (staged ? (size_t)a.tg_bytes + (((size_t)a.M * 8 + 15) & ~(size_t)15) : 0) + (size_t)4 * a.cap + (size_t)4 * a.out_cap;
-  const int64_t wanted = (t.ntiles + 3) / 4;
-  if (staged) launch_resident(&k_match_tile<T, COUNT, true>, lds, wanted, s, a);
-  else launch_resident(&k_match_tile<T, COUNT, false>, lds, wanted, s, a);
+  const size_t lds = (staged ? (size_t)a.tg_bytes + (((size_t)a.M * 8 + 15) & ~(size_t)15) : 0) + t.lds + (size_t)4 * a.out_cap;
+  if (staged) launch_resident(&k_match_tile<T, COUNT, true>, lds, t.grid, s, a);
+  else launch_resident(&k_match_tile<T, COUNT, false>, lds, t.grid, s, a);
   note_route("tile");
 }
 template <class T, bool COUNT>
@@ -390,7 +290,7 @@ void match_entry(const cs_column* col, const cs_column* targets, T* results, int
   if (targets->rows > (1 << 20)) fail(CS_ERR_RANGE, "nvtext: more than 2^20 targets");
   require_device();
   const hipStream_t s = S(stream);
-  Results res(results, sizeof(T) * (size_t)col->rows * (size_t)targets->rows, on_device, s);
+  const ResultsOut res(results, sizeof(T) * (size_t)col->rows * (size_t)targets->rows, on_device, s);
   run_match<T, COUNT>(col, targets, static_cast<T*>(res.dev), s);
   res.finish(s);
 }
@@ -423,7 +323,7 @@ int cs_edit_distance(const cs_column* col, const char* target, int algo, uint32_
     if (col->rows == 0) return;
     require_device();
     const hipStream_t s = S(stream);
-    Results res(results, sizeof(uint32_t) * (size_t)col->rows, on_device, s);
+    const ResultsOut res(results, sizeof(uint32_t) * (size_t)col->rows, on_device, s);
     run_edit_scalar(col, target, static_cast<uint32_t*>(res.dev), s);
     res.finish(s);
   });
@@ -438,7 +338,7 @@ int cs_edit_distance_column(const cs_column* col, const cs_column* targets, int 
     const hipStream_t s = S(stream);
     refuse_long_rows(col, s);
     refuse_long_rows(targets, s);
-    Results res(results, sizeof(uint32_t) * (size_t)col->rows, on_device, s);
+    const ResultsOut res(results, sizeof(uint32_t) * (size_t)col->rows, on_device, s);
     run_edit_dp(col, targets, nullptr, static_cast<uint32_t*>(res.dev), s);
     res.finish(s);
   });
@@ -455,9 +355,8 @@ int cs_porter_stemmer_measure(const cs_column* col, const char* vowels, const ch
     Buf more = dev_alloc(sizeof(cstxt::Char) * cap, s);
     const cstxt::VowelSpec spec = cstxt::make_vowels(vowels, y_char, overflow.data(), (int)cap, ptr<const cstxt::Char>(more));
     if (spec.nmore) CS_HIP(hipMemcpyAsync(more->p, overflow.data(), sizeof(cstxt::Char) * (size_t)spec.nmore, hipMemcpyHostToDevice, s));
-    Results res(results, sizeof(uint32_t) * (size_t)col->rows, on_device, s);
-    run_value(col, MeasureParse{spec}, 0, spec.nmore == 0, static_cast<uint32_t*>(res.dev), s);
-    res.finish(s);  // (synchronises: `overflow` and `more` stay alive until the copy and the kernel are done)
+    // (synchronises: `overflow` and `more` stay alive until the copy and the kernel are done)
+    csparse::run_parse(col, MeasureParse{spec}, results, on_device, !rowwise() && spec.nmore == 0, s);
   });
 }
 int cs_scatter_count(const cs_column* col, const uint32_t* counts, int on_device, cs_stream stream, cs_column** out) {
@@ -476,14 +375,10 @@ int cs_scatter_count(const cs_column* col, const uint32_t* counts, int on_device
       CS_HIP(hipMemcpyAsync(held->p, counts, sizeof(uint32_t) * (size_t)rows, hipMemcpyHostToDevice, s));
       d_counts = ptr<const uint32_t>(held);
     }
-    Buf acc = dev_alloc(8, s);
-    CS_HIP(hipMemsetAsync(acc->p, 0, 8, s));
+    const Buf acc = zeroed_count(s);
     hipLaunchKernelGGL(k_sum_counts, dim3(std::min(blocks_for(rows), 8192u)), dim3(kBlock), 0, s, d_counts, rows, ptr<unsigned long long>(acc));
     CS_HIP(hipGetLastError());
-    int64_t* host = (int64_t*)pinned_scratch(8);
-    CS_HIP(hipMemcpyAsync(host, acc->p, 8, hipMemcpyDeviceToHost, s));
-    CS_HIP(hipStreamSynchronize(s));
-    const int64_t total = host[0];
+    const int64_t total = read_count(acc, s);
     if (total >= ((int64_t)1 << 31)) fail(CS_ERR_RANGE, "nvtext: scatter_count would make 2^31 rows or more");
     note_route("rows");
     if (total == 0) {

@@ -124,6 +124,17 @@ __device__ __forceinline__ bool row_is_valid(const uint8_t* validity, long long 
   return validity == nullptr || ((validity[r >> 3] >> (r & 7)) & 1);
 }
 
+// The row loop of the row-wise kernels (a thread per row on a capped grid of kBlock threads): body(r, p, n, valid) with
+// the row's bytes [p, p + n) in memory, n = 0 for a null row.  `in`: a column view (chars, offsets, validity, rows).
+template <class Col, class Body>
+__device__ __forceinline__ void for_each_row(const Col& in, Body&& body) {
+  for (int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x; r < in.rows; r += (int64_t)gridDim.x * kBlock) {
+    const bool ok = row_is_valid(in.validity, r);
+    const int64_t o0 = in.offsets[r];
+    body(r, in.chars + o0, ok ? (int)(in.offsets[r + 1] - o0) : 0, ok);
+  }
+}
+
 // copies n bytes between arbitrarily aligned global addresses, 8 bytes at a time
 __device__ __forceinline__ void copy_bytes(uint8_t* __restrict__ d, const uint8_t* __restrict__ s, int n) {
   int i = 0;

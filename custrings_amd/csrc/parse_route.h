@@ -1,6 +1,7 @@
-// The parse route of the conversions (string -> one value per row): cs_convert.hip (hash / stoi / ... / to_bools) and
-// cs_datetime.hip (timestamp2long) each instantiate it with a per-row parser, in their own translation unit (the
-// numeric parsers are built with -ffp-contract=off).  A parser P is a functor
+// The parse route (string -> one value per row): cs_convert.hip (hash / stoi / ... / to_bools), cs_datetime.hip
+// (timestamp2long), cs_chartype.hip (the predicates) and cs_textops.hip (stemmer measure, bit-vector edit distance)
+// each instantiate it with a per-row parser, in their own translation unit (the numeric parsers are built with
+// -ffp-contract=off).  A parser P is a functor
 //   using T = <result type>;
 //   __device__ T operator()(const uint8_t* p, int n, bool valid) const;  // row bytes [p, p + n); valid false = null row
 // passed by value in the kernel arguments with its state (the true string of to_bools, the timestamp program).
@@ -9,10 +10,16 @@
 //    (cstile::RowTileWalk: the next tile's bytes in flight while this one is parsed), each lane parses its row out of
 //    LDS and the wave stores its R results side by side.  Taken when every R-row tile of the column fits the prefetch.
 //  - rows: a thread per row reading its bytes from memory (columns no tile size fits -- rows of several KB -- and
-//    CS_CONVERT_ROWWISE=1).
+//    the caller's row-wise switch: CS_CONVERT_ROWWISE=1, CS_TEXT_ROWWISE=1).
 //  Both count the non-zero results with one atomic per workgroup (see k_len, cs_array.hip).
+// A parser may declare two more things (cs_textops.hip does):
+//   static constexpr int kSharedBytes = <n>;  // LDS filled once per workgroup by `stage(lds, tid)` in front of the staged
+//                                             // rows and handed to `operator()(p, n, valid, shared)`; tile route only
+//   static constexpr bool kCounted = false;   // nobody asks for the count: no reduction, no atomic
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "cs_internal.h"
 #include "device_utils.h"
@@ -21,6 +28,15 @@
 namespace csparse {
 
 using cs::ColView;
+
+template <class P, class = void>
+struct SharedBytes : std::integral_constant<int, 0> {};
+template <class P>
+struct SharedBytes<P, std::void_t<decltype(P::kSharedBytes)>> : std::integral_constant<int, (P::kSharedBytes + 15) & ~15> {};
+template <class P, class = void>
+struct Counted : std::true_type {};
+template <class P>
+struct Counted<P, std::void_t<decltype(P::kCounted)>> : std::integral_constant<bool, P::kCounted> {};
 
 template <class P>
 struct ParseArgs {
@@ -32,94 +48,91 @@ struct ParseArgs {
   P parse;
 };
 
+// the parser on a row; `shared`: its LDS region (nullptr on the row-wise route)
+template <class P>
+__device__ __forceinline__ typename P::T parse_row(const P& parse, const uint8_t* p, int n, bool valid, const uint8_t* shared) {
+  if constexpr (SharedBytes<P>::value != 0) return parse(p, n, valid, shared);
+  else return parse(p, n, valid);
+}
+template <class P>
+__device__ __forceinline__ void add_nonzero(const ParseArgs<P>& a, long long v) {
+  if constexpr (Counted<P>::value) {
+    const long long t = csdev::block_reduce_sum_ll(v);
+    if (threadIdx.x == 0 && t) atomicAdd(a.nonzero, (unsigned long long)t);
+  }
+}
+
 template <class P>
 __global__ void __launch_bounds__(256) k_parse_rows(ParseArgs<P> a) {
   using T = typename P::T;
   long long v = 0;
-  for (int64_t r = (int64_t)blockIdx.x * csdev::kBlock + threadIdx.x; r < a.in.rows; r += (int64_t)gridDim.x * csdev::kBlock) {
-    const bool ok = csdev::row_is_valid(a.in.validity, r);
-    const int64_t o0 = a.in.offsets[r];
-    const T x = a.parse(a.in.chars + o0, ok ? (int)(a.in.offsets[r + 1] - o0) : 0, ok);
+  csdev::for_each_row(a.in, [&](int64_t r, const uint8_t* p, int n, bool ok) {
+    const T x = parse_row(a.parse, p, n, ok, nullptr);
     a.out[r] = x;
     v += x != (T)0;
-  }
-  const long long t = csdev::block_reduce_sum_ll(v);
-  if (threadIdx.x == 0 && t) atomicAdd(a.nonzero, (unsigned long long)t);
+  });
+  add_nonzero(a, v);
 }
 
 // A wave per R-row tile, persistent over a contiguous run of tiles (every wave reaches the reduction at the end).
 template <class P>
 __global__ void __launch_bounds__(256) k_parse_tile(ParseArgs<P> a) {
   using T = typename P::T;
+  constexpr int kShared = SharedBytes<P>::value;
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-  uint8_t* lds_in = reinterpret_cast<uint8_t*>(smem) + (size_t)wv * a.cap;
-  cstile::RowTileWalk walk(a.in, a.rows_per_tile, a.ntiles, wv, lane);
+  uint8_t* shared = reinterpret_cast<uint8_t*>(smem);
+  uint8_t* lds_in = shared + kShared + (size_t)wv * a.cap;
+  if constexpr (kShared != 0) {
+    a.parse.stage(shared, (int)threadIdx.x);
+    __syncthreads();
+  }
   long long v = 0;
-  if (!walk.done()) {
-    for (;;) {
-      const cstile::RowTile cur = walk.current();
-      // (lead + span <= cap: every tile's span fits, checked by the host)
-      cstile::stage_chars(lds_in, (int)(cur.g1 - cur.g0) + cur.lead, lane, walk.pf);
-      const bool more = walk.advance();  // the next tile's bytes travel while this one is parsed
-      cstile::wave_lds_fence();
-      if (cur.in_tile) {
-        const T x = a.parse(lds_in + cur.lead + cur.rbeg, cur.n, cur.live);
-        a.out[cur.r0 + lane] = x;
-        v += x != (T)0;
-      }
-      cstile::wave_lds_fence();  // (the LDS is restaged next round)
-      if (!more) break;
-    }
-  }
-  const long long t = csdev::block_reduce_sum_ll(v);
-  if (threadIdx.x == 0 && t) atomicAdd(a.nonzero, (unsigned long long)t);
+  // (every tile's span fits the staging buffer: checked by the host)
+  cstile::walk_staged_tiles<cstile::Oversize::kHostChecked>(a.in, a.rows_per_tile, a.ntiles, lds_in, a.cap, wv, lane,
+                                                            [&](const cstile::RowTile& cur, const uint8_t* p) {
+    if (!cur.in_tile) return;
+    const T x = parse_row(a.parse, p, cur.n, cur.live, shared);
+    a.out[cur.r0 + lane] = x;
+    v += x != (T)0;
+  });
+  add_nonzero(a, v);
 }
 
+// The launch, results to device memory; `tiles`: the tile route may be taken (the family's row-wise switch is off and
+// the parser works out of LDS).  Returns true when it was.
 template <class P>
-bool parse_tiles(const cs_column* col, ParseArgs<P> a, hipStream_t s) {
-  if (cs::cfg("CS_CONVERT_ROWWISE")) return false;
-  const cs::TilePlan tp = cs::plan_row_tiles(col, 32, s);
-  if (!tp.R) return false;
-  a.rows_per_tile = tp.R;
-  a.cap = (int)((tp.span + 48 + 15) & ~(int64_t)15);
-  a.ntiles = (col->rows + tp.R - 1) / tp.R;
-  const size_t lds = (size_t)a.cap * 4;
-  if (lds > 150 * 1024) return false;
-  cs::launch_resident(&k_parse_tile<P>, lds, (a.ntiles + 3) / 4, s, a);
-  return true;
-}
-
-// results to the caller's buffer (device or host); returns the count of non-zero results
-template <class P>
-int64_t run_parse(const cs_column* col, const P& parse, void* results, int on_device, hipStream_t s) {
-  using T = typename P::T;
-  const int64_t rows = col->rows;
-  cs::Buf tmp;
-  void* d_out = results;
-  if (!on_device) {
-    tmp = cs::dev_alloc(sizeof(T) * (size_t)rows, s);
-    d_out = tmp->p;
-  }
-  cs::Buf acc = cs::dev_alloc(8, s);
-  CS_HIP(hipMemsetAsync(acc->p, 0, 8, s));
+bool launch_parse(const cs_column* col, const P& parse, typename P::T* d_out, unsigned long long* nonzero, bool tiles, hipStream_t s) {
   ParseArgs<P> a{};
   a.in = cs::view_of(col);
-  a.out = static_cast<T*>(d_out);
-  a.nonzero = cs::ptr<unsigned long long>(acc);
+  a.out = d_out;
+  a.nonzero = nonzero;
   a.parse = parse;
-  if (parse_tiles(col, a, s)) {
-    cs::note_route("tile");
-  } else {
-    cs::note_route("rows");
-    hipLaunchKernelGGL(k_parse_rows<P>, dim3(std::min(cs::blocks_for(rows), 8192u)), dim3(csdev::kBlock), 0, s, a);
-    CS_HIP(hipGetLastError());
+  const cs::StagedTiles t = tiles ? cs::plan_staged_tiles(col, cstile::kStageSlack, false, {1, 0, 150 * 1024}, s) : cs::StagedTiles{};
+  cs::note_route(t.R ? "tile" : "rows");
+  if (t.R) {
+    a.rows_per_tile = t.R;
+    a.cap = t.cap;
+    a.ntiles = t.ntiles;
+    cs::launch_resident(&k_parse_tile<P>, SharedBytes<P>::value + t.lds, t.grid, s, a);
+    return true;
   }
-  if (!on_device) CS_HIP(hipMemcpyAsync(results, d_out, sizeof(T) * (size_t)rows, hipMemcpyDeviceToHost, s));
-  int64_t* host = (int64_t*)cs::pinned_scratch(8);
-  CS_HIP(hipMemcpyAsync(host, acc->p, 8, hipMemcpyDeviceToHost, s));
+  hipLaunchKernelGGL(k_parse_rows<P>, dim3(std::min(cs::blocks_for(col->rows), 8192u)), dim3(csdev::kBlock), 0, s, a);
+  CS_HIP(hipGetLastError());
+  return false;
+}
+
+// results to the caller's buffer (device or host); returns the count of non-zero results (0 for a parser that is not counted)
+template <class P>
+int64_t run_parse(const cs_column* col, const P& parse, void* results, int on_device, bool tiles, hipStream_t s) {
+  using T = typename P::T;
+  const cs::ResultsOut res(results, sizeof(T) * (size_t)col->rows, on_device, s);
+  const cs::Buf acc = Counted<P>::value ? cs::zeroed_count(s) : nullptr;
+  launch_parse(col, parse, static_cast<T*>(res.dev), cs::ptr<unsigned long long>(acc), tiles, s);
+  res.copy_back(s);
+  if (Counted<P>::value) return cs::read_count(acc, s);
   CS_HIP(hipStreamSynchronize(s));
-  return host[0];
+  return 0;
 }
 
 // the format ops' input validity: LSB-first, bit = 1 valid; nullptr = all valid

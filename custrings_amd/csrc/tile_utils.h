@@ -429,6 +429,32 @@ struct RowTileWalk {
   }
 };
 
+// A wave's whole run on the route "stage R rows in LDS, a lane works on its row": every tile's bytes go from the
+// prefetch registers to `lds_in` (the wave's staging buffer of `cap` bytes), the next tile's loads are issued, and
+// `body(cur, p)` runs between two wave fences, p = the lane's row in LDS.  The whole wave calls the body: it tests
+// cur.in_tile / cur.live itself, and a wave-level step behind the rows (with a fence of its own in front) is part of it.
+// A tile beyond the staging buffer either cannot happen (the host's plan fits every tile), or is not staged and the
+// body gets the row in memory.
+enum class Oversize { kHostChecked, kFromMemory };
+constexpr int kStageSlack = 48;  // what the host adds to the widest tile for `cap`: a body may read that far past its row
+template <Oversize OV, class Col, class Body>
+__device__ __forceinline__ void walk_staged_tiles(const Col& in, int rows_per_tile, long long ntiles, uint8_t* lds_in, int cap, int wv,
+                                                  int lane, Body&& body) {
+  RowTileWalk walk(in, rows_per_tile, ntiles, wv, lane);
+  if (walk.done()) return;
+  for (;;) {
+    const RowTile cur = walk.current();
+    const long long want64 = cur.g1 - cur.g0 + cur.lead;
+    const bool oversize = OV == Oversize::kFromMemory && want64 + kStageSlack > cap;  // (a long row among short ones)
+    stage_chars(lds_in, oversize ? 0 : (int)want64, lane, walk.pf);
+    const bool more = walk.advance();  // the next tile's bytes travel while this one is worked on
+    wave_lds_fence();
+    body(cur, oversize ? in.chars + (cur.g0 + cur.rbeg) : lds_in + cur.lead + cur.rbeg);
+    wave_lds_fence();  // (the LDS is restaged next round)
+    if (!more) break;
+  }
+}
+
 // Decoupled look-back in two halves so that independent work (assembling the output
 // rows in LDS) runs between publishing this sub-tile's aggregate and needing the
 // predecessors': lookback_begin publishes and issues the first poll, lookback_end
