@@ -714,22 +714,17 @@ cs_category* cs::category_build(const cs_column* col, hipStream_t s) {
   }
   // keys column
   const int64_t nkeys = uniq + shift;
-  auto keys = std::make_unique<cs_column>();
-  keys->rows = nkeys;
-  keys->null_count = shift;
+  Built b(nkeys, shift ? Nulls::separate : Nulls::none, s);  // (the null key, when there is one, is key 0)
+  b.col->null_count = shift;
   Buf lens = dev_alloc(sizeof(int32_t) * nkeys, s);
   hipLaunchKernelGGL(k_key_sizes, dim3(blocks_for(nkeys)), dim3(kBlock), 0, s, in, ptr<const Entry>(table),
                      ptr<const int32_t>(item), nkeys, shift, ptr<int32_t>(lens));
-  keys->offsets = dev_alloc(sizeof(int64_t) * (nkeys + 1), s);
-  LenMeta meta;
-  keys->nbytes = offsets_from_lengths(ptr<int32_t>(lens), nkeys, ptr<int64_t>(keys->offsets), s, nullptr, &meta);
-  meta.give(keys.get());
-  keys->chars = dev_alloc((size_t)keys->nbytes, s);
-  if (shift) keys->validity = validity_from_lengths(ptr<int32_t>(lens), nkeys, s);
+  b.scan(ptr<int32_t>(lens));
+  b.alloc_chars();
   hipLaunchKernelGGL(k_key_copy, dim3(blocks_for(nkeys)), dim3(kBlock), 0, s, in, ptr<const Entry>(table),
-                     ptr<const int32_t>(item), nkeys, shift, keys->d_offsets(), ptr<uint8_t>(keys->chars));
+                     ptr<const int32_t>(item), nkeys, shift, b.off, b.chars);
   CS_HIP(hipStreamSynchronize(s));
-  cat->keys = std::move(keys);
+  cat->keys = std::move(b.col);
   return cat.release();
 }
 

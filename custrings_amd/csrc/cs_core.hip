@@ -1206,8 +1206,7 @@ cs_column* concat_columns(const std::vector<const cs_column*>& cols, hipStream_t
     any_mask |= c->validity != nullptr;
   }
   if (rows == 0) return make_all_null(0, s);
-  auto out = std::make_unique<cs_column>();
-  out->rows = rows;
+  Built b(rows, any_mask ? Nulls::separate : Nulls::none, s);
   Buf lens = dev_alloc(sizeof(int32_t) * rows, s);
   int64_t base = 0;
   for (auto* c : cols) {
@@ -1216,20 +1215,17 @@ cs_column* concat_columns(const std::vector<const cs_column*>& cols, hipStream_t
                          ptr<int32_t>(lens) + base);
     base += c->rows;
   }
-  out->offsets = dev_alloc(sizeof(int64_t) * (rows + 1), s);
-  out->nbytes = offsets_from_lengths(ptr<int32_t>(lens), rows, ptr<int64_t>(out->offsets), s);
-  out->chars = dev_alloc((size_t)out->nbytes, s);
-  if (any_mask) out->validity = validity_from_lengths(ptr<int32_t>(lens), rows, s);
-  else out->null_count = 0;
+  b.scan(ptr<int32_t>(lens));
+  b.alloc_chars();
   base = 0;
   for (auto* c : cols) {
     if (c->rows)
       hipLaunchKernelGGL(k_gather_rows_at, dim3(blocks_for(c->rows)), dim3(kBlock), 0, s, view_of(c),
-                         out->d_offsets() + base, ptr<uint8_t>(out->chars));
+                         b.off + base, b.chars);
     base += c->rows;
   }
   CS_HIP(hipStreamSynchronize(s));
-  return out.release();
+  return b.col.release();
 }
 
 }  // namespace cs
@@ -1814,34 +1810,26 @@ int cs_records_from_columns(const cs_column* const* cols, int ncols, int ragged,
       CS_HIP(hipMemsetAsync(list->p, 0, sizeof(int64_t) * (rows + 1), s));
     }
     if (total >= (int64_t)1 << 31) fail(CS_ERR_RANGE, "records: more than 2^31 strings");
-    auto o = std::make_unique<cs_column>();
-    o->rows = total;
-    o->offsets = dev_alloc(sizeof(int64_t) * (total + 1), s);
-    if (total) {
-      Buf lens = dev_alloc(sizeof(int32_t) * total, s);
-      for (int k0 = 0; k0 < ncols; k0 += RecordCols::kMax) {
-        RecordCols rc{};
-        const int nb = batch(k0, rc);
-        hipLaunchKernelGGL(k_record_lengths, dim3(blocks_for(rows)), dim3(kBlock), 0, s, rc, k0, nb, rows, ptr<int64_t>(list), ptr<int32_t>(lens));
-      }
-      o->nbytes = offsets_from_lengths(ptr<int32_t>(lens), total, ptr<int64_t>(o->offsets), s);
-      o->chars = dev_alloc((size_t)o->nbytes, s);
-      o->validity = validity_from_lengths(ptr<int32_t>(lens), total, s);
-      for (int k0 = 0; k0 < ncols; k0 += RecordCols::kMax) {
-        RecordCols rc{};
-        const int nb = batch(k0, rc);
-        hipLaunchKernelGGL(k_record_copy, dim3(blocks_for(rows)), dim3(kBlock), 0, s, rc, k0, nb, rows, ptr<int64_t>(list), o->d_offsets(),
-                           ptr<uint8_t>(o->chars));
-      }
-      CS_HIP(hipGetLastError());
-    } else {
-      CS_HIP(hipMemsetAsync(o->offsets->p, 0, sizeof(int64_t), s));
-      o->chars = dev_alloc(0, s);
-      o->nbytes = 0;
+    Built b(total, total ? Nulls::separate : Nulls::none, s);
+    b.col->offsets = dev_alloc(sizeof(int64_t) * (total + 1), s);  // (before the lengths, as the pool has always seen them)
+    Buf lens;
+    if (total) lens = dev_alloc(sizeof(int32_t) * total, s);
+    for (int k0 = 0; total && k0 < ncols; k0 += RecordCols::kMax) {
+      RecordCols rc{};
+      const int nb = batch(k0, rc);
+      hipLaunchKernelGGL(k_record_lengths, dim3(blocks_for(rows)), dim3(kBlock), 0, s, rc, k0, nb, rows, ptr<int64_t>(list), ptr<int32_t>(lens));
     }
+    b.scan(ptr<int32_t>(lens));
+    b.alloc_chars();
+    for (int k0 = 0; total && k0 < ncols; k0 += RecordCols::kMax) {
+      RecordCols rc{};
+      const int nb = batch(k0, rc);
+      hipLaunchKernelGGL(k_record_copy, dim3(blocks_for(rows)), dim3(kBlock), 0, s, rc, k0, nb, rows, ptr<int64_t>(list), b.off, b.chars);
+    }
+    CS_HIP(hipGetLastError());
     CS_HIP(hipMemcpyAsync(list_offsets, list->p, sizeof(int64_t) * (rows + 1), on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
     CS_HIP(hipStreamSynchronize(s));
-    *out = o.release();
+    *out = b.col.release();
   });
 }
 

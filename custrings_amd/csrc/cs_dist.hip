@@ -437,11 +437,9 @@ cs_category* merge_partitioned(const Exchange& x, const cs_category* local, cons
     for (int r = 0; r < n; ++r) {
       part_at[r] = at;
       if (got_keys[r] == 0) continue;
-      auto c = std::make_unique<cs_column>();
-      c->rows = got_keys[r];
-      c->nbytes = got_bytes[r];
-      c->offsets = dev_alloc(sizeof(int64_t) * (size_t)(got_keys[r] + 1), s);
-      const int64_t total = offsets_from_lengths(ptr<const int32_t>(in_lens) + at, got_keys[r], ptr<int64_t>(c->offsets), s);
+      Built b(got_keys[r], Nulls::none, s);  // (its chars are the received bytes, wrapped: no alloc_chars)
+      std::unique_ptr<cs_column>& c = b.col;
+      const int64_t total = b.scan(ptr<const int32_t>(in_lens) + at);
       if (total != got_bytes[r]) fail(CS_ERR_INTERNAL, "category_build_distributed: a received part's lengths do not add up to its bytes");
       c->chars = dev_wrap(ptr<uint8_t>(in_chars) + cro[r], (size_t)got_bytes[r]);
       // (a null key travels as a key of no bytes at the head of its sender's slice for range 0 -- the sizes exchange said

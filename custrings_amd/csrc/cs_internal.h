@@ -285,14 +285,38 @@ cs_category* category_build(const cs_column* col, hipStream_t s);
 // cs_array.hip: rows of `col` at the given device positions; with `null_when_negative` a negative
 // position yields a null row instead of CS_ERR_RANGE
 cs_column* gather_rows(const cs_column* col, const int32_t* d_pos, int64_t n, hipStream_t s, bool null_when_negative = false);
-// finishes a column from per-row lengths (-1 = null): offsets, validity, an empty chars buffer of the
-// right size; the caller's copy kernel fills the chars, then prefer_offsets32 keeps the narrow offsets
+// The output column of an op that sizes its rows first (int32 lengths, negative = null row): the one host tail from
+// lengths to a column.  The constructor makes the column with its row count and nulls; scan() allocates the offsets
+// and scans the lengths into them (the total is the column's nbytes, the scan's metadata goes to the column; no rows:
+// one zero offset); alloc_chars() allocates the chars (no bytes: an empty buffer) and, for Nulls::separate, writes the
+// validity.  Between the two the caller may act on the total or read a flag of its size kernel.  The caller's write
+// kernel fills `chars` by `off`; prefer_offsets32 afterwards keeps the narrow offsets.
+enum class Nulls {
+  shared,    // the input's validity and null_count (null rows stay null; columns are immutable, so share)
+  none,      // no row can be null: null_count = 0
+  separate,  // validity from the negative lengths, by a kernel of its own once the chars are allocated
+  fused,     // validity from the negative lengths, written by the scan's own pass over them
+};
 struct Built {
   std::unique_ptr<cs_column> col;
-  const int64_t* off;
+  const int64_t* off = nullptr;  // col's int64 offsets (after scan)
+  uint8_t* chars = nullptr;      // col's chars (after alloc_chars)
+  Built(int64_t rows, Nulls nulls, hipStream_t s);
+  Built(const cs_column* like, hipStream_t s);  // like's rows, Nulls::shared with it
+  // `block_sums`: the per-256-row sums, when the caller's size kernel fused them
+  int64_t scan(const int32_t* lens, Buf block_sums = nullptr);
+  uint8_t* alloc_chars();
+
+ private:
+  Nulls nulls_;
+  hipStream_t s_;
+  const int32_t* lens_ = nullptr;
 };
+// scan and alloc_chars with nothing in between
 Built column_from_lengths(const int32_t* lens, int64_t rows, bool any_null_possible, hipStream_t s);
 void prefer_offsets32(cs_column* c, hipStream_t s);
+// hands a vector of columns to a C caller: a malloc'ed array of the released pointers and their count (cs_free frees it)
+void release_columns(std::vector<std::unique_ptr<cs_column>>& cols, cs_column*** out_cols, int* ncols_out);
 
 // profiling hooks (cs_prof_*): time a named kernel launch with HIP events
 struct ProfScope {

@@ -101,34 +101,37 @@ __global__ void k_row_write(ColView in, WriteFn f, const int64_t* __restrict__ o
   f(in.chars + b, (int)(in.offsets[r + 1] - b), r, out_chars + out_off[r]);
 }
 
+// the size pass and the scan of `b`'s offsets; the lengths and block sums stay the caller's until its write pass is launched
+struct RowSizes {
+  Buf lens, sums;
+};
+template <class SizeFn>
+RowSizes size_rows(const cs_column* in, SizeFn sf, hipStream_t s, const char* size_name, Built& b) {
+  const unsigned nb = blocks_for(in->rows);
+  RowSizes z{dev_alloc(sizeof(int32_t) * in->rows, s), dev_alloc(sizeof(int64_t) * nb, s)};
+  {
+    ProfScope ps(size_name, s);
+    hipLaunchKernelGGL(k_row_sizes<SizeFn>, dim3(nb), dim3(kBlock), 0, s, view_of(in), sf,
+                       ptr<int32_t>(z.lens), ptr<int64_t>(z.sums));
+  }
+  b.scan(ptr<int32_t>(z.lens), z.sums);
+  return z;
+}
+template <class WriteFn>
+void write_rows(const cs_column* in, WriteFn wf, hipStream_t s, const char* write_name, const Built& b) {
+  ProfScope ps(write_name, s);
+  hipLaunchKernelGGL(k_row_write<WriteFn>, dim3(blocks_for(in->rows)), dim3(kBlock), 0, s, view_of(in), wf, b.off, b.chars);
+}
+
 template <class SizeFn, class WriteFn>
 cs_column* two_pass(const cs_column* in, SizeFn sf, WriteFn wf, hipStream_t s, const char* size_name,
                     const char* write_name) {
   if (in->rows == 0) return make_all_null(0, s);
-  auto* out = new cs_column;
-  std::unique_ptr<cs_column> holder(out);
-  out->rows = in->rows;
-  out->validity = in->validity;  // null rows stay null; columns are immutable, so share
-  out->null_count = in->null_count;
-  unsigned nb = blocks_for(in->rows);
-  Buf lens = dev_alloc(sizeof(int32_t) * in->rows, s);
-  Buf sums = dev_alloc(sizeof(int64_t) * nb, s);
-  {
-    ProfScope ps(size_name, s);
-    hipLaunchKernelGGL(k_row_sizes<SizeFn>, dim3(nb), dim3(kBlock), 0, s, view_of(in), sf,
-                       ptr<int32_t>(lens), ptr<int64_t>(sums));
-  }
-  out->offsets = dev_alloc(sizeof(int64_t) * (in->rows + 1), s);
-  LenMeta meta;
-  out->nbytes = offsets_from_lengths(ptr<int32_t>(lens), in->rows, ptr<int64_t>(out->offsets), s, sums, &meta);
-  meta.give(out);
-  out->chars = dev_alloc((size_t)out->nbytes, s);
-  {
-    ProfScope ps(write_name, s);
-    hipLaunchKernelGGL(k_row_write<WriteFn>, dim3(nb), dim3(kBlock), 0, s, view_of(in), wf,
-                       out->d_offsets(), ptr<uint8_t>(out->chars));
-  }
-  return holder.release();
+  Built b(in, s);
+  const RowSizes z = size_rows(in, sf, s, size_name, b);
+  b.alloc_chars();
+  write_rows(in, wf, s, write_name, b);
+  return b.col.release();
 }
 
 // ---- functors ---------------------------------------------------------------------
@@ -477,39 +480,17 @@ int cs_strip(const cs_column* col, const char* to_strip, int side, cs_stream str
     CharSet set = make_charset(to_strip ? to_strip : " \n\t", set_more, s);
     // size pass + scan as for every row-wise op; the write pass runs on row tiles (cs_rows.hip)
     if (col->rows > 0 && !cs::cfg("CS_STRIP_ROWWISE")) {
-      auto o = std::make_unique<cs_column>();
-      o->rows = col->rows;
-      o->validity = col->validity;
-      o->null_count = col->null_count;
-      if (strip_single(col, set, side, s, o.get())) {  // one pass (cs_rows.hip: k_strip_stream)
-        *out = o.release();
+      Built b(col, s);
+      if (strip_single(col, set, side, s, b.col.get())) {  // one pass (cs_rows.hip: k_strip_stream)
+        *out = b.col.release();
         return;
       }
-      const unsigned nb = blocks_for(col->rows);
-      Buf lens = dev_alloc(sizeof(int32_t) * col->rows, s);
-      Buf sums = dev_alloc(sizeof(int64_t) * nb, s);
-      {
-        ProfScope ps("k_strip_size", s);
-        hipLaunchKernelGGL(k_row_sizes<StripSize>, dim3(nb), dim3(kBlock), 0, s, view_of(col), StripSize{set, side},
-                           ptr<int32_t>(lens), ptr<int64_t>(sums));
-      }
-      o->offsets = dev_alloc(sizeof(int64_t) * (col->rows + 1), s);
-      LenMeta meta;
-      o->nbytes = offsets_from_lengths(ptr<int32_t>(lens), col->rows, ptr<int64_t>(o->offsets), s, sums, &meta);
-      meta.give(o.get());
-      if (col->plain_bytes == 1) o->plain_bytes = 1;  // (rows cut at character boundaries of a plain column stay plain)
-      if (col->high_sample == 0) o->high_sample = 0;
-      o->chars = dev_alloc((size_t)o->nbytes, s);
-      if (strip_write_tiles(col, set, side, o->d_offsets(), ptr<uint8_t>(o->chars), s)) {
-        *out = o.release();
-        return;
-      }
-      {
-        ProfScope ps("k_strip_write", s);
-        hipLaunchKernelGGL(k_row_write<StripWrite>, dim3(nb), dim3(kBlock), 0, s, view_of(col), StripWrite{set, side},
-                           o->d_offsets(), ptr<uint8_t>(o->chars));
-      }
-      *out = o.release();
+      const RowSizes z = size_rows(col, StripSize{set, side}, s, "k_strip_size", b);
+      if (col->plain_bytes == 1) b.col->plain_bytes = 1;  // (rows cut at character boundaries of a plain column stay plain)
+      if (col->high_sample == 0) b.col->high_sample = 0;
+      b.alloc_chars();
+      if (!strip_write_tiles(col, set, side, b.off, b.chars, s)) write_rows(col, StripWrite{set, side}, s, "k_strip_write", b);
+      *out = b.col.release();
       return;
     }
     *out = two_pass(col, StripSize{set, side}, StripWrite{set, side}, S(stream), "k_strip_size", "k_strip_write");
@@ -866,11 +847,7 @@ static int split_impl(const cs_column* col, const char* delimiter, int maxsplit,
     if ((!a.reverse && (!delimiter || ascii_delim)) || reverse_fast) {
       std::vector<std::unique_ptr<cs_column>> fast;
       if (split_fast(col, reinterpret_cast<const unsigned char*>(delimiter), delimiter ? nd.n : 0, a.tokens, s, fast, reverse_fast)) {
-        cs_column** arr = (cs_column**)malloc(sizeof(cs_column*) * fast.size());
-        if (!arr) fail(CS_ERR_ALLOC, "host allocation failed");
-        for (size_t k = 0; k < fast.size(); ++k) arr[k] = fast[k].release();
-        *out_cols = arr;
-        *ncols_out = (int)fast.size();
+        release_columns(fast, out_cols, ncols_out);
         return;
       }
     }
@@ -929,11 +906,7 @@ static int split_impl(const cs_column* col, const char* delimiter, int maxsplit,
       }
       CS_HIP(hipStreamSynchronize(s));  // `outs` staging is on the host stack
     }
-    cs_column** arr = (cs_column**)malloc(sizeof(cs_column*) * cols.size());
-    if (!arr) fail(CS_ERR_ALLOC, "host allocation failed");
-    for (size_t k = 0; k < cols.size(); ++k) arr[k] = cols[k].release();
-    *out_cols = arr;
-    *ncols_out = (int)cols.size();
+    release_columns(cols, out_cols, ncols_out);
   });
 }
 
@@ -977,35 +950,24 @@ int cs_tokenize(const cs_column* col, const char* delimiter, cs_stream stream, c
     }
     Buf tok_base = dev_alloc(sizeof(int64_t) * (rows + 1), s);
     int64_t ntok = offsets_from_lengths(ptr<int32_t>(counts), rows, ptr<int64_t>(tok_base), s, sums);
-    auto* c = new cs_column;
-    std::unique_ptr<cs_column> holder(c);
-    c->rows = ntok;
-    c->null_count = 0;
-    c->offsets = dev_alloc(sizeof(int64_t) * (ntok + 1), s);
-    if (ntok == 0) {
-      CS_HIP(hipMemsetAsync(c->offsets->p, 0, sizeof(int64_t), s));
-      c->chars = dev_alloc(0, s);
-      *out = holder.release();
-      return;
-    }
-    Buf tok_lens = dev_alloc(sizeof(int32_t) * ntok, s);
-    {
+    Built b(ntok, Nulls::none, s);
+    b.col->offsets = dev_alloc(sizeof(int64_t) * (ntok + 1), s);  // (before the lengths, as the pool has always seen them)
+    Buf tok_lens;
+    if (ntok) {
+      tok_lens = dev_alloc(sizeof(int32_t) * ntok, s);
       ProfScope ps("k_tok_sizes", s);
       hipLaunchKernelGGL(k_tok_emit<0>, dim3(nb), dim3(kBlock), 0, s, view_of(col), a,
                          ptr<const int64_t>(tok_base), ptr<int32_t>(tok_lens), (const int64_t*)nullptr,
                          (uint8_t*)nullptr);
     }
-    LenMeta meta;
-    c->nbytes = offsets_from_lengths(ptr<int32_t>(tok_lens), ntok, ptr<int64_t>(c->offsets), s, nullptr, &meta);
-    meta.give(c);
-    c->chars = dev_alloc((size_t)c->nbytes, s);
-    {
+    b.scan(ptr<int32_t>(tok_lens));
+    b.alloc_chars();
+    if (ntok) {
       ProfScope ps("k_tok_write", s);
       hipLaunchKernelGGL(k_tok_emit<1>, dim3(nb), dim3(kBlock), 0, s, view_of(col), a,
-                         ptr<const int64_t>(tok_base), (int32_t*)nullptr, c->d_offsets(),
-                         ptr<uint8_t>(c->chars));
+                         ptr<const int64_t>(tok_base), (int32_t*)nullptr, b.off, b.chars);
     }
-    *out = holder.release();
+    *out = b.col.release();
   });
 }
 
@@ -1069,22 +1031,13 @@ int cs_ngrams(const cs_column* tokens, unsigned ngrams, const char* separator, c
       hipLaunchKernelGGL(k_ngram_sizes, dim3(blocks_for(ng)), dim3(kBlock), 0, s, view_of(tokens),
                          ptr<const int32_t>(kept), ng, (int)ngrams, sep.n, ptr<int32_t>(lens));
     }
-    auto* c = new cs_column;
-    std::unique_ptr<cs_column> holder(c);
-    c->rows = ng;
-    c->null_count = 0;
-    c->offsets = dev_alloc(sizeof(int64_t) * (ng + 1), s);
-    LenMeta meta;
-    c->nbytes = offsets_from_lengths(ptr<int32_t>(lens), ng, ptr<int64_t>(c->offsets), s, nullptr, &meta);
-    meta.give(c);
-    c->chars = dev_alloc((size_t)c->nbytes, s);
+    Built b = column_from_lengths(ptr<int32_t>(lens), ng, false, s);
     {
       ProfScope ps("k_ngram_write", s);
       hipLaunchKernelGGL(k_ngram_write, dim3(blocks_for(ng)), dim3(kBlock), 0, s, view_of(tokens),
-                         ptr<const int32_t>(kept), ng, (int)ngrams, sep.d(), sep.n, c->d_offsets(),
-                         ptr<uint8_t>(c->chars));
+                         ptr<const int32_t>(kept), ng, (int)ngrams, sep.d(), sep.n, b.off, b.chars);
     }
-    *out = holder.release();
+    *out = b.col.release();
   });
 }
 

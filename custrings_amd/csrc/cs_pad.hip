@@ -221,10 +221,8 @@ __global__ void __launch_bounds__(256) k_pad_write_tile(PadArgs a) {
 template <int OP>
 cs_column* run_pad_op(const cs_column* col, PadArgs a, hipStream_t s) {
   const int64_t rows = col->rows;
-  auto o = std::make_unique<cs_column>();
-  o->rows = rows;
-  o->validity = col->validity;  // null rows stay null; columns are immutable, so share
-  o->null_count = col->null_count;
+  Built b(col, s);
+  cs_column* const o = b.col.get();
   a.in = view_of(col);
   // the tile plan: R rows whose bytes fit the prefetch (a column with a few longer tiles still gets it: those tiles go from
   // memory); the staging buffers of four waves must fit the LDS
@@ -236,7 +234,7 @@ cs_column* run_pad_op(const cs_column* col, PadArgs a, hipStream_t s) {
   a.ntiles = t.ntiles;
   const unsigned row_grid = std::min(blocks_for(rows), 65536u);
   if (OP == cspad::OP_WRAP) {
-    col->share_extents_with(o.get());
+    col->share_extents_with(o);
     o->nbytes = col->nbytes;
     o->max_row = col->max_row;
     o->max_span64 = col->max_span64;
@@ -256,22 +254,18 @@ cs_column* run_pad_op(const cs_column* col, PadArgs a, hipStream_t s) {
         CS_HIP(hipGetLastError());
       }
     }
-    o->offsets = dev_alloc(sizeof(int64_t) * (size_t)(rows + 1), s);
-    LenMeta meta;
-    o->nbytes = offsets_from_lengths(ptr<int32_t>(lens), rows, ptr<int64_t>(o->offsets), s, nullptr, &meta);
-    meta.give(o.get());
+    b.scan(ptr<int32_t>(lens));
     unsigned over = 0;
     CS_HIP(hipMemcpy(&over, flag->p, sizeof(unsigned), hipMemcpyDeviceToHost));
     if (over) fail(CS_ERR_RANGE, "nvstrings: an output row would reach 2^31 bytes");
   }
-  o->chars = dev_alloc((size_t)o->nbytes, s);
-  a.out_off = o->d_offsets();
-  a.out_chars = ptr<uint8_t>(o->chars);
+  a.out_chars = b.alloc_chars();
+  a.out_off = o->d_offsets();  // (wrap: the input's extents)
   {
     ProfScope ps("k_pad_write", s);
     if (tile) {
       // the out-tile: the widest 64-row span of the output (an R-row tile lies inside one), capped
-      const int64_t span = o->max_span64 >= 0 ? o->max_span64 : max_span64(o.get(), s);
+      const int64_t span = o->max_span64 >= 0 ? o->max_span64 : max_span64(o, s);
       a.out_cap = (int)((std::min<int64_t>(span, kOutCapMax) + 16 + 15) & ~(int64_t)15);
       launch_resident(&k_pad_write_tile<OP>, t.lds + (size_t)a.out_cap * 4, t.grid, s, a);
     } else {
@@ -280,7 +274,7 @@ cs_column* run_pad_op(const cs_column* col, PadArgs a, hipStream_t s) {
     }
   }
   note_route(tile ? "tile" : "rows");
-  return o.release();
+  return b.col.release();
 }
 
 cs_column* run_pad(const cs_column* col, const Params& P, const int32_t* starts, const int32_t* stops, hipStream_t s) {

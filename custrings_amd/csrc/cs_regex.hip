@@ -3372,11 +3372,8 @@ int cs_replace_re(const cs_column* col, const cs_regex* cre, const char* repl, i
       }
     }
     RowSrc src{view_of(col), d_unicode_flags(), col->nbytes + (col->chars && col->chars->capacity ? 64 : 0)};
-    auto* o = new cs_column;
-    std::unique_ptr<cs_column> holder(o);
-    o->rows = col->rows;
-    o->validity = col->validity;
-    o->null_count = col->null_count;
+    Built b(col, s);  // (the single pass below fills it itself: it allocates before it knows the sizes)
+    cs_column* const o = b.col.get();
     const int minlen = (tdfa || wide) ? re->tdfa[13] : 0;
     // Single pass when a match cannot be empty: a match is at least `minlen` bytes, so a row grows
     // by at most (rb - minlen) bytes per match; rb <= minlen means "never grows" and the rows are
@@ -3744,7 +3741,7 @@ int cs_replace_re(const cs_column* col, const cs_regex* cre, const char* repl, i
             for (int i = 0; i < rb; ++i) ascii = ascii && (unsigned char)repl[i] < 0x80 && repl[i] != 0;
             if (ascii) o->high_sample = 0;
           }
-          *out = holder.release();
+          *out = b.col.release();
           return 0;
         }
         return err;
@@ -3819,35 +3816,32 @@ int cs_replace_re(const cs_column* col, const cs_regex* cre, const char* repl, i
                            maxrepl, ptr<int32_t>(lens));
     }
     CS_HIP(hipGetLastError());
-    o->offsets = dev_alloc(sizeof(int64_t) * (col->rows + 1), s);
-    LenMeta meta;
-    o->nbytes = offsets_from_lengths(ptr<int32_t>(lens), col->rows, ptr<int64_t>(o->offsets), s, nullptr, &meta);
-    meta.give(o);
-    o->chars = dev_alloc((size_t)o->nbytes, s);
+    b.scan(ptr<int32_t>(lens));
+    b.alloc_chars();
     {
       ProfScope ps("k_replace_re_write", s);
       if (wide && tp.d.in_lds)
         hipLaunchKernelGGL((k_tdfa_replace_write<true, true>), dim3(tp.grid), dim3(256), tp.lds_bytes, s, src, tp.d,
-                           ptr<const uint8_t>(d_repl), rb, maxrepl, o->d_offsets(), ptr<uint8_t>(o->chars));
+                           ptr<const uint8_t>(d_repl), rb, maxrepl, b.off, b.chars);
       else if (wide)
         hipLaunchKernelGGL((k_tdfa_replace_write<false, true>), dim3(tp.grid), dim3(256), 0, s, src, tp.d,
-                           ptr<const uint8_t>(d_repl), rb, maxrepl, o->d_offsets(), ptr<uint8_t>(o->chars));
+                           ptr<const uint8_t>(d_repl), rb, maxrepl, b.off, b.chars);
       else if (tdfa && tp.d.in_lds)
         hipLaunchKernelGGL(k_tdfa_replace_write<true>, dim3(tp.grid), dim3(256), tp.lds_bytes, s, src, tp.d,
-                           ptr<const uint8_t>(d_repl), rb, maxrepl, o->d_offsets(), ptr<uint8_t>(o->chars));
+                           ptr<const uint8_t>(d_repl), rb, maxrepl, b.off, b.chars);
       else if (tdfa)
         hipLaunchKernelGGL(k_tdfa_replace_write<false>, dim3(tp.grid), dim3(256), 0, s, src, tp.d,
-                           ptr<const uint8_t>(d_repl), rb, maxrepl, o->d_offsets(), ptr<uint8_t>(o->chars));
+                           ptr<const uint8_t>(d_repl), rb, maxrepl, b.off, b.chars);
       else if (pl.small)
         hipLaunchKernelGGL((k_replace_re_write<true>), dim3(pl.grid), dim3(pl.threads), pl.lds_bytes, s, src, pl.d,
-                           ptr<const uint8_t>(d_repl), rb, maxrepl, o->d_offsets(), ptr<uint8_t>(o->chars));
+                           ptr<const uint8_t>(d_repl), rb, maxrepl, b.off, b.chars);
       else
         hipLaunchKernelGGL((k_replace_re_write<false>), dim3(pl.grid), dim3(pl.threads), pl.lds_bytes, s, src, pl.d,
-                           ptr<const uint8_t>(d_repl), rb, maxrepl, o->d_offsets(), ptr<uint8_t>(o->chars));
+                           ptr<const uint8_t>(d_repl), rb, maxrepl, b.off, b.chars);
     }
     CS_HIP(hipGetLastError());
     CS_HIP(hipStreamSynchronize(s));  // d_repl / arena lifetime
-    *out = holder.release();
+    *out = b.col.release();
   });
 }
 
@@ -4053,35 +4047,21 @@ int cs_extract(const cs_column* col, const cs_regex* cre, cs_stream stream, cs_c
     std::vector<std::unique_ptr<cs_column>> cols;
     if (packed) {
       columns_from_packed_spans(col, groups, ptr<const uint32_t>(spans), ptr<const int32_t>(tile_tot), choose_tile(col, s).cap, s, cols);
-      cs_column** arr = (cs_column**)malloc(sizeof(cs_column*) * groups);
-      if (!arr) fail(CS_ERR_ALLOC, "host allocation failed");
-      for (int g = 0; g < groups; ++g) arr[g] = cols[g].release();
-      *out_cols = arr;
-      *ncols_out = groups;
+      release_columns(cols, out_cols, ncols_out);
       return;
     }
     ExtractOut eo{};
     for (int g = 0; g < groups; ++g) {
-      auto o = std::make_unique<cs_column>();
-      o->rows = rows;
-      const int32_t* gl = ptr<int32_t>(lens) + (size_t)g * rows;
-      o->offsets = dev_alloc(sizeof(int64_t) * (rows + 1), s);
-      LenMeta meta;
-      o->nbytes = offsets_and_validity_from_lengths(gl, rows, ptr<int64_t>(o->offsets), &o->validity, s, &meta);
-      meta.give(o.get());
-      o->chars = dev_alloc((size_t)o->nbytes, s);
-      eo.off[g] = o->d_offsets();
-      eo.chars[g] = ptr<uint8_t>(o->chars);
-      cols.push_back(std::move(o));
+      Built b(rows, Nulls::fused, s);
+      b.scan(ptr<int32_t>(lens) + (size_t)g * rows);
+      eo.off[g] = b.off;
+      eo.chars[g] = b.alloc_chars();
+      cols.push_back(std::move(b.col));
     }
     write_spans(col, groups, ptr<int32_t>(begins), ptr<int32_t>(lens), eo, s);
     CS_HIP(hipGetLastError());
     CS_HIP(hipStreamSynchronize(s));  // arena / span buffers
-    cs_column** arr = (cs_column**)malloc(sizeof(cs_column*) * groups);
-    if (!arr) fail(CS_ERR_ALLOC, "host allocation failed");
-    for (int g = 0; g < groups; ++g) arr[g] = cols[g].release();
-    *out_cols = arr;
-    *ncols_out = groups;
+    release_columns(cols, out_cols, ncols_out);
   });
 }
 
@@ -4097,13 +4077,7 @@ int cs_findall(const cs_column* col, const cs_regex* cre, cs_stream stream, cs_c
     *ncols_out = 0;
     const int64_t rows = col->rows;
     if (rows == 0) return;
-    auto finish = [&](std::vector<std::unique_ptr<cs_column>>& cols) {
-      cs_column** arr = (cs_column**)malloc(sizeof(cs_column*) * cols.size());
-      if (!arr) fail(CS_ERR_ALLOC, "host allocation failed");
-      for (size_t k = 0; k < cols.size(); ++k) arr[k] = cols[k].release();
-      *out_cols = arr;
-      *ncols_out = (int)cols.size();
-    };
+    auto finish = [&](std::vector<std::unique_ptr<cs_column>>& cols) { release_columns(cols, out_cols, ncols_out); };
     std::vector<std::unique_ptr<cs_column>> cols;
     Buf dmax = dev_alloc(8, s);
     int* hmax = (int*)pinned_scratch(8);
@@ -4230,17 +4204,11 @@ int cs_findall(const cs_column* col, const cs_regex* cre, cs_stream stream, cs_c
       const int nk = std::min(kMaxGroups, ncols - k0);
       ExtractOut eo{};
       for (int k = 0; k < nk; ++k) {
-        auto o = std::make_unique<cs_column>();
-        o->rows = rows;
-        const int32_t* gl = ptr<int32_t>(lens) + (size_t)(k0 + k) * rows;
-        o->offsets = dev_alloc(sizeof(int64_t) * (rows + 1), s);
-        LenMeta meta;
-        o->nbytes = offsets_and_validity_from_lengths(gl, rows, ptr<int64_t>(o->offsets), &o->validity, s, &meta);
-        meta.give(o.get());
-        o->chars = dev_alloc((size_t)o->nbytes, s);
-        eo.off[k] = o->d_offsets();
-        eo.chars[k] = ptr<uint8_t>(o->chars);
-        cols.push_back(std::move(o));
+        Built b(rows, Nulls::fused, s);
+        b.scan(ptr<int32_t>(lens) + (size_t)(k0 + k) * rows);
+        eo.off[k] = b.off;
+        eo.chars[k] = b.alloc_chars();
+        cols.push_back(std::move(b.col));
       }
       write_spans(col, nk, ptr<int32_t>(begins) + (size_t)k0 * rows, ptr<int32_t>(lens) + (size_t)k0 * rows, eo, s);
     }
@@ -4385,10 +4353,7 @@ int cs_replace_with_backrefs(const cs_column* col, const cs_regex* cre, const ch
                         : (lng ? &k_tdfa_scan_stream<5, true, true> : &k_tdfa_scan_stream<5, true, false>);
       launch_resident(kern, slds, (sa.nsub + 3) / 4, s, sa);
     };
-    auto o = std::make_unique<cs_column>();
-    o->rows = rows;
-    o->validity = col->validity;
-    o->null_count = col->null_count;
+    Built b(col, s);
     Buf lens = dev_alloc(sizeof(int32_t) * rows, s);
     {
       ProfScope ps("k_backrefs_size", s);
@@ -4399,23 +4364,20 @@ int cs_replace_with_backrefs(const cs_column* col, const cs_regex* cre, const ch
         launch(false, ptr<int32_t>(lens), nullptr, nullptr);
       }
     }
-    o->offsets = dev_alloc(sizeof(int64_t) * (rows + 1), s);
-    LenMeta meta;
-    o->nbytes = offsets_from_lengths(ptr<int32_t>(lens), rows, ptr<int64_t>(o->offsets), s, nullptr, &meta);
-    meta.give(o.get());
-    o->chars = dev_alloc((size_t)o->nbytes, s);
+    b.scan(ptr<int32_t>(lens));
+    b.alloc_chars();
     {
       ProfScope ps("k_backrefs_write", s);
       if (stream) {
-        sa.out_off = o->d_offsets();
-        sa.out_chars = ptr<uint8_t>(o->chars);
+        sa.out_off = b.off;
+        sa.out_chars = b.chars;
         launch_stream(true);
       } else {
-        launch(true, nullptr, o->d_offsets(), ptr<uint8_t>(o->chars));
+        launch(true, nullptr, b.off, b.chars);
       }
     }
     CS_HIP(hipStreamSynchronize(s));
-    *out = o.release();
+    *out = b.col.release();
   });
 }
 
@@ -4477,24 +4439,18 @@ int cs_replace_re_multi(const cs_column* col, const cs_regex* const* res, int np
     if (all_dfa) hipLaunchKernelGGL((k_multi_replace<true, false>), dim3(grid), dim3(256), 0, s, a, ptr<int32_t>(lens), (const int64_t*)nullptr, (uint8_t*)nullptr, ptr<unsigned>(bad));
     else hipLaunchKernelGGL((k_multi_replace<false, false>), dim3(grid), dim3(256), 0, s, a, ptr<int32_t>(lens), (const int64_t*)nullptr, (uint8_t*)nullptr, ptr<unsigned>(bad));
     CS_HIP(hipGetLastError());
-    auto o = std::make_unique<cs_column>();
-    o->rows = rows;
-    o->validity = col->validity;
-    o->null_count = col->null_count;
-    o->offsets = dev_alloc(sizeof(int64_t) * (rows + 1), s);
-    LenMeta meta;
-    o->nbytes = offsets_from_lengths(ptr<int32_t>(lens), rows, ptr<int64_t>(o->offsets), s, nullptr, &meta);
-    meta.give(o.get());
+    Built b(col, s);
+    b.scan(ptr<int32_t>(lens));
     unsigned* hb = (unsigned*)pinned_scratch(sizeof(unsigned));
     CS_HIP(hipMemcpyAsync(hb, bad->p, sizeof(unsigned), hipMemcpyDeviceToHost, s));
     CS_HIP(hipStreamSynchronize(s));
     if (*hb) fail(CS_ERR_INVALID_ARG, "replace_re: a pattern matched the empty string");
-    o->chars = dev_alloc((size_t)o->nbytes, s);
-    if (all_dfa) hipLaunchKernelGGL((k_multi_replace<true, true>), dim3(grid), dim3(256), 0, s, a, (int32_t*)nullptr, o->d_offsets(), ptr<uint8_t>(o->chars), ptr<unsigned>(bad));
-    else hipLaunchKernelGGL((k_multi_replace<false, true>), dim3(grid), dim3(256), 0, s, a, (int32_t*)nullptr, o->d_offsets(), ptr<uint8_t>(o->chars), ptr<unsigned>(bad));
+    b.alloc_chars();
+    if (all_dfa) hipLaunchKernelGGL((k_multi_replace<true, true>), dim3(grid), dim3(256), 0, s, a, (int32_t*)nullptr, b.off, b.chars, ptr<unsigned>(bad));
+    else hipLaunchKernelGGL((k_multi_replace<false, true>), dim3(grid), dim3(256), 0, s, a, (int32_t*)nullptr, b.off, b.chars, ptr<unsigned>(bad));
     CS_HIP(hipGetLastError());
     CS_HIP(hipStreamSynchronize(s));
-    *out = o.release();
+    *out = b.col.release();
   });
 }
 

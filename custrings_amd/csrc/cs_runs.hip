@@ -366,23 +366,16 @@ bool replace_class_runs(const cs_column* col, const int32_t* d_bits, const std::
   a.cap_out = (most + 32 + 15) & ~15;
   const size_t lds1 = 512 + (kRunsWave0 + (size_t)a.cap_out) * 4;
   if (lds1 > 150 * 1024) return false;
-  auto o = std::make_unique<cs_column>();
-  o->rows = rows;
-  o->validity = col->validity;  // null rows stay null; columns are immutable, so share
-  o->null_count = col->null_count;
-  o->offsets = dev_alloc(sizeof(int64_t) * (size_t)(rows + 1), s);
-  LenMeta meta;
-  o->nbytes = offsets_from_lengths(ptr<int32_t>(lens), rows, ptr<int64_t>(o->offsets), s, nullptr, &meta);
-  meta.give(o.get());
-  o->chars = dev_alloc((size_t)o->nbytes, s);
-  a.out_off = o->d_offsets();
-  a.out_chars = ptr<uint8_t>(o->chars);
+  Built b(col, s);
+  b.scan(ptr<int32_t>(lens));
+  a.out_chars = b.alloc_chars();
+  a.out_off = b.off;
   {
     ProfScope ps("k_runs_write", s);
     launch_resident(&k_runs_tile<1>, lds1, (a.ntiles + 3) / 4, s, a);
   }
   CS_HIP(hipStreamSynchronize(s));
-  *out = o.release();
+  *out = b.col.release();
   return true;
 }
 

@@ -39,23 +39,17 @@ extern "C" int cs_synth_column(int kind, int64_t first_row, int64_t rows, uint64
       *out = make_all_null(0, s);
       return;
     }
-    auto c = std::make_unique<cs_column>();
-    c->rows = rows;
+    Built b(rows, kind != 3 ? Nulls::separate : Nulls::none, s);
     unsigned nb = blocks_for(rows);
     Buf lens = dev_alloc(sizeof(int32_t) * rows, s);
     Buf sums = dev_alloc(sizeof(int64_t) * nb, s);
     hipLaunchKernelGGL(k_synth_sizes, dim3(nb), dim3(kBlock), 0, s, kind, first_row, rows, seed, param,
                        ptr<int32_t>(lens), ptr<int64_t>(sums));
-    c->offsets = dev_alloc(sizeof(int64_t) * (rows + 1), s);
-    LenMeta meta;  // (a generated column is sized at ingest like any other: NVStringsImpl.cu:399-444)
-    c->nbytes = offsets_from_lengths(ptr<int32_t>(lens), rows, ptr<int64_t>(c->offsets), s, sums, &meta);
-    meta.give(c.get());
-    c->chars = dev_alloc((size_t)c->nbytes, s);
-    if (kind != 3) c->validity = validity_from_lengths(ptr<int32_t>(lens), rows, s);
-    else c->null_count = 0;
+    b.scan(ptr<int32_t>(lens), sums);  // (a generated column is sized at ingest like any other: NVStringsImpl.cu:399-444)
+    b.alloc_chars();
     hipLaunchKernelGGL(k_synth_write, dim3(nb), dim3(kBlock), 0, s, kind, first_row, rows, seed, param,
-                       ptr<const int32_t>(lens), c->d_offsets(), ptr<uint8_t>(c->chars));
+                       ptr<const int32_t>(lens), b.off, b.chars);
     CS_HIP(hipStreamSynchronize(s));
-    *out = c.release();
+    *out = b.col.release();
   });
 }
