@@ -102,7 +102,7 @@ bool run_case_tiles(const cs_column* col, bool ascii_ok, unsigned bit, hipStream
   o->null_count = col->null_count;
   o->max_span64 = col->max_span64;
   o->max_row = col->max_row;
-  col->share_extents_with(o);
+  col->share_extents_with(o, s);
   o->validity = col->validity;
   o->chars = chars;
   *out = o;

@@ -284,7 +284,18 @@ Buf dev_wrap(const void* p, size_t bytes) {
   b->p = const_cast<void*>(p);
   b->bytes = bytes;
   b->capacity = 0;
+  b->borrowed = true;
   return b;
+}
+
+Buf dev_owned(const Buf& b, hipStream_t s) {
+  if (!b || !b->borrowed) return b;
+  Buf own = dev_alloc(b->bytes, s);
+  if (b->bytes) {
+    CS_HIP(hipMemcpyAsync(own->p, b->p, b->bytes, hipMemcpyDeviceToDevice, s));
+    CS_HIP(hipStreamSynchronize(s));
+  }
+  return own;
 }
 
 void* pinned_scratch(size_t bytes) {
@@ -998,10 +1009,21 @@ const int64_t* cs_column::d_offsets() const {
   }
   return cs::ptr<const int64_t>(offsets);
 }
-void cs_column::share_extents_with(cs_column* o) const {
+void cs_column::share_extents_with(cs_column* o, hipStream_t s) const {
   std::lock_guard<std::mutex> lk(g_widen_mu);
-  o->offsets = offsets;
-  o->offsets32 = offsets32;
+  o->offsets = cs::dev_owned(offsets, s);
+  o->offsets32 = cs::dev_owned(offsets32, s);
+}
+cs_column* cs::share_column(const cs_column* in, hipStream_t s) {
+  auto o = std::make_unique<cs_column>(*in);
+  in->share_extents_with(o.get(), s);
+  if (in->chars && in->chars->borrowed) {
+    o->chars = cs::dev_owned(in->chars, s);
+    o->virt = nullptr;  // (views over the input's chars: built again on first use)
+    o->virt_state = 0;
+    o->odd = nullptr;
+  }
+  return o.release();
 }
 namespace cs {
 // a null row contributes no bytes: clamp its extent to zero while copying

@@ -68,11 +68,16 @@ struct DevBuf {
   size_t capacity = 0;  // bytes actually held (0 for wrapped buffers)
   hipStream_t stream = nullptr;
   bool ipc_mapped = false;  // opened with hipIpcOpenMemHandle: closed, not freed (cs_column_ipc_import)
+  bool borrowed = false;    // dev_wrap: memory this Buf does not keep alive (a zero-copy ingest's chars and offsets)
   ~DevBuf();
 };
 using Buf = std::shared_ptr<DevBuf>;
 Buf dev_alloc(size_t bytes, hipStream_t stream);
 Buf dev_wrap(const void* p, size_t bytes);  // caller-owned, never freed
+// What an output column may keep of an input's buffer: the Buf itself, or -- when it is borrowed -- a pool copy of its
+// bytes (made on `s` and waited for: the caller may take its memory back once the op returns).  Owned and IPC-mapped
+// buffers stay alive through the Buf and are shared as they are.
+Buf dev_owned(const Buf& b, hipStream_t s);
 template <class T>
 T* ptr(const Buf& b) {
   return b ? static_cast<T*>(b->p) : nullptr;
@@ -119,8 +124,8 @@ struct cs_column {
   const int64_t* d_offsets() const;
   const int32_t* d_offsets32() const { return cs::ptr<const int32_t>(offsets32); }
   const uint8_t* d_validity() const { return cs::ptr<const uint8_t>(validity); }
-  // the other column gets the same (immutable) extents
-  void share_extents_with(cs_column* o) const;
+  // the other column gets the same (immutable) extents (copies of them where they are borrowed: dev_owned)
+  void share_extents_with(cs_column* o, hipStream_t s) const;
 };
 
 // ---- the category: sorted unique keys + one int32 code per row (-1 / key 0 conventions: cs_category.hip)
@@ -145,6 +150,9 @@ inline hipStream_t S(cs_stream s) { return static_cast<hipStream_t>(s); }
 inline unsigned blocks_for(int64_t rows) { return (unsigned)((rows + 255) / 256); }
 inline size_t validity_bytes(int64_t rows) { return (size_t)((rows + 63) / 64) * 8; }
 
+// A second handle on the column's (immutable) buffers: the result of an op that changes nothing.  Borrowed buffers are
+// copied (dev_owned), so that no column an op returns refers to memory the library does not own.
+cs_column* share_column(const cs_column* in, hipStream_t s);
 // Empty column with `rows` rows, all null (NVStrings(count)) or zero rows.
 cs_column* make_all_null(int64_t rows, hipStream_t s);
 

@@ -406,8 +406,6 @@ __global__ void k_join_write(ColView in, const uint8_t* __restrict__ sep, int se
     for (int i = 0; i < sepn; ++i) *o++ = sep[i];
 }
 
-cs_column* share(const cs_column* in) { return new cs_column(*in); }
-
 template <class T>
 T read_back(const Buf& b, hipStream_t s) {
   T* host = (T*)pinned_scratch(sizeof(T));
@@ -982,7 +980,7 @@ int cs_ngrams(const cs_column* tokens, unsigned ngrams, const char* separator, c
     if (!separator) separator = "";
     const int64_t rows = tokens->rows;
     if (rows == 0) {
-      *out = share(tokens);
+      *out = share_column(tokens, s);
       return;
     }
     // tile kernel with closed-form offsets when no row is dropped (cs_ngram.hip)
@@ -1018,7 +1016,7 @@ int cs_ngrams(const cs_column* tokens, unsigned ngrams, const char* separator, c
       return;
     }
     if (ngrams == 1) {
-      *out = share(tokens);
+      *out = share_column(tokens, s);
       return;
     }
     Buf kept = dev_alloc(sizeof(int32_t) * count, s);

@@ -234,7 +234,7 @@ cs_column* run_pad_op(const cs_column* col, PadArgs a, hipStream_t s) {
   a.ntiles = t.ntiles;
   const unsigned row_grid = std::min(blocks_for(rows), 65536u);
   if (OP == cspad::OP_WRAP) {
-    col->share_extents_with(o);
+    col->share_extents_with(o, s);
     o->nbytes = col->nbytes;
     o->max_row = col->max_row;
     o->max_span64 = col->max_span64;

@@ -246,7 +246,7 @@ int cs_replace_tokens(const cs_column* col, const cs_column* targets, const cs_c
     hipStream_t s = S(stream);
     const int64_t rows = col->rows;
     if (rows == 0 || targets->rows == 0) {  // tokens.cu:567-568: a copy
-      *out = new cs_column(*col);
+      *out = share_column(col, s);
       return;
     }
     if (repls->rows == 0) fail(CS_ERR_INVALID_ARG, "replace-tokens: no replacement given");
@@ -277,7 +277,7 @@ int cs_normalize_spaces(const cs_column* col, cs_stream stream, cs_column** out)
     hipStream_t s = S(stream);
     const int64_t rows = col->rows;
     if (rows == 0) {
-      *out = new cs_column(*col);
+      *out = share_column(col, s);
       return;
     }
     Buf set_more;
