@@ -170,6 +170,11 @@ _PROTOS = {
     "cs_swapcase": (i32, [vp, vp, P(vp)]),
     "cs_capitalize": (i32, [vp, vp, P(vp)]),
     "cs_title": (i32, [vp, vp, P(vp)]),
+    "cs_url_encode": (i32, [vp, vp, P(vp)]),
+    "cs_url_decode": (i32, [vp, vp, P(vp)]),
+    "cs_translate": (i32, [vp, vp, vp, i32, vp, P(vp)]),
+    "cs_fillna": (i32, [vp, cp, vp, P(vp)]),
+    "cs_fillna_column": (i32, [vp, vp, vp, P(vp)]),
     "cs_replace_re": (i32, [vp, vp, cp, i32, vp, P(vp)]),
     "cs_replace_with_backrefs": (i32, [vp, vp, cp, vp, P(vp)]),
     "cs_extract": (i32, [vp, vp, vp, P(P(vp)), P(i32)]),

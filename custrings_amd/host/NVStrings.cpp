@@ -621,3 +621,17 @@ unsigned int NVStrings::is_empty(bool* results, bool devmem) { return chartype(m
 NVStrings* NVStrings::swapcase() { return made([&](cs_column** c) { return cs_swapcase(m_col, nullptr, c); }); }
 NVStrings* NVStrings::capitalize() { return made([&](cs_column** c) { return cs_capitalize(m_col, nullptr, c); }); }
 NVStrings* NVStrings::title() { return made([&](cs_column** c) { return cs_title(m_col, nullptr, c); }); }
+
+// ---- the URL codec, translate and fillna (urlencode.cu, modify.cu:302-489) ---------------------------------------------
+NVStrings* NVStrings::translate(std::pair<unsigned, unsigned>* table, unsigned int count) {
+  std::vector<uint32_t> from(count), to(count);
+  for (unsigned int i = 0; i < count; ++i) {
+    from[i] = table[i].first;
+    to[i] = table[i].second;
+  }
+  return made([&](cs_column** c) { return cs_translate(m_col, from.data(), to.data(), (int)count, nullptr, c); });
+}
+NVStrings* NVStrings::fillna(const char* str) { return made([&](cs_column** c) { return cs_fillna(m_col, str, nullptr, c); }); }
+NVStrings* NVStrings::fillna(NVStrings& strs) { return made([&](cs_column** c) { return cs_fillna_column(m_col, strs.m_col, nullptr, c); }); }
+NVStrings* NVStrings::url_encode() { return made([&](cs_column** c) { return cs_url_encode(m_col, nullptr, c); }); }
+NVStrings* NVStrings::url_decode() { return made([&](cs_column** c) { return cs_url_decode(m_col, nullptr, c); }); }

@@ -825,6 +825,140 @@ CASE_FN(n_swapcase, swapcase)
 CASE_FN(n_capitalize, capitalize)
 CASE_FN(n_title, title)
 
+// ---- index / rindex, the URL codec, translate, fillna (pystrings.cpp:2015-2050, 2426-2530, 3044-3104, 3834-3856) ------------
+// find / rfind that raise on a miss: (self, str, start, end|None, devptr).  With a device address the results are written
+// there either way and a miss raises "not found in N elements" (null rows count as found, as cs_find has it); the host
+// list has None for a null row and raises at the first -1.
+template <class Find>
+static PyObject* index_results(NVStrings* s, const char* name, const char* str, int* devptr, Find&& find) {
+  const unsigned int count = s->size();
+  if (devptr) {
+    unsigned int found = 0;
+    if (!guarded([&] { found = find(devptr, true); })) return nullptr;
+    if (found != count) {
+      PyErr_Format(PyExc_ValueError, "nvstrings.%s: [%s] not found in %d elements", name, str ? str : "", (int)(count - found));
+      return nullptr;
+    }
+    return PyLong_FromVoidPtr(devptr);
+  }
+  if (count == 0) return PyList_New(0);
+  std::vector<int> host(count);
+  if (!guarded([&] { find(host.data(), false); })) return nullptr;
+  for (unsigned int i = 0; i < count; ++i)
+    if (host[i] == -1) {
+      PyErr_Format(PyExc_ValueError, "nvstrings.%s: [%s] not found in element %d", name, str ? str : "", (int)i);
+      return nullptr;
+    }
+  PyObject* ret = PyList_New(count);
+  for (unsigned int i = 0; i < count; ++i) {
+    if (host[i] < -1) {
+      Py_INCREF(Py_None);
+      PyList_SetItem(ret, i, Py_None);
+    } else {
+      PyList_SetItem(ret, i, PyLong_FromLong((long)host[i]));
+    }
+  }
+  return ret;
+}
+static PyObject* n_index(PyObject*, PyObject* args) {
+  NVStrings* s = SELF(args);
+  const char* str = str_arg(args, 1);
+  const int start = (int)int_arg(args, 2, 0), end = (int)int_arg(args, 3, -1);
+  return index_results(s, "index", str, ptr_arg<int>(args, 4), [&](int* out, bool dev) { return s->find(str, start, end, out, dev); });
+}
+static PyObject* n_rindex(PyObject*, PyObject* args) {
+  NVStrings* s = SELF(args);
+  const char* str = str_arg(args, 1);
+  const int start = (int)int_arg(args, 2, 0), end = (int)int_arg(args, 3, -1);
+  return index_results(s, "rindex", str, ptr_arg<int>(args, 4), [&](int* out, bool dev) { return s->rfind(str, start, end, out, dev); });
+}
+CASE_FN(n_url_encode, url_encode)
+CASE_FN(n_url_decode, url_decode)
+// one side of a translate pair: an ordinal, a str (its first character) or, for a target, None (0: drop the character)
+static bool code_point(PyObject* o, bool none_ok, unsigned* out) {
+  if (o == Py_None && none_ok) {
+    *out = 0;
+    return true;
+  }
+  if (PyUnicode_Check(o) && PyUnicode_GetLength(o) >= 1) {
+    *out = (unsigned)PyUnicode_ReadChar(o, 0);
+    return true;
+  }
+  if (PyLong_Check(o)) {
+    const unsigned long v = PyLong_AsUnsignedLong(o);
+    if (PyErr_Occurred() || v > 0xFFFFFFFFul) {
+      PyErr_Clear();
+      return false;
+    }
+    *out = (unsigned)v;
+    return true;
+  }
+  return false;
+}
+static PyObject* n_translate(PyObject*, PyObject* args) {  // (self, table): a dict of ordinal -> ordinal | None, or a list of [char, char | None]
+  NVStrings* s = SELF(args);
+  PyObject* t = arg(args, 1);
+  std::vector<std::pair<unsigned, unsigned>> table;
+  bool ok = true;
+  if (PyList_Check(t)) {
+    for (Py_ssize_t i = 0; ok && i < PyList_Size(t); ++i) {
+      PyObject* e = PyList_GetItem(t, i);
+      const bool seq = PyList_Check(e) || PyTuple_Check(e);
+      std::pair<unsigned, unsigned> p;
+      ok = seq && PySequence_Size(e) == 2;
+      if (ok) {
+        PyObject *k = PySequence_GetItem(e, 0), *v = PySequence_GetItem(e, 1);
+        ok = code_point(k, false, &p.first) && code_point(v, true, &p.second);
+        Py_XDECREF(k);
+        Py_XDECREF(v);
+      }
+      table.push_back(p);
+    }
+    if (!ok) {
+      PyErr_SetString(PyExc_ValueError, "nvstrings.translate: invalid map entry");
+      return nullptr;
+    }
+  } else if (PyDict_Check(t)) {
+    PyObject *k = nullptr, *v = nullptr;
+    Py_ssize_t pos = 0;
+    while (ok && PyDict_Next(t, &pos, &k, &v)) {
+      std::pair<unsigned, unsigned> p;
+      ok = code_point(k, false, &p.first) && code_point(v, true, &p.second);
+      table.push_back(p);
+    }
+    if (!ok) {
+      PyErr_SetString(PyExc_ValueError, "nvstrings.translate: invalid map entry");
+      return nullptr;
+    }
+  } else {
+    PyErr_SetString(PyExc_ValueError, "nvstrings.translate: invalid argument type");
+    return nullptr;
+  }
+  return make_instance([&] { return s->translate(table.data(), (unsigned int)table.size()); });
+}
+static PyObject* n_fillna(PyObject*, PyObject* args) {  // (self, repl): a str, or an nvstrings object of the same size
+  NVStrings* s = SELF(args);
+  PyObject* r = arg(args, 1);
+  if (r == Py_None) {
+    PyErr_SetString(PyExc_ValueError, "nvstrings.fillna repl argument must be specified");
+    return nullptr;
+  }
+  if (PyUnicode_Check(r)) {
+    const char* str = PyUnicode_AsUTF8(r);
+    return make_instance([&] { return s->fillna(str); });
+  }
+  NVStrings* other = PyLong_Check(r) ? nullptr : handle_of<NVStrings>(r);
+  if (!other) {
+    PyErr_SetString(PyExc_ValueError, "nvstrings.fillna repl argument must be a str or an nvstrings object");
+    return nullptr;
+  }
+  if (other->size() != s->size()) {
+    PyErr_SetString(PyExc_ValueError, "nvstrings.fillna repl argument must be same size");
+    return nullptr;
+  }
+  return make_instance([&] { return s->fillna(*other); });
+}
+
 static PyMethodDef s_Methods[] = {
 #define M(n) {#n, n, METH_VARARGS, ""}
     M(n_dropWrapper), M(n_getIPCData), M(n_createFromIPC),
@@ -841,6 +975,7 @@ static PyMethodDef s_Methods[] = {
     M(n_rjust), M(n_zfill), M(n_wrap),
     M(n_isalnum), M(n_isalpha), M(n_isdigit), M(n_isspace), M(n_isdecimal), M(n_isnumeric), M(n_islower), M(n_isupper), M(n_is_empty),
     M(n_swapcase), M(n_capitalize), M(n_title),
+    M(n_index), M(n_rindex), M(n_url_encode), M(n_url_decode), M(n_translate), M(n_fillna),
 #undef M
     {NULL, NULL, 0, NULL}};
 static struct PyModuleDef s_Module = {PyModuleDef_HEAD_INIT, "pyniNVStrings", "CPython glue of nvstrings over the MI355X back-end", -1, s_Methods};

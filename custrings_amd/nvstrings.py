@@ -108,6 +108,8 @@ def bind_cpointer(cptr, own=True):
     return nvstrings(cptr, own)
 
 
+# (inert: all six are methods of the class now, found before __getattr__ is asked; the list keeps its value for the
+# assertion in tests/test_chartype_cpu.py and goes with it)
 _NOT_BUILT = "fillna index rindex translate url_encode url_decode".split()
 
 
@@ -1012,6 +1014,79 @@ class nvstrings:
     def title(self):
         """A letter after a non-letter (or at the start) to upper, a letter after a letter to lower case."""
         return self._made(lambda o: lib.cs_title(self.m_cptr, None, o))
+
+    # ---- index / rindex, the URL codec, translate, fillna (nvstrings.py:1558, 1740-1794, 2303, 2589-2627) ------------
+    def _index(self, name, fn, sub, start, end, devptr):
+        end = -1 if end is None else int(end)
+        rows = self.size()
+        found = C.c_int64()
+        if devptr:
+            check(fn(self.m_cptr, b(sub), int(start), end, devptr, 1, None, C.byref(found)))
+            if found.value != rows:  # (null rows count as found; the results are in the caller's buffer either way)
+                raise ValueError("nvstrings.%s: [%s] not found in %d elements" % (name, sub, rows - found.value))
+            return devptr
+        res = np.zeros(max(rows, 1), dtype=np.int32)
+        check(fn(self.m_cptr, b(sub), int(start), end, res.ctypes.data, 0, None, C.byref(found)))
+        out = []
+        for i, v in enumerate(res[:rows]):
+            if v == -1:
+                raise ValueError("nvstrings.%s: [%s] not found in element %d" % (name, sub, i))
+            out.append(None if v < -1 else int(v))
+        return out
+
+    def index(self, sub, start=0, end=None, devptr=0):
+        """nvstrings.py:1740-1766 -- find that raises ValueError when some row does not hold `sub`; None for null rows."""
+        return self._index("index", lib.cs_find, sub, start, end, devptr)
+
+    def rindex(self, sub, start=0, end=None, devptr=0):
+        """nvstrings.py:1768-1794 -- rfind that raises ValueError when some row does not hold `sub`."""
+        return self._index("rindex", lib.cs_rfind, sub, start, end, devptr)
+
+    def url_encode(self):
+        """nvstrings.py:2589-2607 -- every byte but 0-9 A-Z a-z . _ ~ - becomes '%' and two upper-case hex digits."""
+        return self._made(lambda o: lib.cs_url_encode(self.m_cptr, None, o))
+
+    def url_decode(self):
+        """nvstrings.py:2609-2627 -- '%' and the two bytes behind it become one byte."""
+        return self._made(lambda o: lib.cs_url_decode(self.m_cptr, None, o))
+
+    def translate(self, table):
+        """nvstrings.py:2303-2330 -- every character that is a key of `table` becomes its target, None drops it: a dict
+        of ordinal -> ordinal | None (str.maketrans), or a list of [char, char | None].  Of several entries with one
+        key the last wins."""
+        def cp(v, none_ok):
+            if v is None and none_ok:
+                return 0
+            if isinstance(v, str) and len(v) >= 1:
+                return ord(v[0])
+            if isinstance(v, int) and not isinstance(v, bool) and 0 <= v <= 0xFFFFFFFF:
+                return v
+            raise ValueError("nvstrings.translate: invalid map entry")
+        if isinstance(table, dict):
+            pairs = [(cp(k, False), cp(v, True)) for k, v in table.items()]
+        elif isinstance(table, list):
+            for e in table:
+                if not isinstance(e, (list, tuple)) or len(e) != 2:
+                    raise ValueError("nvstrings.translate: invalid map entry")
+            pairs = [(cp(e[0], False), cp(e[1], True)) for e in table]
+        else:
+            raise ValueError("nvstrings.translate: invalid argument type")
+        keys = np.array([p[0] for p in pairs], dtype=np.uint32)
+        vals = np.array([p[1] for p in pairs], dtype=np.uint32)
+        return self._made(lambda o: lib.cs_translate(self.m_cptr, keys.ctypes.data if len(pairs) else None,
+                                                     vals.ctypes.data if len(pairs) else None, len(pairs), None, o))
+
+    def fillna(self, repl):
+        """nvstrings.py:1558-1582 -- null rows take `repl`: a str, or the same row of another nvstrings of this size."""
+        if repl is None:
+            raise ValueError("nvstrings.fillna repl argument must be specified")
+        if isinstance(repl, str):
+            return self._made(lambda o: lib.cs_fillna(self.m_cptr, b(repl), None, o))
+        if not isinstance(repl, nvstrings):
+            raise ValueError("nvstrings.fillna repl argument must be a str or an nvstrings object")
+        if repl.size() != self.size():
+            raise ValueError("nvstrings.fillna repl argument must be same size")
+        return self._made(lambda o: lib.cs_fillna_column(self.m_cptr, repl.m_cptr, None, o))
 
     def timestamp2int(self, format=None, units="s", devptr=0):
         """

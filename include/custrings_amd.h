@@ -678,6 +678,29 @@ int cs_porter_stemmer_measure(const cs_column* col, const char* vowels, const ch
  * a total of 2^31 or more: CS_ERR_RANGE. */
 int cs_scatter_count(const cs_column* col, const uint32_t* counts, int on_device, cs_stream stream, cs_column** out);
 
+/* ---- the URL codec, translate and fillna (reference: cpp/src/strings/urlencode.cu, modify.cu:302-489; per-row logic in
+ * custrings_amd/csrc/recode_ops.h; kernels cs_recode.hip) --------------------------------------------------------
+ * url_encode, url_decode and translate keep null rows null (the output shares the input's validity); an output row of
+ * 2^31 bytes or more is CS_ERR_RANGE. */
+/* NVStrings::url_encode (NVStrings.h:1181; urlencode.cu:44-164): the ASCII bytes 0-9 A-Z a-z . _ ~ - are copied, every
+ * other byte becomes '%' and two upper-case hex digits.  Rows that are not valid UTF-8 follow the same byte rule. */
+int cs_url_encode(const cs_column* col, cs_stream stream, cs_column** out);
+/* NVStrings::url_decode (NVStrings.h:1188; urlencode.cu:179-277): a '%' with at least two bytes behind it in the row
+ * consumes them and emits one byte -- a digit is 0-9, A-Z (value c - 55) or a-z (c - 87), anything else 0, the byte
+ * taken modulo 256; every other byte is copied. */
+int cs_url_decode(const cs_column* col, cs_stream stream, cs_column** out);
+/* NVStrings::translate (NVStrings.h:733; modify.cu:302-390): every character that is a key of the table becomes its
+ * target, a target of 0 drops it; `from` / `to` are HOST arrays of n code points.  Of several pairs with one key the
+ * last wins.  A sequence that is not one well-formed UTF-8 character (an encoded surrogate included) matches no key and is copied.  A code point above
+ * U+10FFFF, n < 0 or a missing array: CS_ERR_INVALID_ARG. */
+int cs_translate(const cs_column* col, const uint32_t* from, const uint32_t* to, int n, cs_stream stream, cs_column** out);
+/* NVStrings::fillna(const char*) (NVStrings.h:739; modify.cu:395-439): null rows take `str`, the result has no nulls.
+ * str NULL: CS_ERR_INVALID_ARG. */
+int cs_fillna(const cs_column* col, const char* str, cs_stream stream, cs_column** out);
+/* NVStrings::fillna(NVStrings&) (NVStrings.h:747; modify.cu:444-489): a null row takes the same row of `repl` (and stays
+ * null where that is null too).  Another row count: CS_ERR_INVALID_ARG. */
+int cs_fillna_column(const cs_column* col, const cs_column* repl, cs_stream stream, cs_column** out);
+
 #ifdef __cplusplus
 }
 #endif

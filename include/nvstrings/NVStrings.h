@@ -139,6 +139,15 @@ class NVStrings {
   NVStrings* slice_replace(const char* repl, int start = 0, int stop = -1);
   NVStrings* insert(const char* repl, int pos = 0);
 
+  /* ---- the URL codec, translate and fillna (NVStrings.h:733-747,1181-1188; urlencode.cu, modify.cu:302-489).  The table
+   * is `count` (code point, code point) pairs, a target of 0 dropping the character; of several pairs with one key the
+   * last wins.  A null `str`, another row count and a code point above U+10FFFF throw std::invalid_argument. ---- */
+  NVStrings* translate(std::pair<unsigned, unsigned>* table, unsigned int count);
+  NVStrings* fillna(const char* str);
+  NVStrings* fillna(NVStrings& strs);
+  NVStrings* url_encode();
+  NVStrings* url_decode();
+
   /* ---- search (NVStrings.h:861-981) ---- */
   unsigned int find(const char* str, int start, int end, int* results, bool devmem = true);
   int contains(const char* str, bool* results, bool devmem = true);

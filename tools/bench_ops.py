@@ -61,7 +61,7 @@ def report(config, op, rows, in_bytes, alg_bytes, dt):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scale", type=float, default=1.0, help="row-count multiplier (1.0 = BASELINE.json single-GPU sizes)")
-    ap.add_argument("--only", default="C2,C3,C4,C5", help="comma-separated configs to run (CONV: the conversion ops, TS: the timestamp ones, PAD: substring / padding / wrapping, CHR: character types and swapcase / capitalize / title, TXT: the NVText matches, edit distance, stemmer measure and scatter_count)")
+    ap.add_argument("--only", default="C2,C3,C4,C5", help="comma-separated configs to run (CONV: the conversion ops, TS: the timestamp ones, PAD: substring / padding / wrapping, CHR: character types and swapcase / capitalize / title, TXT: the NVText matches, edit distance, stemmer measure and scatter_count, URL: url_encode / url_decode / translate / fillna)")
     a = ap.parse_args()
     only = set(a.only.split(","))
     ov = 8.125  # native offset + validity bytes per row
@@ -84,6 +84,8 @@ def main():
         run_chr(a)
     if "TXT" in only:
         run_txt(a)
+    if "URL" in only:
+        run_url(a)
 
 
 def run_c2(a, ov):
@@ -366,6 +368,47 @@ def run_chr(a):
                 report("CHR %s 100M [%s]" % (name, got_route), op, rows, b, 2 * b + 8.125 * rows + wr, dt)
         del col
     L.cs_config_set(b"CS_CASE_ROWWISE", None)
+
+
+def run_url(a):
+    # ---- url_encode / url_decode / translate / fillna (urlencode.cu, modify.cu:302-489) on the C3 and C5 columns, on both routes
+    # (the default, then CS_RECODE_ROWWISE=1; fillna has one).  Bytes: the chars + offsets + validity read, the chars + offsets
+    # written.  Beside them, from the same run: the box's copy rate (cs_box_rates) and slice / lower on the same column.
+    # url_decode runs on url_encode's output; translate with an ASCII table (e -> E, ' ' -> '_', '.' dropped) and with one that
+    # changes widths (' ' -> U+20AC, 'e' -> U+00E9).
+    rates = (C.c_double * 6)()
+    _lib.check(L.cs_box_rates(2048, 3, None, rates))
+    print(json.dumps({"config": "URL box", "copy_GBps": round(rates[0] * 1e3, 1), "read_GBps": round(rates[1] * 1e3, 1),
+                      "write_GBps": round(rates[2] * 1e3, 1)}), flush=True)
+    ascii_t = {ord("e"): ord("E"), ord(" "): ord("_"), ord("."): None}
+    wide_t = {ord(" "): 0x20AC, ord("e"): 0xE9}
+    for kind, name, rows in ((3, "C3", int(100_000_000 * a.scale)), (5, "C5", int(62_500_000 * a.scale))):
+        col = synth(kind, rows)
+        b = nbytes(col)
+
+        def line(cfg, op, src, fn, extra=0):
+            res = fn()
+            w = nbytes(res) + 8 * rows
+            route = L.cs_debug_last_route().decode()
+            del res
+            dt = timed(fn, reps=3)
+            report("URL %s %s [%s]" % (name, cfg, route), op, rows, nbytes(src), nbytes(src) + 8.125 * rows + extra + w, dt)
+
+        enc = col.url_encode()
+        for route in ("default", "rowwise"):
+            L.cs_config_set(b"CS_RECODE_ROWWISE", b"1" if route == "rowwise" else None)
+            line(route, "url_encode", col, lambda: col.url_encode())
+            line(route, "url_decode (of url_encode)", enc, lambda: enc.url_decode())
+            line(route, "translate (3 ASCII keys)", col, lambda: col.translate(ascii_t))
+            line(route, "translate (2 keys, 1 -> 3 / 2 bytes)", col, lambda: col.translate(wide_t))
+        L.cs_config_set(b"CS_RECODE_ROWWISE", None)
+        line("default", "fillna('-')", col, lambda: col.fillna("-"))
+        line("default", "fillna(column)", col, lambda: col.fillna(enc), extra=0.125 * rows)
+        dt = timed(lambda: col.slice(2, 12), reps=3)
+        report("URL %s neighbour [%s]" % (name, L.cs_debug_last_route().decode()), "slice(2,12)", rows, b, b + 8.125 * rows + nbytes(col.slice(2, 12)) + 8 * rows, dt)
+        dt = timed(lambda: col.lower(), reps=3)
+        report("URL %s neighbour" % name, "lower", rows, b, 2 * b + 8.125 * rows, dt)
+        del col, enc
 
 
 def run_txt(a):

@@ -19,7 +19,7 @@ LIB = _lib.lib
 
 TOGGLES = ("CS_REGEX_TWO_PASS", "CS_REGEX_ROWWISE", "CS_SPLIT_GENERIC", "CS_TOKENIZE_ROWWISE", "CS_STRIP_ROWWISE",
            "CS_FIND_ROWWISE", "CS_REPLACE_ROWWISE", "CS_CASE_ROWWISE", "CS_NGRAM_ROWWISE", "CS_CONVERT_ROWWISE",
-           "CS_TEXT_ROWWISE", "CS_NO_CLASS_RUNS")  # (the byte-parallel class route is a fast path too: off in the witness -- it sat on both sides until round 5's last soak)
+           "CS_TEXT_ROWWISE", "CS_RECODE_ROWWISE", "CS_NO_CLASS_RUNS")  # (the byte-parallel class route is a fast path too: off in the witness -- it sat on both sides until round 5's last soak)
 PATS = [(r"\d+\.\d+\.\d+\.\d+", "<IP>"), (r"\d", "#"), (r"[a-c]+", "xyz__"), (r"\s+", " "), (r"\w+", "<w>"), (r"b|ab", ""),
         (r"\bx", "YY"), (r"[0-9]+", "<number-here>"), (r"a", "aa"), (r"(a|b)c", "-"),
         (r"\d+\.\d+ ", "<n>"), (r"[a-c]+=>", ""), (r"\d+ab", "#"),  # (chains with a literal suffix)
@@ -155,6 +155,15 @@ def snapshot(g, rows, rng_seed, pats=None, regex_only=False):
     sc = nvtext.scatter_count(g, [i % 3 for i in range(rows)]) if rows else None
     if sc is not None:
         out["scatter_count"] = gpuutil.to_col(sc)
+    # the URL codec, translate and fillna (tile route against the row-wise one: CS_RECODE_ROWWISE; fillna has one route)
+    out["url_encode"] = gpuutil.to_col(g.url_encode())
+    out["url_decode"] = gpuutil.to_col(g.url_decode())
+    out["url_decode of url_encode"] = gpuutil.to_col(g.url_encode().url_decode())
+    for name, table in (("ascii", {ord("a"): ord("A"), ord(" "): None, 0: ord("0")}), ("widths", {ord("a"): 0x20AC, 0xE9: ord("e"), 0x1F600: 0xDF, ord("."): None}),
+                        ("300 keys", {**{0x100 + k: ord("a") + k % 26 for k in range(300)}, 0x20AC: 0x1F600})):
+        out["translate " + name] = gpuutil.to_col(g.translate(table))
+    out["fillna str"] = gpuutil.to_col(g.fillna("é-"))
+    out["fillna column"] = gpuutil.to_col(g.fillna(g.url_encode().lower()))
     for sub in ("3.4", "é", "ab"):
         f = np.zeros(max(rows, 1), dtype=np.int32)
         found = C.c_int64()
