@@ -193,6 +193,33 @@ _PROTOS = {
     "cs_category_values_ptr": (vp, [vp]),
     "cs_category_get_values": (i32, [vp, vp, i32, vp]),
     "cs_remap_codes": (i32, [vp, i64, vp, vp, vp]),
+    # numeric categories (numeric_category.h)
+    "cs_numcat_build": (i32, [vp, i64, vp, i32, i32, vp, P(vp)]),
+    "cs_numcat_destroy": (i32, [vp]),
+    "cs_numcat_size": (i64, [vp]),
+    "cs_numcat_keys_size": (i64, [vp]),
+    "cs_numcat_type": (i32, [vp]),
+    "cs_numcat_keys_ptr": (vp, [vp]),
+    "cs_numcat_values_ptr": (vp, [vp]),
+    "cs_numcat_nulls_ptr": (vp, [vp]),
+    "cs_numcat_has_nulls": (i32, [vp]),
+    "cs_numcat_keys_have_null": (i32, [vp]),
+    "cs_numcat_get_keys": (i32, [vp, vp, i32, vp]),
+    "cs_numcat_get_values": (i32, [vp, vp, i32, vp]),
+    "cs_numcat_to_type": (i32, [vp, vp, vp, i32, vp]),
+    "cs_numcat_gather_type": (i32, [vp, vp, i64, vp, vp, i32, vp]),
+    "cs_numcat_index_for": (i32, [vp, vp, vp, P(i32)]),
+    "cs_numcat_indexes_for": (i32, [vp, vp, vp, i32, vp, P(i64)]),
+    "cs_numcat_add_keys": (i32, [vp, vp, i64, vp, i32, vp, P(vp)]),
+    "cs_numcat_remove_keys": (i32, [vp, vp, i64, vp, i32, vp, P(vp)]),
+    "cs_numcat_set_keys": (i32, [vp, vp, i64, vp, i32, vp, P(vp)]),
+    "cs_numcat_remove_unused_keys": (i32, [vp, vp, P(vp)]),
+    "cs_numcat_merge": (i32, [vp, vp, vp, P(vp)]),
+    "cs_numcat_gather": (i32, [vp, vp, i64, i32, vp, P(vp)]),
+    "cs_numcat_gather_and_remap": (i32, [vp, vp, i64, i32, vp, P(vp)]),
+    "cs_numcat_gather_values": (i32, [vp, vp, i64, i32, vp, P(vp)]),
+    "cs_numcat_copy": (i32, [vp, vp, P(vp)]),
+    "cs_debug_numcat_sort_rows": (i32, [vp, i64, i32, i32, vp]),
     "cs_tokenize": (i32, [vp, cp, vp, P(vp)]),
     "cs_tokenize_multi": (i32, [vp, vp, vp, P(vp)]),
     "cs_ngrams": (i32, [vp, C.c_uint, cp, vp, P(vp)]),

@@ -701,6 +701,61 @@ int cs_fillna(const cs_column* col, const char* str, cs_stream stream, cs_column
  * null where that is null too).  Another row count: CS_ERR_INVALID_ARG. */
 int cs_fillna_column(const cs_column* col, const cs_column* repl, cs_stream stream, cs_column** out);
 
+/* ---- numeric categories (numeric_category.h) ---------------------------- */
+/* Sorted unique keys of one numeric type and an int32 value per row.  -0.0 and +0.0 are one key; all NaN are one key,
+ * behind +inf.  The number kept for a key is that of the lowest-indexed row of its class.  `nulls` is an LSB-first bitmask,
+ * a 0 bit is a null item; when an item is null, key 0 is the null key and null rows have value 0.  A row is null exactly
+ * when the key set includes the null key and the row's value is 0: the bitmask of a category follows from its values.
+ * `on_device` says where the caller's arrays (items, nulls, indexes, results) live.  Outputs own their buffers. */
+typedef struct cs_numcat cs_numcat;
+typedef enum cs_numtype { CS_NUM_I8 = 0, CS_NUM_I32 = 1, CS_NUM_I64 = 2, CS_NUM_F32 = 3, CS_NUM_F64 = 4 } cs_numtype;
+/* numeric_category<T>(items, count, nulls).  items NULL or n == 0: an empty category.  n >= 2^31 - 1: CS_ERR_RANGE. */
+int cs_numcat_build(const void* items, int64_t n, const uint8_t* nulls, cs_numtype type, int on_device, cs_stream stream,
+                    cs_numcat** out);
+int cs_numcat_destroy(cs_numcat* cat);
+int64_t cs_numcat_size(const cs_numcat* cat);
+int64_t cs_numcat_keys_size(const cs_numcat* cat);
+int cs_numcat_type(const cs_numcat* cat);              /* cs_numtype */
+const void* cs_numcat_keys_ptr(const cs_numcat* cat);  /* device memory; NULL without keys */
+const int32_t* cs_numcat_values_ptr(const cs_numcat* cat);
+const uint8_t* cs_numcat_nulls_ptr(const cs_numcat* cat); /* NULL unless the key set includes the null key */
+int cs_numcat_has_nulls(const cs_numcat* cat);            /* some row is null */
+int cs_numcat_keys_have_null(const cs_numcat* cat);
+int cs_numcat_get_keys(const cs_numcat* cat, void* out, int on_device, cs_stream stream);
+int cs_numcat_get_values(const cs_numcat* cat, int32_t* out, int on_device, cs_stream stream);
+/* to_type: results[i] = keys[values[i]] (0 where the value is -1); `nulls`, when given, is always written ((size + 7) / 8
+ * bytes, all rows' bits 1 when none is null). */
+int cs_numcat_to_type(const cs_numcat* cat, void* results, uint8_t* nulls, int on_device, cs_stream stream);
+/* gather_type: keys[indexes[i]]; an index outside [0, keys_size): CS_ERR_RANGE.  The bit of an index that names the null key is 0. */
+int cs_numcat_gather_type(const cs_numcat* cat, const int32_t* indexes, int64_t n, void* results, uint8_t* nulls, int on_device,
+                          cs_stream stream);
+/* `key`: HOST pointer to one number of the category's type, NULL = the null key.  An absent key: -1 / no rows. */
+int cs_numcat_index_for(const cs_numcat* cat, const void* key, cs_stream stream, int32_t* out);
+/* the rows whose value is the key's index, ascending; `results` may be NULL (count only) */
+int cs_numcat_indexes_for(const cs_numcat* cat, const void* key, int32_t* results, int on_device, cs_stream stream, int64_t* count);
+/* The key-set family: a new category every time.  Values of removed keys become -1; removing the null key leaves no null rows. */
+int cs_numcat_add_keys(const cs_numcat* cat, const void* items, int64_t n, const uint8_t* nulls, int on_device, cs_stream stream,
+                       cs_numcat** out);
+int cs_numcat_remove_keys(const cs_numcat* cat, const void* items, int64_t n, const uint8_t* nulls, int on_device, cs_stream stream,
+                          cs_numcat** out);
+int cs_numcat_set_keys(const cs_numcat* cat, const void* items, int64_t n, const uint8_t* nulls, int on_device, cs_stream stream,
+                       cs_numcat** out);
+int cs_numcat_remove_unused_keys(const cs_numcat* cat, cs_stream stream, cs_numcat** out);
+/* merged sorted key set; this category's values followed by cat2's, renumbered.  Different types: CS_ERR_INVALID_ARG. */
+int cs_numcat_merge(const cs_numcat* cat, const cs_numcat* cat2, cs_stream stream, cs_numcat** out);
+/* gather: same keys, the indexes (each in [0, keys_size)) as values; gather_and_remap: only the keys they name;
+ * gather_values: values[indexes[i]], each index in [0, size).  Otherwise CS_ERR_RANGE. */
+int cs_numcat_gather(const cs_numcat* cat, const int32_t* indexes, int64_t n, int on_device, cs_stream stream, cs_numcat** out);
+int cs_numcat_gather_and_remap(const cs_numcat* cat, const int32_t* indexes, int64_t n, int on_device, cs_stream stream,
+                               cs_numcat** out);
+int cs_numcat_gather_values(const cs_numcat* cat, const int32_t* indexes, int64_t n, int on_device, cs_stream stream,
+                            cs_numcat** out);
+int cs_numcat_copy(const cs_numcat* cat, cs_stream stream, cs_numcat** out);
+/* A yardstick for tools/bench_ops.py, not a route of the library: the images of all n rows with their row numbers through
+ * the radix sort (the reference's algorithm -- sort every row -- on this project's sort).  Nothing is returned; the call
+ * waits for the sort.  UNSUPPORTED: a cs_debug_* entry point is not part of the interface a caller may rely on. */
+int cs_debug_numcat_sort_rows(const void* items, int64_t n, cs_numtype type, int on_device, cs_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,7 +61,7 @@ def report(config, op, rows, in_bytes, alg_bytes, dt):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scale", type=float, default=1.0, help="row-count multiplier (1.0 = BASELINE.json single-GPU sizes)")
-    ap.add_argument("--only", default="C2,C3,C4,C5", help="comma-separated configs to run (CONV: the conversion ops, TS: the timestamp ones, PAD: substring / padding / wrapping, CHR: character types and swapcase / capitalize / title, TXT: the NVText matches, edit distance, stemmer measure and scatter_count, URL: url_encode / url_decode / translate / fillna)")
+    ap.add_argument("--only", default="C2,C3,C4,C5", help="comma-separated configs to run (CONV: the conversion ops, TS: the timestamp ones, PAD: substring / padding / wrapping, CHR: character types and swapcase / capitalize / title, TXT: the NVText matches, edit distance, stemmer measure and scatter_count, URL: url_encode / url_decode / translate / fillna, NUM: the numeric categories -- from_numbers, to_numbers, merge_and_remap -- beside two yardsticks)")
     a = ap.parse_args()
     only = set(a.only.split(","))
     ov = 8.125  # native offset + validity bytes per row
@@ -86,6 +86,8 @@ def main():
         run_txt(a)
     if "URL" in only:
         run_url(a)
+    if "NUM" in only:
+        run_num(a)
 
 
 def run_c2(a, ov):
@@ -456,6 +458,41 @@ def run_txt(a):
                 line("scatter_count (0/1/2)", scatter, 4 * rows + b + 2 * 8.125 * rows)
         del col
     L.cs_config_set(b"CS_TEXT_ROWWISE", None)
+
+
+
+
+def run_num(a):
+    """from_numbers on 100M rows of int32 / int64 / float64 at K = 1 000, K = 1 M and K = N distinct keys, to_numbers and
+    merge_and_remap of two such categories -- and, in the same run, two yardsticks that are not the code under test:
+    radix_sort_pairs64 over all N (image, row) pairs (the reference's sort-every-row on this project's sort) and the string
+    cs_category_build at the same N and K.  Algorithmic bytes of the build: the rows read once, an int32 value written."""
+    from custrings_amd import nvcategory
+
+    rows = int(100_000_000 * a.scale)
+    for K in (1000, 1_000_000, rows):
+        K = min(K, rows)
+        base = torch.randperm(rows, device="cuda") if K == rows else torch.randint(0, K, (rows,), device="cuda")
+        base = base - K // 2  # negatives mixed in
+        for name, code, col in (("int32", 1, base.to(torch.int32)), ("int64", 2, base.to(torch.int64)), ("float64", 4, base.to(torch.float64) * 0.5)):
+            width = col.element_size()
+            dt = timed(lambda: nvcategory.from_numbers(col))
+            report("NUM", "from_numbers %s K=%d" % (name, K), rows, rows * width, rows * (width + 4), dt)
+            dt = timed(lambda: _lib.check(L.cs_debug_numcat_sort_rows(col.data_ptr(), rows, code, 1, None)))
+            report("NUM", "yardstick radix_sort_pairs64 of all rows %s K=%d" % (name, K), rows, rows * width, rows * (width + 4), dt)
+            cat = nvcategory.from_numbers(col)
+            out = torch.empty_like(col)
+            dt = timed(lambda: cat.to_numbers(out))
+            report("NUM", "to_numbers %s K=%d" % (name, K), rows, rows * 4, rows * (width + 4), dt)
+            other = nvcategory.from_numbers(col + (K // 2))  # half of the keys shared
+            dt = timed(lambda: cat.merge_and_remap(other))
+            report("NUM", "merge_and_remap %s K=%d" % (name, K), 2 * rows, 2 * rows * 4, 2 * rows * 8, dt)
+            del cat, other, out, col
+        del base
+        strs = synth(4, rows, K)
+        dt = timed(lambda: nvcategory.from_strings(strs))
+        report("NUM", "yardstick string cs_category_build K=%d" % K, rows, nbytes(strs), nbytes(strs) + rows * 4, dt)
+        del strs
 
 
 if __name__ == "__main__":
