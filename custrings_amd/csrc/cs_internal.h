@@ -51,6 +51,16 @@ int guard(F&& f) {
 // device when its current device differs (hipSetDevice is per thread).
 void require_device();
 int bound_device();  // -1 before cs_init
+// A C entry that makes a column from a column: `*out` is f()'s column, null when anything fails.
+template <class F>
+int column_entry(const cs_column* col, cs_column** out, F&& f) {
+  return guard([&] {
+    if (!col || !out) fail(CS_ERR_INVALID_ARG, "null column or output");
+    *out = nullptr;
+    require_device();
+    *out = f();
+  });
+}
 // One message per process on stderr and a counter (cs_fallback_count): a persistent single-pass
 // kernel gave up and the host recomputed the column with the two-pass kernels.
 void note_fallback(const char* what);

@@ -2,16 +2,10 @@
 // The per-row logic of the three ops that change row lengths is recode_ops.h, shared with the CPU harness of
 // tests/test_recode_cpu.py.
 //
-// url_encode, url_decode and translate are a size pass, a scan (cs::Built) and a write pass, on two routes, both templated
-// on the op:
-//  - tile: a wave stages R consecutive rows in LDS (cstile::walk_staged_tiles, both passes).  The size pass maps its rows
-//    to one int32 each out of LDS; the write pass has every lane write its row into an LDS out-tile and the tile leaves
-//    with 16-byte stores (cstile::wave_flush_shift).  A tile whose input exceeds the staging buffer is read from memory
-//    (Oversize::kFromMemory); a tile whose OUTPUT exceeds the out-tile -- url_encode grows a row up to 3x, translate up to
-//    4x -- is written to memory by its lanes, from wherever its input is.  translate's 128 ASCII targets are staged once
-//    per workgroup in front of the waves' buffers.
-//  - rows: a thread per row from memory (CS_RECODE_ROWWISE=1, and columns the tile plan refuses).
-// An output row of 2^31 bytes or more is CS_ERR_RANGE; the offsets are int64.
+// url_encode, url_decode and translate run on the sized route (sized_route.h: size pass, scan, write pass; tile and rows,
+// CS_RECODE_ROWWISE=1) with the route's own write body: url_encode grows a row up to 3x, translate up to 4x, and a staged
+// tile whose output exceeds the out-tile is written to memory by its lanes out of LDS.  translate's 128 ASCII targets
+// are the op's shared region.
 // fillna sizes its rows from offsets and validity alone and copies spans (a thread per row, as cs_scatter's copy does).
 #include <hip/hip_runtime.h>
 
@@ -22,7 +16,7 @@
 #include "cs_internal.h"
 #include "device_utils.h"
 #include "recode_ops.h"
-#include "tile_utils.h"
+#include "sized_route.h"
 
 using namespace cs;
 using namespace csdev;
@@ -31,167 +25,41 @@ using csrecode::Table;
 
 namespace {
 
-constexpr int kOutCapMax = 16 * 1024;  // LDS out-tile per wave at most (tiles beyond it are written to memory)
-constexpr int kAsciiBytes = csrecode::kAsciiKeys * (int)sizeof(uint32_t);
-
-struct RecodeArgs {
-  ColView in;
-  SafeMask safe;  // url_encode
-  Table tab;      // translate (device memory)
-  int32_t* lens;           // size pass
-  unsigned* overflow;      // size pass: set when a row reaches 2^31 bytes
-  const int64_t* out_off;  // write pass
-  uint8_t* out_chars;
-  int rows_per_tile, cap, out_cap;
-  long long ntiles;
+struct UrlEncode {
+  SafeMask safe;
+  __device__ __forceinline__ int64_t size(int64_t, const uint8_t* p, int n) const { return csrecode::encode_size(safe, p, n); }
+  __device__ __forceinline__ void write(int64_t, const uint8_t* p, int n, uint8_t* o) const { csrecode::encode_write(safe, p, n, o); }
+};
+struct UrlDecode {
+  __device__ __forceinline__ int64_t size(int64_t, const uint8_t* p, int n) const { return csrecode::decode_size(p, n); }
+  __device__ __forceinline__ void write(int64_t, const uint8_t* p, int n, uint8_t* o) const { csrecode::decode_write(p, n, o); }
+};
+struct Translate {
+  Table tab;  // (device memory)
+  // the workgroup's copy of the 128 ASCII targets
+  static constexpr int kSharedBytes = csrecode::kAsciiKeys * (int)sizeof(uint32_t);
+  __device__ __forceinline__ void stage(uint8_t* lds, int tid) const {
+    if (tid < csrecode::kAsciiKeys) reinterpret_cast<uint32_t*>(lds)[tid] = tab.ascii[tid];
+  }
+  __device__ __forceinline__ Table staged(const uint8_t* shared) const {
+    Table t = tab;
+    t.ascii = reinterpret_cast<const uint32_t*>(shared);
+    return t;
+  }
+  __device__ __forceinline__ int64_t size(int64_t, const uint8_t* p, int n) const { return csrecode::translate_size(tab, p, n); }
+  __device__ __forceinline__ int64_t size(int64_t, const uint8_t* p, int n, const uint8_t* shared) const {
+    return csrecode::translate_size(staged(shared), p, n);
+  }
+  __device__ __forceinline__ void write(int64_t, const uint8_t* p, int n, uint8_t* o) const { csrecode::translate_write(tab, p, n, o); }
+  __device__ __forceinline__ void write(int64_t, const uint8_t* p, int n, uint8_t* o, const uint8_t* shared) const {
+    csrecode::translate_write(staged(shared), p, n, o);
+  }
 };
 
-template <int OP>
-constexpr int shared_bytes() {
-  return OP == csrecode::OP_TRANSLATE ? kAsciiBytes : 0;
-}
-
-template <int OP>
-__device__ __forceinline__ int64_t row_size(const RecodeArgs& a, const Table& t, const uint8_t* p, int n) {
-  if constexpr (OP == csrecode::OP_URL_ENCODE) return csrecode::encode_size(a.safe, p, n);
-  else if constexpr (OP == csrecode::OP_URL_DECODE) return csrecode::decode_size(p, n);
-  else return csrecode::translate_size(t, p, n);
-}
-template <int OP>
-__device__ __forceinline__ void row_write(const RecodeArgs& a, const Table& t, const uint8_t* p, int n, uint8_t* o) {
-  if constexpr (OP == csrecode::OP_URL_ENCODE) csrecode::encode_write(a.safe, p, n, o);
-  else if constexpr (OP == csrecode::OP_URL_DECODE) csrecode::decode_write(p, n, o);
-  else csrecode::translate_write(t, p, n, o);
-}
-
-// the size of row r, its n bytes at p (memory or LDS); -1 for a null row
-template <int OP>
-__device__ __forceinline__ void size_row(const RecodeArgs& a, const Table& t, int64_t r, const uint8_t* p, int n, bool valid) {
-  int32_t len = -1;
-  if (valid) {
-    const int64_t sz = row_size<OP>(a, t, p, n);
-    if (sz >= ((int64_t)1 << 31)) {
-      atomicOr(a.overflow, 1u);
-      len = 0;
-    } else {
-      len = (int32_t)sz;
-    }
-  }
-  a.lens[r] = len;
-}
-
-// the workgroup's copy of translate's ASCII targets at the front of the LDS; the waves' buffers follow it
-template <int OP>
-__device__ __forceinline__ Table stage_table(const RecodeArgs& a, uint32_t* smem) {
-  Table t = a.tab;
-  if constexpr (OP == csrecode::OP_TRANSLATE) {
-    if (threadIdx.x < csrecode::kAsciiKeys) smem[threadIdx.x] = a.tab.ascii[threadIdx.x];
-    __syncthreads();
-    t.ascii = smem;
-  }
-  return t;
-}
-
-// ---- rows ----------------------------------------------------------------------------------------------------------------
-template <int OP>
-__global__ void __launch_bounds__(256) k_recode_size_rows(RecodeArgs a) {
-  for_each_row(a.in, [&](int64_t r, const uint8_t* p, int n, bool valid) { size_row<OP>(a, a.tab, r, p, n, valid); });
-}
-
-template <int OP>
-__global__ void __launch_bounds__(256) k_recode_write_rows(RecodeArgs a) {
-  for_each_row(a.in, [&](int64_t r, const uint8_t* p, int n, bool valid) {
-    if (valid) row_write<OP>(a, a.tab, p, n, a.out_chars + a.out_off[r]);
-  });
-}
-
-// ---- tiles ---------------------------------------------------------------------------------------------------------------
-template <int OP>
-__global__ void __launch_bounds__(256) k_recode_size_tile(RecodeArgs a) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-  const Table t = stage_table<OP>(a, smem);
-  uint8_t* lds_in = reinterpret_cast<uint8_t*>(smem) + shared_bytes<OP>() + (size_t)wv * a.cap;
-  cstile::walk_staged_tiles<cstile::Oversize::kFromMemory>(a.in, a.rows_per_tile, a.ntiles, lds_in, a.cap, wv, lane,
-                                                           [&](const cstile::RowTile& cur, const uint8_t* p) {
-    if (cur.in_tile) size_row<OP>(a, t, cur.r0 + lane, p, cur.n, cur.live);
-  });
-}
-
-template <int OP>
-__global__ void __launch_bounds__(256) k_recode_write_tile(RecodeArgs a) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-  const Table t = stage_table<OP>(a, smem);
-  uint8_t* lds_in = reinterpret_cast<uint8_t*>(smem) + shared_bytes<OP>() + (size_t)wv * (a.cap + a.out_cap);
-  uint8_t* lds_out = lds_in + a.cap;
-  cstile::walk_staged_tiles<cstile::Oversize::kFromMemory>(a.in, a.rows_per_tile, a.ntiles, lds_in, a.cap, wv, lane,
-                                                           [&](const cstile::RowTile& cur, const uint8_t* p) {
-    // the tile's output rows [ob, oe): lanes beyond its rows repeat the end
-    const long long oo0 = a.out_off[cur.r0 + min(lane, cur.nrows)];
-    const long long oo1 = a.out_off[cur.r0 + min(lane + 1, cur.nrows)];
-    const long long ob = cstile::rl64(oo0, 0), oe = cstile::rl64(oo1, 63);
-    if (oe - ob + 16 > a.out_cap) {  // (wave-uniform) beyond the out-tile: every row to memory by its lane
-      if (cur.live) row_write<OP>(a, t, p, cur.n, a.out_chars + oo0);
-      return;
-    }
-    if (cur.live) row_write<OP>(a, t, p, cur.n, lds_out + (int)(oo0 - ob));
-    cstile::wave_lds_fence();
-    cstile::wave_flush_shift(a.out_chars + ob, (int)(oe - ob), lds_out, lane);
-  });
-}
-
-// ---- host ------------------------------------------------------------------------------------------------------------------
-template <int OP>
-cs_column* run_recode(const cs_column* col, RecodeArgs a, hipStream_t s) {
-  const int64_t rows = col->rows;
-  if (rows == 0) return make_all_null(0, s);
-  Built b(col, s);
-  cs_column* const o = b.col.get();
-  a.in = view_of(col);
-  // the tile plan: R rows whose bytes fit the prefetch (a column with a few longer tiles still gets it: those tiles go from
-  // memory); the staging buffers of four waves and the out-tiles must fit the LDS
-  StagedTiles t;
-  if (!cs::cfg("CS_RECODE_ROWWISE")) t = plan_staged_tiles(col, cstile::kStageSlack, true, {1, 0, 100 * 1024}, s);
-  const bool tile = t.R != 0;
-  a.rows_per_tile = t.R;
-  a.cap = t.cap;
-  a.ntiles = t.ntiles;
-  const unsigned row_grid = std::min(blocks_for(rows), 65536u);
-  Buf lens = dev_alloc(sizeof(int32_t) * (size_t)rows, s);
-  Buf flag = dev_alloc(sizeof(unsigned), s);
-  CS_HIP(hipMemsetAsync(flag->p, 0, sizeof(unsigned), s));
-  a.lens = ptr<int32_t>(lens);
-  a.overflow = ptr<unsigned>(flag);
-  {
-    ProfScope ps("k_recode_size", s);
-    if (tile) {
-      launch_resident(&k_recode_size_tile<OP>, shared_bytes<OP>() + t.lds, t.grid, s, a);
-    } else {
-      hipLaunchKernelGGL(k_recode_size_rows<OP>, dim3(row_grid), dim3(kBlock), 0, s, a);
-      CS_HIP(hipGetLastError());
-    }
-  }
-  b.scan(ptr<int32_t>(lens));
-  unsigned over = 0;
-  CS_HIP(hipMemcpy(&over, flag->p, sizeof(unsigned), hipMemcpyDeviceToHost));
-  if (over) fail(CS_ERR_RANGE, "nvstrings: an output row would reach 2^31 bytes");
-  a.out_chars = b.alloc_chars();
-  a.out_off = b.off;
-  {
-    ProfScope ps("k_recode_write", s);
-    if (tile) {
-      // the out-tile: the widest 64-row span of the output (an R-row tile lies inside one), capped
-      const int64_t span = o->max_span64 >= 0 ? o->max_span64 : max_span64(o, s);
-      a.out_cap = (int)((std::min<int64_t>(span, kOutCapMax) + 16 + 15) & ~(int64_t)15);
-      launch_resident(&k_recode_write_tile<OP>, shared_bytes<OP>() + t.lds + (size_t)a.out_cap * 4, t.grid, s, a);
-    } else {
-      hipLaunchKernelGGL(k_recode_write_rows<OP>, dim3(row_grid), dim3(kBlock), 0, s, a);
-      CS_HIP(hipGetLastError());
-    }
-  }
-  note_route(tile ? "tile" : "rows");
-  return b.col.release();
+template <class Op>
+cs_column* run_recode(const cs_column* col, const Op& op, hipStream_t s) {
+  if (col->rows == 0) return make_all_null(0, s);
+  return cssized::run_sized(col, op, "CS_RECODE_ROWWISE", "k_recode_size", "k_recode_write", s);
 }
 
 // ---- fillna ----------------------------------------------------------------------------------------------------------------
@@ -237,34 +105,20 @@ cs_column* run_fillna(const cs_column* col, const cs_column* repl, const char* s
   return b.col.release();
 }
 
-template <class F>
-int recode_entry(const cs_column* col, cs_column** out, F&& f) {
-  return guard([&] {
-    if (!col || !out) fail(CS_ERR_INVALID_ARG, "null column or output");
-    *out = nullptr;
-    require_device();
-    *out = f();
-  });
-}
-
 }  // namespace
 
 extern "C" {
 
 int cs_url_encode(const cs_column* col, cs_stream stream, cs_column** out) {
-  return recode_entry(col, out, [&] {
-    RecodeArgs a{};
-    a.safe = csrecode::url_safe_mask();
-    return run_recode<csrecode::OP_URL_ENCODE>(col, a, S(stream));
-  });
+  return column_entry(col, out, [&] { return run_recode(col, UrlEncode{csrecode::url_safe_mask()}, S(stream)); });
 }
 
 int cs_url_decode(const cs_column* col, cs_stream stream, cs_column** out) {
-  return recode_entry(col, out, [&] { return run_recode<csrecode::OP_URL_DECODE>(col, RecodeArgs{}, S(stream)); });
+  return column_entry(col, out, [&] { return run_recode(col, UrlDecode{}, S(stream)); });
 }
 
 int cs_translate(const cs_column* col, const uint32_t* from, const uint32_t* to, int n, cs_stream stream, cs_column** out) {
-  return recode_entry(col, out, [&] {
+  return column_entry(col, out, [&] {
     if (n < 0 || (n > 0 && (!from || !to))) fail(CS_ERR_INVALID_ARG, "nvstrings::translate: the table is missing");
     hipStream_t s = S(stream);
     csrecode::HostTable h;
@@ -276,26 +130,26 @@ int cs_translate(const cs_column* col, const uint32_t* from, const uint32_t* to,
     host.insert(host.end(), h.vals.begin(), h.vals.end());
     Buf d = dev_alloc(host.size() * sizeof(uint32_t), s);
     CS_HIP(hipMemcpyAsync(d->p, host.data(), host.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    RecodeArgs a{};
+    Translate a{};
     a.tab.ascii = ptr<const uint32_t>(d);
     a.tab.keys = a.tab.ascii + csrecode::kAsciiKeys;
     a.tab.vals = a.tab.keys + nk;
     a.tab.nkeys = (int)nk;
-    cs_column* c = run_recode<csrecode::OP_TRANSLATE>(col, a, s);
+    cs_column* c = run_recode(col, a, s);
     CS_HIP(hipStreamSynchronize(s));  // (the table is done with)
     return c;
   });
 }
 
 int cs_fillna(const cs_column* col, const char* str, cs_stream stream, cs_column** out) {
-  return recode_entry(col, out, [&] {
+  return column_entry(col, out, [&] {
     if (!str) fail(CS_ERR_INVALID_ARG, "nvstrings::fillna parameter cannot be null");
     return run_fillna(col, nullptr, str, S(stream));
   });
 }
 
 int cs_fillna_column(const cs_column* col, const cs_column* repl, cs_stream stream, cs_column** out) {
-  return recode_entry(col, out, [&] {
+  return column_entry(col, out, [&] {
     if (!repl) fail(CS_ERR_INVALID_ARG, "nvstrings::fillna parameter cannot be null");
     if (repl->rows != col->rows) fail(CS_ERR_INVALID_ARG, "nvstrings::fillna parameter must have the same number of strings");
     return run_fillna(col, repl, nullptr, S(stream));

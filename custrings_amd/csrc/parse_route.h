@@ -29,10 +29,7 @@ namespace csparse {
 
 using cs::ColView;
 
-template <class P, class = void>
-struct SharedBytes : std::integral_constant<int, 0> {};
-template <class P>
-struct SharedBytes<P, std::void_t<decltype(P::kSharedBytes)>> : std::integral_constant<int, (P::kSharedBytes + 15) & ~15> {};
+using cstile::SharedBytes;
 template <class P, class = void>
 struct Counted : std::true_type {};
 template <class P>

@@ -15,6 +15,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "device_utils.h"
 
 // per-phase cycle accounting of the persistent kernels (instrumented builds only: make prof)
@@ -435,25 +437,42 @@ struct RowTileWalk {
 // cur.in_tile / cur.live itself, and a wave-level step behind the rows (with a fence of its own in front) is part of it.
 // A tile beyond the staging buffer either cannot happen (the host's plan fits every tile), or is not staged and the
 // body gets the row in memory.
+// `loads(cur, unstaged)` runs per tile in front of the staging and of the next tile's loads: what the body needs from
+// memory beyond the rows (the tile's output offsets) is then in flight ahead of them, not behind.  What it returns is
+// handed to the body as a third argument; it may set `unstaged` (only when the body takes a row from memory, kFromMemory).
 enum class Oversize { kHostChecked, kFromMemory };
 constexpr int kStageSlack = 48;  // what the host adds to the widest tile for `cap`: a body may read that far past its row
-template <Oversize OV, class Col, class Body>
+template <Oversize OV, class Col, class Loads, class Body>
 __device__ __forceinline__ void walk_staged_tiles(const Col& in, int rows_per_tile, long long ntiles, uint8_t* lds_in, int cap, int wv,
-                                                  int lane, Body&& body) {
+                                                  int lane, Loads&& loads, Body&& body) {
   RowTileWalk walk(in, rows_per_tile, ntiles, wv, lane);
   if (walk.done()) return;
   for (;;) {
     const RowTile cur = walk.current();
     const long long want64 = cur.g1 - cur.g0 + cur.lead;
-    const bool oversize = OV == Oversize::kFromMemory && want64 + kStageSlack > cap;  // (a long row among short ones)
+    bool oversize = OV == Oversize::kFromMemory && want64 + kStageSlack > cap;  // (a long row among short ones)
+    const auto loaded = loads(cur, oversize);
     stage_chars(lds_in, oversize ? 0 : (int)want64, lane, walk.pf);
     const bool more = walk.advance();  // the next tile's bytes travel while this one is worked on
     wave_lds_fence();
-    body(cur, oversize ? in.chars + (cur.g0 + cur.rbeg) : lds_in + cur.lead + cur.rbeg);
+    body(cur, oversize ? in.chars + (cur.g0 + cur.rbeg) : lds_in + cur.lead + cur.rbeg, loaded);
     wave_lds_fence();  // (the LDS is restaged next round)
     if (!more) break;
   }
 }
+// the same with nothing more to load per tile: body(cur, p)
+template <Oversize OV, class Col, class Body>
+__device__ __forceinline__ void walk_staged_tiles(const Col& in, int rows_per_tile, long long ntiles, uint8_t* lds_in, int cap, int wv,
+                                                  int lane, Body&& body) {
+  walk_staged_tiles<OV>(in, rows_per_tile, ntiles, lds_in, cap, wv, lane, [](const RowTile&, bool&) { return 0; },
+                        [&](const RowTile& cur, const uint8_t* p, int) { body(cur, p); });
+}
+// The LDS region a per-row functor P of such a kernel may declare (`static constexpr int kSharedBytes`): filled once per
+// workgroup by P's `stage(lds, tid)` in front of the waves' staging buffers (parse_route.h, sized_route.h); 0 without one.
+template <class P, class = void>
+struct SharedBytes : std::integral_constant<int, 0> {};
+template <class P>
+struct SharedBytes<P, std::void_t<decltype(P::kSharedBytes)>> : std::integral_constant<int, (P::kSharedBytes + 15) & ~15> {};
 
 // Decoupled look-back in two halves so that independent work (assembling the output
 // rows in LDS) runs between publishing this sub-tile's aggregate and needing the

@@ -255,6 +255,75 @@ def test_against_harness(generated, harness, monkeypatch, k, rowwise):
             assert np.array_equal(goffs, ioffs)
 
 
+# ---- a staged tile whose output exceeds the out-tile ----------------------------------------------------------------------------
+# the host's tile plan, restated (cs_core.hip plan_row_tiles / plan_staged_tiles, sized_route.h write_sized)
+PF_BYTES, STAGE_SLACK, OUT_TILE, WAVE_ROW = 6144, 48, 16 * 1024, 256
+
+
+def tile_plan(rows, out_rows):
+    """-> per tile (first row, end row, its input is staged wherever the chars begin, its output bytes).  The plan takes the
+    largest R of 64 / 32 / 16 whose widest R-row span + 32 fits the prefetch, else 64-row tiles sized for all but a few; a
+    tile's input is staged when its span, up to 15 bytes of lead and the slack fit the wave's buffer; pad then assembles
+    the tile in the LDS out-tile unless its output exceeds OUT_TILE (such a tile goes from memory to memory)."""
+    def offsets(rr):
+        return np.concatenate([[0], np.cumsum([0 if x is None else len(x) for x in rr])])
+
+    offs, oo, n = offsets(rows), offsets(out_rows), len(rows)
+    R, span = 64, PF_BYTES - 64
+    for cand in (64, 32, 16):
+        widest = max(int(offs[min(r0 + cand, n)] - offs[r0]) for r0 in range(0, n, cand))
+        if widest + 32 <= PF_BYTES:
+            R, span = cand, widest
+            break
+    cap = (span + STAGE_SLACK + 15) & ~15
+    return [(r0, min(r0 + R, n), int(offs[min(r0 + R, n)] - offs[r0]) + 15 + STAGE_SLACK <= cap, int(oo[min(r0 + R, n)] - oo[r0]))
+            for r0 in range(0, n, R)]
+
+
+LONG_ROW = 129  # in the last tile (rows 128 .. 133), beside a null row and an empty one
+GROW_SETTINGS = {
+    # op: (harness arguments, the model's, the call, the long row's tile leaves through the LDS out-tile)
+    "repeat": (dict(reps=4), [4], lambda g: g.repeat(4), False),  # 22 KB: from memory, the long row by the whole wave
+    "ljust": (dict(width=300), [300], lambda g: g.ljust(300), True),  # (the 64-row tiles do not fit: rows of 300 bytes by the wave)
+    "slice": (dict(start=1, stop=20, step=3), [1, 20, 3], lambda g: g.slice(1, 20, 3), True),  # strided: never by the wave
+    "slice_replace": (dict(repl="_é_".encode(), start=2, stop=5), ["_é_", 2, 5], lambda g: g.slice_replace(2, 5, "_é_"), True),
+    "wrap": (dict(width=6), [6], lambda g: g.wrap(6), True),
+}
+
+
+@pytest.fixture(scope="module")
+def grow(harness):
+    """-> (rows, device column, {op: the harness's rows, which are the model's})"""
+    rows = m.gen_rows(134, seed=31, maxlen=6)
+    rows[40] = "abc dé ".encode() * 700  # 5600 bytes: its tile is the column's widest, so that the tile under test is staged
+    rows[128:] = [b"ab", "ab é€ 中-😀\t7 ".encode() * 275, None, b"", "é x".encode(), b"-7\tz"]  # (whatever its first byte's address)
+    assert len(rows) == 134 and len(rows[LONG_ROW]) == 5500
+    want = {}
+    for op, (kw, args, _, through_lds) in GROW_SETTINGS.items():
+        want[op] = harness.run(op, rows, **kw)
+        assert want[op] == m.apply_column(op, rows, args), op
+        plan = tile_plan(rows, want[op])
+        r0, r1, staged, out_span = plan[-1]
+        assert (r0, r1) == (128, 134) and staged and (out_span <= OUT_TILE) == through_lds, (op, plan[-1])
+        if op == "ljust":  # the full tiles spill, and every row of theirs goes by the wave
+            assert all(o > OUT_TILE for _, _, _, o in plan[:-1]) and all(r is None or len(r) > WAVE_ROW for r in want[op][:128])
+    return rows, column(rows), want
+
+
+@pytest.mark.parametrize("rowwise", [False, True], ids=["tile", "rows"])
+@pytest.mark.parametrize("op", list(GROW_SETTINGS))
+def test_staged_tile_with_output_beyond_the_out_tile(grow, monkeypatch, op, rowwise):
+    if rowwise:
+        monkeypatch.setenv("CS_PAD_ROWWISE", "1")
+    rows, g, want = grow
+    out = GROW_SETTINGS[op][2](g)
+    assert _route() == ("rows" if rowwise else "tile")
+    gchars, goffs, gvalid = out._export64()
+    assert np.array_equal(np.unpackbits(gvalid, bitorder="little")[: len(rows)].astype(bool), [r is not None for r in rows])
+    assert goffs.tolist() == np.concatenate([[0], np.cumsum([0 if r is None else len(r) for r in want[op]])]).tolist()
+    assert gchars.tobytes() == b"".join(r for r in want[op] if r is not None)
+
+
 def test_slice_from_against_harness(generated, harness, monkeypatch):
     import torch
 
