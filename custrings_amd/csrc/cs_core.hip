@@ -1788,6 +1788,53 @@ int cs_debug_spin(int blocks, int lds_bytes, int milliseconds, cs_stream stream)
     CS_HIP(hipGetLastError());
   });
 }
+// The lengths-to-offsets scans by themselves, one host function per route, nothing changed in any of them (tests/test_gpu_scan.py).
+int cs_debug_offsets_from_lengths(const int32_t* lens, int64_t n, int segs, int route, int64_t* offsets, uint8_t* validity, int64_t* out,
+                                  cs_stream stream) {
+  return guard([&] {
+    if (!lens || !offsets || !out || n < 0 || route < 0 || route > 4 || segs < 1 || (segs != 1 && route != 4) || (validity && route != 1))
+      fail(CS_ERR_INVALID_ARG, "debug_offsets_from_lengths: bad arguments");
+    require_device();
+    hipStream_t s = S(stream);
+    LenMeta meta;
+    switch (route) {
+      case 0:
+        if (n == 0) out[0] = offsets_from_lengths(lens, n, offsets, s, nullptr, &meta);
+        else out[0] = offsets_by_chunks(lens, n, offsets, nullptr, s, &meta);
+        break;
+      case 1: {
+        Buf v;
+        out[0] = offsets_and_validity_from_lengths(lens, n, offsets, &v, s, &meta);
+        if (validity && n) CS_HIP(hipMemcpyAsync(validity, v->p, validity_bytes(n), hipMemcpyDeviceToDevice, s));
+        break;
+      }
+      case 2:
+        if (n == 0) out[0] = offsets_from_lengths(lens, n, offsets, s, nullptr, &meta);
+        else out[0] = offsets_by_workgroups(lens, n, offsets, s, nullptr, &meta);
+        break;
+      case 3:
+        offsets_from_lengths_async(lens, n, offsets, s);
+        CS_HIP(hipMemcpyAsync(out, offsets + n, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        break;
+      case 4: {
+        std::vector<int64_t> totals(segs), largest(segs);
+        offsets_from_lengths_segmented(lens, n, segs, offsets, totals.data(), s, largest.data());
+        for (int k = 0; k < segs; ++k) {
+          out[3 * k] = totals[k];
+          out[3 * k + 1] = largest[k];
+          out[3 * k + 2] = -1;
+        }
+        break;
+      }
+    }
+    CS_HIP(hipGetLastError());
+    CS_HIP(hipStreamSynchronize(s));
+    if (route != 4) {
+      out[1] = meta.max_row;
+      out[2] = meta.max_span64;
+    }
+  });
+}
 int cs_prof_get(const char* kernel, double* total_ms, int64_t* launches) {
   return guard([&] {
     std::lock_guard<std::mutex> lk(g_mu);

@@ -755,6 +755,16 @@ int cs_numcat_copy(const cs_numcat* cat, cs_stream stream, cs_numcat** out);
  * the radix sort (the reference's algorithm -- sort every row -- on this project's sort).  Nothing is returned; the call
  * waits for the sort.  UNSUPPORTED: a cs_debug_* entry point is not part of the interface a caller may rely on. */
 int cs_debug_numcat_sort_rows(const void* items, int64_t n, cs_numtype type, int on_device, cs_stream stream);
+/* For the tests of the scan under every output column: runs ONE of the library's lengths-to-offsets routes over `lens`
+ * (device, segs * n int32, negative = null row -> 0 bytes) into `offsets` (device, segs * (n + 1) int64), and waits.
+ * route 0: the chunk scan with metadata; 1: the same with the validity mask of the fused pass, copied to `validity`
+ * (device, (n + 63) / 64 * 8 bytes; may be null, must be null on the other routes); 2: the workgroup scan (what
+ * CS_SCAN_BY_WORKGROUPS selects); 3: the scan that reads nothing back; 4: the segmented scan (the only route with segs > 1).
+ * out (host, 3 per segment): total bytes, longest row, largest 64-row span; -1 where the route does not report the number.
+ * Routes 0 and 2 call the two scans themselves: which of them offsets_from_lengths picks (its reading of CS_SCAN_BY_WORKGROUPS)
+ * is not what this entry point covers.  No chars are allocated.  UNSUPPORTED, as every cs_debug_* entry point. */
+int cs_debug_offsets_from_lengths(const int32_t* lens, int64_t n, int segs, int route, int64_t* offsets, uint8_t* validity, int64_t* out,
+                                  cs_stream stream);
 
 #ifdef __cplusplus
 }

@@ -56,3 +56,24 @@ def compile_re(pat):
     from custrings_amd import nvstrings
 
     return nvstrings._compile(pat)
+
+
+def cached_meta(g):
+    """What the column has cached: [largest 64-row span, longest row, ...], -1 = not known."""
+    L = lib()
+    out = (C.c_int64 * 4)()
+    L.check(L.lib.cs_column_cached_meta(g.m_cptr, out))
+    return list(out)
+
+
+def measured_meta(g):
+    """(largest 64-row span, longest row) from the exported offsets."""
+    _, offs, _ = g._export64()
+    offs = np.asarray(offs, dtype=np.int64)
+    rows = len(offs) - 1
+    if rows == 0:
+        return 0, 0
+    lens = np.diff(offs)
+    starts = np.arange(0, rows, 64)
+    ends = np.minimum(starts + 64, rows)
+    return int((offs[ends] - offs[starts]).max()), int(lens.max())

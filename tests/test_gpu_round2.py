@@ -53,6 +53,35 @@ def test_gpu_array_ops(gpu_engine, oracle_engine, seed):
     assert g.scalar_scatter(s, None, p2[:40]) == o.scalar_scatter(s, None, p2[:40])
 
 
+@pytest.mark.parametrize("n", [4095, 4096, 4097, 20_000])
+def test_gpu_order_and_sort_keep_equal_strings_in_index_order(gpu_engine, n):
+    """Around one radix tile of keys and at several: rows drawn from 300 distinct strings (prefixes of one another, empty,
+    multi-byte) plus nulls, so that most rows have equals.  Against Python's stable sort on (null class, [byte length],
+    [bytes]), reversed as a whole for descending (which keeps equal rows in index order too): NVStrings.h "sort" and "order"
+    place nulls by `nullfirst` whatever the direction."""
+    rnd = random.Random(n)
+    pool = {"", "a", "ab", "abc", "é", "éa", "z" * 40}
+    while len(pool) < 300:
+        pool.add("".join(rnd.choice(["a", "b", "c", "Z", " ", "0", "é", "ß", "😀"]) for _ in range(rnd.randint(1, 12))))
+    pool = sorted(pool)
+    s = [None if rnd.random() < 0.05 else rnd.choice(pool) for _ in range(n)]
+    raw = [None if x is None else x.encode("utf8") for x in s]
+    col = gpu_engine.col(s)
+    for stype in (0, 1, 2, 3):
+        for asc in (True, False):
+            for nf in (True, False):
+                null_class = 0 if nf == asc else 1
+
+                def key(i):
+                    if raw[i] is None:
+                        return (null_class, 0, b"")
+                    return (1 - null_class, len(raw[i]) if stype & 1 else 0, raw[i] if stype & 2 else b"")
+
+                want = sorted(range(n), key=key, reverse=not asc)
+                assert col.order(stype, asc, nf) == want, (stype, asc, nf)
+                assert col.sort(stype, asc, nf).to_host() == [s[i] for i in want], (stype, asc, nf)
+
+
 def test_gpu_gather_mask_and_from_index(gpu_engine):
     from custrings_amd import _lib, nvstrings
     import ctypes as C

@@ -10,30 +10,11 @@ import pytest
 import cpulibs
 import engines
 import gpuutil
+from gpuutil import cached_meta, measured_meta
 
 pytestmark = pytest.mark.gpu
 
 IPV4 = r"\d+\.\d+\.\d+\.\d+"
-
-
-def cached_meta(g):
-    L = gpuutil.lib()
-    out = (C.c_int64 * 4)()
-    L.check(L.lib.cs_column_cached_meta(g.m_cptr, out))
-    return list(out)
-
-
-def measured_meta(g):
-    """(largest 64-row span, longest row) from the exported offsets."""
-    _, offs, _ = g._export64()
-    offs = np.asarray(offs, dtype=np.int64)
-    rows = len(offs) - 1
-    if rows == 0:
-        return 0, 0
-    lens = np.diff(offs)
-    starts = np.arange(0, rows, 64)
-    ends = np.minimum(starts + 64, rows)
-    return int((offs[ends] - offs[starts]).max()), int(lens.max())
 
 
 @pytest.mark.parametrize("kind,rows", [(3, 70_001), (2, 50_000), (5, 30_000)])
