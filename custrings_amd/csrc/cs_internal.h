@@ -296,6 +296,28 @@ int virtual_piece_bytes();
 int64_t virtual_reduce_u8(const VirtualRows* vr, const uint8_t* piece_res, int64_t rows, uint8_t* out, hipStream_t s);
 int64_t virtual_reduce_i32(const VirtualRows* vr, const int32_t* piece_res, int64_t rows, int32_t* out, hipStream_t s);
 cs_column* virtual_rows_to_rows(const cs_column* col, const VirtualRows* vr, std::unique_ptr<cs_column> pieces_out, hipStream_t s);
+// cs_regex.hip: one replace_re call, all of its parameters in sight.  cs_replace_re fills the first six; cs_replace adds its
+// needle and cs_replace_with_backrefs its template, and both ask for the single pass only: their own kernels are the
+// fallback, so replace_re_column throws where the single pass does not apply or gives up.
+struct ReplaceCall {
+  const cs_column* col;
+  const cs_regex* re;
+  const char* repl;  // the replacement text (host), `rb` bytes and a NUL
+  int rb;
+  int maxrepl;  // replacements per row at most; negative: all
+  hipStream_t s;
+  // the needle itself when it has at most eight bytes and no border (no proper prefix that is also a suffix: occurrences
+  // cannot overlap), first byte lowest: the stream kernel then finds the matches by byte comparison; literal_len 0: none
+  unsigned long long literal = 0;
+  int literal_len = 0;
+  // the template (a csvm::BackrefTemplate): host copy (sizing: how much a match can grow), device copy, bytes of its text;
+  // null: plain replace_re
+  const void* tmpl_host = nullptr;
+  const void* tmpl_dev = nullptr;
+  int tmpl_text_bytes = 0;
+  bool single_pass_only = false;
+};
+cs_column* replace_re_column(const ReplaceCall& c);  // the new column (the caller's), or throws
 // cs_radix.hip: stable LSD radix sort of n (64-bit key, 32-bit item) pairs by key, ascending, in place (synchronises `s`)
 void radix_sort_pairs64(uint64_t* keys, int32_t* items, int64_t n, hipStream_t s);
 // cs_category.hip: keys = sorted unique rows (null first), values[r] = index of row r's key

@@ -46,17 +46,6 @@ struct cs_regex {
 namespace cs {
 bool replace_class_runs(const cs_column* col, const int32_t* d_bits, const std::vector<int32_t>& bits, const char* repl, int rb, hipStream_t s, cs_column** out);
 bool count_class_runs(const cs_column* col, const int32_t* d_bits, const std::vector<int32_t>& bits, hipStream_t s, int32_t* results, int64_t* hits);
-thread_local int g_replace_plain_only = 0;  // set by cs_replace around its call of cs_replace_re: single-pass kernel or nothing
-// cs_replace also leaves the needle itself here when it has at most eight bytes and no border (no proper prefix that is
-// also a suffix: occurrences cannot overlap): the stream kernel then finds the matches by byte comparison, all bytes of
-// the sub-tile at once, instead of walking the DFA
-thread_local unsigned long long g_replace_literal = 0;
-thread_local int g_replace_literal_len = 0;
-// cs_replace_with_backrefs hands its template to the same single-pass kernel (the device copy of the template struct);
-// nullptr: plain replace_re
-thread_local const void* g_backrefs_dev = nullptr;
-thread_local int g_backrefs_text_bytes = 0;
-thread_local const void* g_backrefs_host = nullptr;  // the same template, host copy (sizing: how much a match can grow)
 }
 
 namespace {
@@ -3315,6 +3304,669 @@ int cs_count_re(const cs_column* col, const cs_regex* re, int32_t* results, int 
   });
 }
 
+}  // extern "C"
+
+// ---- replace_re: the host route ---------------------------------------------------------------------------------------
+// cs::replace_re_column runs a cs::ReplaceCall (cs_internal.h) as the sequence it is -- the column's pieces, class runs,
+// the single pass, the two-pass kernels -- each step a function that returns the column, or nullptr when it declines.
+// The single pass in turn: its SHAPE (what is fixed for the call), its FORM (which variant of k_tdfa_replace_stream runs),
+// per attempt its SIZING (out tile, output buffer, LDS layout -- the second, roomier attempt differs only there), the
+// KERNEL (replace_stream_kernel: the one place that names the instantiations) and the LAUNCH.
+// Several questions below launch kernels or wait on the stream the first time they are asked of a column
+// (sample_has_high_bytes, odd_rows_few, odd_rows, candidate_share, bits_route, max_span64, few_spans64_over, choose_tile):
+// the order of the `&&` chains decides whether they are asked at all.  Keep it.
+namespace {
+
+struct ReplaceRun {  // a call and what its steps share
+  const cs::ReplaceCall& c;
+  cs_regex* re;
+  bool tdfa, wide;  // the tagged DFA runs the program; ... with five to eight live threads (the two-pass kernels on TdfaWide)
+  TPlan tp;         // (tdfa || wide)
+  Plan pl;          // (neither: the list simulator)
+  Buf d_repl;       // the replacement text on the device
+  RowSrc src;
+};
+
+// rows beyond the 96-bit masks, white space a safe cut for this program: the pieces' replace_re is the rows' (cs_virtual.hip)
+cs_column* replace_on_pieces(const ReplaceRun& r) {
+  const cs::ReplaceCall& c = r.c;
+  if (c.tmpl_dev || c.single_pass_only || c.maxrepl >= 0 || !r.tdfa || cs::cfg("CS_CLASS_RUNS_ALWAYS")) return nullptr;
+  const VirtualRows* vr = pieces_for(c.col, r.re, c.s, true);
+  if (!vr) return nullptr;
+  cs::ReplaceCall pieces = c;
+  pieces.col = vr->col.get();
+  std::unique_ptr<cs_column> po(cs::replace_re_column(pieces));
+  note_route_pieces();
+  return virtual_rows_to_rows(c.col, vr, std::move(po), c.s);
+}
+
+// One character class, once or in a `+` loop, on a column the 96-bit-mask forms do not take -- rows beyond 93 bytes,
+// tiles of fewer than 64 rows, non-ASCII text -- and whose candidates are everywhere: byte-parallel stream compaction
+// (cs_runs.hip; BASELINE.json C5: replace_re([aeiou]+) on 40-150-byte rows, 82.8 ms on the long-row automaton forms).
+cs_column* replace_by_class_runs(const ReplaceRun& r) {
+  const cs::ReplaceCall& c = r.c;
+  const cs_column* col = c.col;
+  const cs_regex* re = r.re;
+  if (c.tmpl_dev || c.single_pass_only || c.maxrepl >= 0 || col->rows <= 0 || re->bits.empty() || !(re->bits[2] & (csbits::F_BYTE_CLASS | csbits::F_FLAG_CLASS)) || !re->d_bits)
+    return nullptr;
+  const TileChoice tc0 = choose_tile(col, c.s, true);
+  const bool masks_form = tc0.R == 64 && !tc0.lng && (!sample_has_high_bytes(col, c.s) || odd_rows_few(col, c.s));  // (few rows with such bytes: holes)
+  // (a class with builtins -- `\w+` -- sends every tile with a byte >= 0x80 row by row: worth it against the automaton's
+  // long-row and dense forms -- `\w+` on the C5 column 97.7 -> 11.2 ms, on C2 16.2 -> 5.1 --, not against the chain
+  // arithmetic where that runs: `\s+` on C2 4.4 there, 6.7 here)
+  const bool chain_there = !re->tdfa.empty() && ((re->tdfa[30] >> 16) & 15) != 0 && tc0.R == 64 && !tc0.lng;
+  const bool flag_class = (re->bits[2] & csbits::F_BYTE_CLASS) == 0;
+  const bool wanted = cs::cfg("CS_CLASS_RUNS_ALWAYS") || (!masks_form && !(flag_class && chain_there) && candidate_share(re, col, c.s) >= 0.05);
+  cs_column* out = nullptr;
+  if (!wanted || !replace_class_runs(col, ptr<const int32_t>(re->d_bits), re->bits, c.repl, c.rb, c.s, &out)) return nullptr;
+  note_route("runs");
+  return out;
+}
+
+// What is fixed for a call's single pass, whichever form runs and however many attempts it takes.
+struct ReplaceShape {
+  // A match is at least `minlen` bytes, so a row grows by at most `growth` = rb - minlen bytes per match; no growth means
+  // "never grows" and the rows are rewritten in place.  A growing replacement is provisioned for kMaxRec matches per row
+  // first (or, `roomy_first`, for up to the worst case: patterns of one or two bytes tend to match often); a launch that
+  // runs out of room says so in its error word and is repeated once with the roomier sizing.
+  int minlen, minlen_p, growth;
+  // (a pattern that matches the empty string inserts at most one replacement per character and one at the row's end:
+  // short replacements are provisioned for exactly that -- `x*` -> '-' doubles the column -- and stay on the single pass;
+  // with a longer one the pattern is unbounded -- the zero-length repeat rule -- and takes the two-pass kernels)
+  bool empties;
+  // (programs of five to eight threads: the stream kernel's WIDE forms -- tables in LDS, replacements of up to 16 bytes)
+  bool wide_stream;
+  TileChoice tc;
+  // (the column's largest 64-row span does not fit, all but a few do: buffers for those, the kernel handles the rest)
+  bool outliers;
+  int cap;  // bytes of the in tile
+  // a column whose sample holds a few bytes >= 0x80: the unit forms run as on plain ASCII, the rows that hold such bytes are
+  // sized beforehand and written afterwards, a thread a row (StreamArgs::hole_mask) -- replace_re of the gtest pattern on the C5
+  // column's pieces: 34 ms when a third of the sub-tiles went to the row-by-row scan for the sake of one row each
+  bool holes_ok;
+  bool roomy_first;
+  int64_t sized_total = -1, sized_tilemax = 0;  // matches in the column / in its busiest tile, when they were counted first
+};
+
+// A growing replacement for a pattern of one or two bytes (`\d+` -> '<number>', `\d` -> '##'): provisioned for the worst
+// case the out tile is three times the in tile -- two workgroups a CU -- and the output twice the column (18 ms on the
+// C3 column where `\d+` -> '#' takes 5.9).  count_re first (2.4 ms) says how many matches the column and its busiest
+// tile hold: the out tile and the output are sized exactly: 17.9 -> 12.1 ms.
+// (where the worst case is within three times the in tile anyway -- `\d` -> '##' -- the count only costs: 15.6 -> 17.9 ms)
+void count_matches_first(const ReplaceRun& r, ReplaceShape* sh) {
+  const cs_column* col = r.c.col;
+  const hipStream_t s = r.c.s;
+  Buf counts = dev_alloc(sizeof(int32_t) * (size_t)col->rows, s), stats = dev_alloc(16, s);
+  scan<2>(col, r.re, nullptr, ptr<int32_t>(counts), 1, s, nullptr, "k_count_re");
+  CS_HIP(hipMemsetAsync(stats->p, 0, 16, s));
+  hipLaunchKernelGGL(k_match_stats, dim3(1024), dim3(256), 0, s, ptr<const int32_t>(counts), col->rows, sh->tc.R, ptr<unsigned long long>(stats),
+                     reinterpret_cast<unsigned*>(ptr<unsigned long long>(stats) + 1));
+  CS_HIP(hipGetLastError());
+  unsigned long long* h = (unsigned long long*)pinned_scratch(16);
+  CS_HIP(hipMemcpyAsync(h, stats->p, 16, hipMemcpyDeviceToHost, s));
+  CS_HIP(hipStreamSynchronize(s));
+  sh->sized_total = (int64_t)h[0];
+  sh->sized_tilemax = (int64_t)(unsigned)h[1];
+  note_route("");
+}
+
+// The shape of the call; false: no single pass for it.
+bool replace_shape(const ReplaceRun& r, ReplaceShape* shape) {
+  const cs::ReplaceCall& c = r.c;
+  const cs_column* col = c.col;
+  const cs_regex* re = r.re;
+  const hipStream_t s = c.s;
+  const int rb = c.rb;
+  ReplaceShape& sh = *shape;
+  const int minlen = sh.minlen = (r.tdfa || r.wide) ? re->tdfa[13] : 0;
+  sh.minlen_p = std::max(minlen, 1);
+  sh.growth = rb > minlen ? rb - minlen : 0;
+  sh.empties = minlen == 0 && sh.growth > 0;
+  const bool bounded = sh.growth == 0 || minlen >= 1 || rb <= 8;  // (longer ones: the out tile of 1 + rb times the input does not fit the LDS)
+  sh.wide_stream = r.wide && r.tp.d.in_lds && rb <= 16 && !c.tmpl_dev && !cs::cfg("CS_WIDE_TWO_PASS");
+  if (!(r.tdfa || sh.wide_stream) || !bounded || cs::cfg("CS_REGEX_TWO_PASS")) return false;
+  sh.tc = choose_tile(col, s, !cs::cfg("CS_NO_SMALL_TILES"));
+  constexpr int64_t kOutlierSpan = cstile::kPfBytes - 176;  // (its capacity is kPfBytes)
+  sh.outliers = !sh.tc.R && r.tdfa && r.tp.d.in_lds && rb <= 16 && !c.tmpl_dev && !cs::cfg("CS_NO_OUTLIER_TILES") && max_span64(col, s) <= (16 << 20) &&
+                few_spans64_over(col, kOutlierSpan, s);
+  if (sh.outliers) sh.tc = TileChoice{64, (int)((kOutlierSpan + 15 + 32 + 127) & ~(int64_t)127), false, kOutlierSpan};
+  const TileChoice& tc = sh.tc;
+  const int cap = sh.cap = tc.cap;
+  sh.holes_ok = r.tdfa && r.tp.d.in_lds && c.maxrepl < 0 && !c.tmpl_dev && !c.single_pass_only && !sh.wide_stream && !sh.outliers && tc.R == 64 && !tc.lng &&
+                sample_has_high_bytes(col, s) && odd_rows_few(col, s);
+  // (replacements of 17 .. kMaxStreamRepl bytes ride the four-register variants, their text read from memory at assembly)
+  // (... where a match is long enough for the row not to outgrow the out tile: a 19-byte replacement of one-digit matches
+  // goes to the two-pass kernels at once instead of failing the single pass twice first)
+  // (... or where the sample says matches are few: at most about three candidate bytes a row -- the first attempt is
+  // provisioned for kMaxRec matches a row; `-` -> 35 bytes on the log lines, two or three dashes each: 58 ms on the two-pass
+  // kernels.  A column that has more after all loses one launch before them)
+  const bool few_matches = rb <= kMaxStreamRepl && minlen >= 1 && col->rows > 0 &&
+                           candidate_share(re, col, s) * ((double)col->nbytes / (double)col->rows) <= (double)(kMaxRec - 1);
+  const size_t lds = (r.tp.d.in_lds ? r.tp.lds_bytes : 0) + (size_t)(cap + cap + 64 + (cap >> 3) + 32) * 4 + 16;
+  if (lds > 150 * 1024 || !(rb <= 16 || (rb <= kMaxStreamRepl && rb <= 4 * minlen) || few_matches) || !tc.R) return false;
+  sh.roomy_first = sh.growth > 0 && (minlen <= 2 || sh.wide_stream || sh.outliers || cs::cfg("CS_REPLACE_ROOMY"));
+  if (sh.roomy_first && rb >= 3 * sh.minlen_p && r.tdfa && !sh.wide_stream && !sh.outliers && !c.tmpl_dev && !c.single_pass_only && c.maxrepl < 0 && !sh.empties && r.tp.d.in_lds &&
+      !cs::cfg("CS_NO_COUNT_SIZING"))
+    count_matches_first(r, shape);
+  return true;
+}
+
+// replace_with_backrefs on a chain whose groups are runs of items: an expansion is the template's literal bytes plus the
+// groups it names, so a match grows by at most
+//   G = literal bytes + sum over items of (times the item is named - 1) * its length
+// -- with every item named at most once, G = literal bytes - the least length of the items NOT named, often <= 0
+// (`\4.\3.\2.\1` on four dotted groups: 3 - 3).  An item named twice and unbounded: -1, unknown.
+int64_t brefs_chain_growth(const cs_regex* re, const csvm::BackrefTemplate* ht) {
+  const cstd::View hv = cstd::make_view(re->tdfa.data());
+  const int ni = (int)((hv.chain >> 16) & 15u);
+  const unsigned long long hcrep = cstd::chain_crep(re->tdfa.data());
+  const uint32_t gmap = (uint32_t)re->tdfa[re->tdfa[15] - 1];
+  int named[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int j = 0; j < ht->nrefs; ++j) {
+    const int g = ht->idx[j];
+    int lo = 0, hi = 0;
+    if (g == 0) hi = ni;
+    else if (g <= 4 && g <= ht->groups) lo = (int)((gmap >> (8 * (g - 1))) & 15u), hi = (int)((gmap >> (8 * (g - 1) + 4)) & 15u);
+    for (int k = lo; k < hi && k < 8; ++k) ++named[k];
+  }
+  int64_t G = ht->bytes;
+  for (int k = 0; k < ni && k < 8; ++k) {
+    const int least = (int)(cstd::chain_rep(hcrep, k) & 15u), most = (int)(cstd::chain_rep(hcrep, k) >> 4);
+    if (named[k] == 0) G -= least;
+    else if (named[k] > 1) {
+      if (most == 0) return -1;
+      G += (int64_t)(named[k] - 1) * most;
+    }
+  }
+  return std::max<int64_t>(G, 0);
+}
+
+// Which variant of the stream kernel runs (the template parameters' meaning: at k_tdfa_replace_stream).
+struct ReplaceForm {
+  bool brefs;    // replace_with_backrefs: the unit scan, groups carried by the DFA (four at most), tables in LDS
+  bool literal;  // cs_replace's needle by byte comparison
+  bool bits_form;  // the bit-parallel form (regex_bits.h): patterns whose candidates are everywhere -- a bitmap per character class
+  // replace_with_backrefs on a chain whose groups are runs of items, the sample plain ASCII: the form that keeps neither
+  // tables nor group tags in LDS (<.., BREFS, .., CHAIN>); its out tile is sized from the template (brefs_chain_growth)
+  bool bchain;
+  int64_t brefs_grow;  // per match; -1: unknown (the old "twice the input")
+  // the unit scan (<.., UNITS>): patterns whose tagged DFA offers the decomposition, no limit on the number of
+  // replacements, rows within the 96-byte masks
+  bool units;
+  bool chain_form;     // (a chain pattern on a column whose sample is plain ASCII: the form without the unit / lean scans)
+  bool chain_pattern;  // (the route note: "chain" or "units")
+  bool lng;            // rows beyond the 96-byte candidate masks (and up to 255 bytes) take the sliding-window form
+  bool inplace;        // no growth; otherwise the register-record assembly, with the rescan on the roomy attempt and in every unit form
+  bool rep16;          // rb > 8
+};
+
+// The form of the call; false: the template has no form here (the caller's two-pass form runs).
+bool replace_form(const ReplaceRun& r, const ReplaceShape& sh, ReplaceForm* form) {
+  const cs::ReplaceCall& c = r.c;
+  const cs_column* col = c.col;
+  const cs_regex* re = r.re;
+  const hipStream_t s = c.s;
+  const TileChoice& tc = sh.tc;
+  const bool in_lds = r.tp.d.in_lds, all = c.maxrepl < 0, outliers = sh.outliers, wide_stream = sh.wide_stream;
+  const bool offers_units = (re->tdfa[31] & 1) != 0, chain = ((re->tdfa[30] >> 16) & 15) != 0, group_chain = chain && ((re->tdfa[30] >> 20) & 1) != 0;
+  ReplaceForm& f = *form;
+  f.brefs = c.tmpl_dev != nullptr;
+  // (a chain without a unit decomposition has no route for sub-tiles with bytes >= 0x80 in this form: only on columns whose sample is plain ASCII)
+  if (f.brefs && !((offers_units || (group_chain && !sample_has_high_bytes(col, s))) && !tc.lng && tc.R == 64 && in_lds && !re->gtags.empty() && re->prog.num_groups <= cstd::Tdfa::kGroupBatch &&
+                   re->gtags.size() * 4 <= 8 * 1024))
+    return false;
+  // (not the unit scan for the literal needles of cs_replace: short needles match densely, and then the per-row kernel with
+  // its in-place compaction is the faster one -- 'ab' -> 'x' on the C2 column: 1.25 against 1.77 ms)
+  f.literal = !f.brefs && !outliers && c.single_pass_only && c.literal_len > 0 && all && !tc.lng && tc.R == 64 && !cs::cfg("CS_NO_LITERAL_SCAN");
+  // (the bit form builds on the unit forms' layout and assembly, whether or not the pattern offers a unit decomposition)
+  f.bits_form = !f.literal && !f.brefs && !wide_stream && r.tdfa && all && !tc.lng && tc.R == 64 && !outliers && !c.single_pass_only && in_lds &&
+                bits_route(re, col, s, BITS_REPLACE, sh.holes_ok);
+  f.bchain = f.brefs && group_chain && !tc.lng && tc.R == 64 && all && c.tmpl_host && !cs::cfg("CS_NO_BREFS_CHAIN") && !sample_has_high_bytes(col, s);
+  f.brefs_grow = f.bchain ? brefs_chain_growth(re, static_cast<const csvm::BackrefTemplate*>(c.tmpl_host)) : -1;
+  // (units, or a chain pattern without them: one with a suffix)
+  f.units = f.literal || f.brefs || f.bits_form || ((offers_units || chain) && all && !tc.lng && tc.R == 64 && !outliers && !c.single_pass_only && !cs::cfg("CS_NO_UNITS"));
+  f.chain_form = !f.bits_form && !f.brefs && !wide_stream && !outliers && f.units && sh.cap <= 5 * 1024 && in_lds && !f.literal && all && chain &&
+                 (!sample_has_high_bytes(col, s) || sh.holes_ok) && !cs::cfg("CS_NO_CHAIN_FORM");
+  f.chain_pattern = chain;
+  f.lng = tc.lng;
+  f.inplace = sh.growth == 0;
+  f.rep16 = c.rb > 8;
+  return true;
+}
+
+// An attempt's sizes: the out tile and the output buffer, then the LDS layout (k_tdfa_replace_stream's).
+struct StreamSizing {
+  int cap_out;    // bytes of the out tile
+  int64_t extra;  // bytes of output beyond the input's
+  size_t gt_bytes, bits_lds, tbl_lds, lds1;  // group tags + template text, the bit form, the tables (or their header), all of it
+  bool chain_global;                         // the tables stay in memory
+};
+
+// The out tile and the output of an attempt: `cap_out` and `extra`.
+void size_stream_output(const ReplaceRun& r, const ReplaceShape& sh, const ReplaceForm& f, bool roomy, StreamSizing* z) {
+  const cs_column* col = r.c.col;
+  const int rb = r.c.rb, cap = sh.cap, growth = sh.growth, minlen_p = sh.minlen_p;
+  const int64_t span_room = std::min<int64_t>(cap, (sh.tc.span + 15 + 32 + 15) & ~(int64_t)15);
+  const int64_t few = (int64_t)col->rows * kMaxRec * growth;  // extra bytes if no row has more than kMaxRec matches
+  int cap_out = cap + ((64 * kMaxRec * growth + 127) & ~127);
+  // (no growth: the out tile holds at most the in tile's span -- rounded up to 16, not to the in tile's 128: a form of
+  // 54 496 bytes of LDS ran two workgroups per CU where 54 240 run three)
+  if (growth == 0 && !sh.outliers) cap_out = (int)span_room;
+  int64_t extra = std::min<int64_t>(few, col->nbytes + (1ll << 30));
+  if (roomy && sh.sized_total >= 0) {
+    // (the matches were counted first: the busiest tile's growth and the column's, exactly)
+    cap_out = (int)((span_room + sh.sized_tilemax * growth + 127) & ~(int64_t)127);
+    extra = sh.sized_total * growth + 64;
+  } else if (roomy) {
+    const int64_t worst = ((int64_t)cap * rb + minlen_p - 1) / minlen_p;
+    cap_out = std::max(cap_out, (int)((std::min<int64_t>(worst, 3ll * cap) + 127) & ~(int64_t)127));
+    const int64_t worst_extra = (col->nbytes * growth + minlen_p - 1) / minlen_p;
+    extra = std::min(worst_extra, std::max<int64_t>(extra, col->nbytes));
+    if (sh.empties) {  // every character and every row end may take a replacement
+      cap_out = (int)(((int64_t)cap * (1 + rb) + 64 * rb + 127) & ~(int64_t)127);
+      extra = col->nbytes * rb + col->rows * rb;
+    }
+  }
+  if (f.brefs && f.brefs_grow >= 0) {
+    // (at most span / minlen matches in a sub-tile, each growing by at most brefs_grow bytes -- the roomy sizing; the first
+    // attempt provisions a quarter of the input instead when that is less: `(\d+)` -> `<\1>` may triple a row of digits
+    // and spaces, and adds a sixth to a log line -- at the worst case's 84 KB of LDS one workgroup fits a CU, 48.8 ms on the
+    // C3 column; a launch that runs out of room says so and the roomy one follows)
+    int64_t tile_grow = (sh.tc.span / minlen_p + 1) * f.brefs_grow, col_grow = (col->nbytes / minlen_p + 1) * f.brefs_grow;
+    if (!roomy) {
+      tile_grow = std::min<int64_t>(tile_grow, std::max<int64_t>(sh.tc.span / 4, 256));
+      col_grow = std::min<int64_t>(col_grow, col->nbytes / 4 + (1 << 20));
+    }
+    cap_out = (int)((span_room + tile_grow + (tile_grow ? 127 : 0)) & ~(int64_t)(tile_grow ? 127 : 15));
+    extra = col_grow;
+  } else if (f.brefs) {
+    // (the template may grow a row by any amount: room for twice the input, a launch that needs more says so and the
+    // two-pass form takes over)
+    cap_out = std::max(cap_out, 2 * cap);
+    extra = std::max<int64_t>(extra, col->nbytes);
+  }
+  z->cap_out = cap_out;
+  z->extra = extra;
+}
+
+StreamSizing replace_sizing(const ReplaceRun& r, const ReplaceShape& sh, const ReplaceForm& f, bool roomy) {
+  const cs_regex* re = r.re;
+  const int cap = sh.cap;
+  StreamSizing z{};
+  size_stream_output(r, sh, f, roomy, &z);
+  const int bits_k = f.bits_form ? std::max(re->bits[1], 2) : 2;
+  z.bits_lds = f.bits_form ? (size_t)bits_lds_bytes((int)re->bits.size()) : 0;
+  // (the kernel's layout, k_tdfa_replace_stream: a bitmap's bytes, what stands behind the first one)
+  const size_t bm = (size_t)(cap >> 3) + (f.bits_form ? 16 : 32);
+  const size_t unit_bytes = f.bchain                          ? bm + 16 + kUnitQueue * 12
+                            : (f.chain_form || f.bits_form) ? (size_t)(bits_k - 1) * bm + 16
+                            : f.units                         ? (size_t)(bits_k - 1) * bm + kUnitQueue * 4 + 16 + (f.brefs ? kUnitQueue * 12 + 64 * 4 : 0)
+                                                              : 0;
+  // (backrefs: the group tags and the template text sit behind the DFA table)
+  z.gt_bytes = f.brefs ? (f.bchain ? 0 : ((re->gtags.size() * 4 + 15) & ~size_t(15))) + (((size_t)r.c.tmpl_text_bytes + 31) & ~size_t(15)) : 0;
+  // The chain arithmetic reads no table: when the tables are what keeps a third workgroup off the CU (the 26-instruction
+  // dotted quad with `\b` and {1,3}: 36 states, 19 KB), they stay in memory -- only a sub-tile the arithmetic does not take
+  // (bytes >= 0x80, a row beyond the masks) walks them there, and the sample says those are rare.
+  const size_t tbl = r.tp.d.in_lds ? r.tp.lds_bytes : 0;
+  const size_t tile_lds = z.gt_bytes + z.bits_lds + (size_t)(cap + z.cap_out + 64 + bm + unit_bytes) * 4 + 16;
+  constexpr size_t kThird = 160 * 1024 / 3;
+  // (the bit form likewise: its kernel with the tables in memory is built for three workgroups a CU -- 168 registers)
+  // (... whenever its tile leaves room for three, whatever the tables' size: the form with the tables in LDS is the 189-register
+  // one -- for patterns of up to five classes: the gtest pattern's seven fit a third workgroup too once the layout was trimmed,
+  // but its evaluation then spills where it hurts: 8.4 against 7.1 ms)
+  z.chain_global = ((f.chain_form && tbl + tile_lds > kThird && tile_lds + cstd::kHeadTailWords * 4 <= kThird) ||
+                    (f.bits_form && re->bits[1] <= 5 && tile_lds + cstd::kHeadTailWords * 4 <= kThird) || ((f.chain_form || f.bits_form) && cs::cfg("CS_CHAIN_TABLES_IN_MEMORY"))) &&
+                   !cs::cfg("CS_CHAIN_TABLES_IN_LDS");
+  z.tbl_lds = (z.chain_global || f.bchain) ? (size_t)cstd::kHeadTailWords * 4 : tbl;  // (header + tail words: tsetup)
+  z.lds1 = z.tbl_lds + tile_lds;
+  return z;
+}
+
+// The rows a single pass leaves holes for (cs_virtual.hip: OddRows), a thread a row: sized before the launch (`lens`),
+// written after it (`out_off`, `out_chars`).
+void launch_hole_rows(const ReplaceRun& r, const OddRows* od, int32_t* lens, const int64_t* out_off, uint8_t* out_chars) {
+  const hipStream_t s = r.c.s;
+  const unsigned grid = (unsigned)std::min<int64_t>((od->count + 255) / 256, 2048);
+  const size_t lds = r.tp.lds_bytes + (size_t)256 * kListRowBytes;  // (the tables and a row a thread)
+  const auto kern = lens ? &k_tdfa_replace_list<false> : &k_tdfa_replace_list<true>;
+  if (lds > 48 * 1024) CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  ProfScope ps("k_tdfa_replace_list", s);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, r.src, r.tp.d, ptr<const int32_t>(od->list), od->count, ptr<const uint8_t>(r.d_repl), r.c.rb, lens, out_off, out_chars);
+  CS_HIP(hipGetLastError());
+  if (!lens) CS_HIP(hipStreamSynchronize(s));  // (the write pass: the column is handed out next)
+}
+
+// The route note of a form (cs_debug_last_route).
+const char* replace_stream_route(const ReplaceShape& sh, const ReplaceForm& f) {
+  return f.bits_form ? "bits" : f.bchain ? "brefs-chain" : f.brefs ? "brefs" : f.literal ? "literal" : sh.wide_stream ? "wide" : f.units ? (f.chain_pattern ? "chain" : "units") : "plain";
+}
+
+// The instantiation of k_tdfa_replace_stream a form runs on: every one the library holds is named here, once.  The
+// parameters are <IN_LDS, REP16, INPLACE, RESCAN, LONG, UNITS, PF, BREFS, WIDE, OUTL, CHAIN, BITS, HOLES> (their
+// meaning: at the kernel).  REP16 follows the replacement's length in every form but the templates'; a unit form is
+// never in place and always rescans; the plain, wide and outlier forms are in place when nothing grows and rescan on
+// the roomy attempt (the outlier and wide forms' first attempt is the roomy one).
+// (tables in LDS: a DFA beyond the LDS budget never gets here -- the forms with the tables in memory that are not
+// chain forms were never reached by a test and spilled 20-60 registers: out since round 6, kernel_coverage.txt)
+using StreamKernel = void (*)(StreamArgs);
+StreamKernel replace_stream_kernel(const ReplaceShape& sh, const ReplaceForm& f, bool chain_global, bool with_holes, bool roomy) {
+  constexpr int P6 = cstile::kPfChunks;
+  const bool r16 = f.rep16, lng = f.lng, pf5 = sh.cap <= 5 * 1024;
+  if (!sh.outliers && !sh.wide_stream && !f.units) {  // the plain forms: the rows' lean scan
+    if (f.inplace)
+      return lng ? (r16 ? &k_tdfa_replace_stream<true, true, true, false, true> : &k_tdfa_replace_stream<true, false, true, false, true>)
+                 : (r16 ? &k_tdfa_replace_stream<true, true, true, false, false> : &k_tdfa_replace_stream<true, false, true, false, false>);
+    if (roomy)
+      return lng ? (r16 ? &k_tdfa_replace_stream<true, true, false, true, true> : &k_tdfa_replace_stream<true, false, false, true, true>)
+                 : (r16 ? &k_tdfa_replace_stream<true, true, false, true, false> : &k_tdfa_replace_stream<true, false, false, true, false>);
+    return lng ? (r16 ? &k_tdfa_replace_stream<true, true, false, false, true> : &k_tdfa_replace_stream<true, false, false, false, true>)
+               : (r16 ? &k_tdfa_replace_stream<true, true, false, false, false> : &k_tdfa_replace_stream<true, false, false, false, false>);
+  }
+  if (sh.outliers) {  // (the forms that handle oversize sub-tiles: in place, or with the rescan assembly)
+    if (f.inplace)
+      return r16 ? &k_tdfa_replace_stream<true, true, true, false, false, false, P6, false, false, true>
+                 : &k_tdfa_replace_stream<true, false, true, false, false, false, P6, false, false, true>;
+    return r16 ? &k_tdfa_replace_stream<true, true, false, true, false, false, P6, false, false, true>
+               : &k_tdfa_replace_stream<true, false, false, true, false, false, P6, false, false, true>;
+  }
+  if (sh.wide_stream) {
+    if (!r16) {
+      if (f.inplace) return lng ? &k_tdfa_replace_stream<true, false, true, false, true, false, P6, false, true> : &k_tdfa_replace_stream<true, false, true, false, false, false, P6, false, true>;
+      return lng ? &k_tdfa_replace_stream<true, false, false, true, true, false, P6, false, true> : &k_tdfa_replace_stream<true, false, false, true, false, false, P6, false, true>;
+    }
+    if (f.inplace) return lng ? &k_tdfa_replace_stream<true, true, true, false, true, false, P6, false, true> : &k_tdfa_replace_stream<true, true, true, false, false, false, P6, false, true>;
+    return lng ? &k_tdfa_replace_stream<true, true, false, true, true, false, P6, false, true> : &k_tdfa_replace_stream<true, true, false, true, false, false, P6, false, true>;
+  }
+  if (f.bchain)
+    return pf5 ? &k_tdfa_replace_stream<false, false, false, true, false, true, 5, true, false, false, true>
+               : &k_tdfa_replace_stream<false, false, false, true, false, true, P6, true, false, false, true>;
+  if (f.brefs) return pf5 ? &k_tdfa_replace_stream<true, false, false, true, false, true, 5, true> : &k_tdfa_replace_stream<true, false, false, true, false, true, P6, true>;
+  if (f.bits_form && chain_global)
+    return r16 ? &k_tdfa_replace_stream<false, true, false, true, false, true, P6, false, false, false, true, true>
+               : &k_tdfa_replace_stream<false, false, false, true, false, true, P6, false, false, false, true, true>;
+  if (f.bits_form)
+    return r16 ? &k_tdfa_replace_stream<true, true, false, true, false, true, P6, false, false, false, true, true>
+               : &k_tdfa_replace_stream<true, false, false, true, false, true, P6, false, false, false, true, true>;
+  if (f.chain_form && chain_global)
+    return r16 ? &k_tdfa_replace_stream<false, true, false, true, false, true, 5, false, false, false, true>
+               : &k_tdfa_replace_stream<false, false, false, true, false, true, 5, false, false, false, true>;
+  if (f.chain_form)
+    return r16 ? &k_tdfa_replace_stream<true, true, false, true, false, true, 5, false, false, false, true>
+               : &k_tdfa_replace_stream<true, false, false, true, false, true, 5, false, false, false, true>;
+  // the unit form proper (literal needles ride it too): with the hole words only when the column has holes
+  if (pf5 && with_holes) return r16 ? &k_tdfa_replace_stream<true, true, false, true, false, true, 5> : &k_tdfa_replace_stream<true, false, false, true, false, true, 5>;
+  if (with_holes) return r16 ? &k_tdfa_replace_stream<true, true, false, true, false, true> : &k_tdfa_replace_stream<true, false, false, true, false, true>;
+  if (pf5)
+    return r16 ? &k_tdfa_replace_stream<true, true, false, true, false, true, 5, false, false, false, false, false, false>
+               : &k_tdfa_replace_stream<true, false, false, true, false, true, 5, false, false, false, false, false, false>;
+  return r16 ? &k_tdfa_replace_stream<true, true, false, true, false, true, P6, false, false, false, false, false, false>
+             : &k_tdfa_replace_stream<true, false, false, true, false, true, P6, false, false, false, false, false, false>;
+}
+
+// The kernel's arguments.  `status` is carved into
+// [aggregates nsub][error word + phase counters 16][tickets 128: sixteen counters][exclusive prefixes nsub]
+// (+ kScanBatch windows of slack: the scanner wave fetches whole batches)
+size_t stream_status_bytes(int64_t nsub) { return sizeof(cstile::u64) * (2 * (size_t)nsub + 16 + 128 + 64 * cstile::kScanBatch); }
+StreamArgs replace_stream_args(const ReplaceRun& r, const ReplaceShape& sh, const ReplaceForm& f, const StreamSizing& z, const Buf& out_off, const Buf& out_chars, const Buf& status) {
+  const cs::ReplaceCall& c = r.c;
+  const cs_regex* re = r.re;
+  StreamArgs sa{};
+  sa.in = view_of(c.col);
+  sa.flags = d_unicode_flags();
+  sa.L = r.tp.d;
+  if (z.chain_global || f.bchain) sa.L.in_lds = 2;
+  sa.repl = ptr<const uint8_t>(r.d_repl);
+  sa.rb = c.rb;
+  sa.maxrepl = c.maxrepl;
+  sa.out_off = ptr<int64_t>(out_off);
+  sa.out_chars = ptr<uint8_t>(out_chars);
+  sa.out_cap = c.col->nbytes + z.extra;
+  sa.rows_per_tile = sh.tc.R;
+  sa.nsub = (c.col->rows + sh.tc.R - 1) / sh.tc.R;
+  sa.status = ptr<cstile::u64>(status);
+  sa.error = reinterpret_cast<unsigned*>(sa.status + sa.nsub);
+  sa.tickets = sa.status + sa.nsub + 16;
+  sa.excl = sa.status + sa.nsub + 16 + 128;
+  sa.cap_in = sh.cap;
+  sa.cap_out = z.cap_out;
+  sa.tbl_bytes = (int)(z.tbl_lds + z.gt_bytes + z.bits_lds);
+  sa.bits = f.bits_form ? ptr<const int32_t>(re->d_bits) : nullptr;
+  sa.bits_off = (int)(z.tbl_lds + z.gt_bytes);
+  sa.bits_words = f.bits_form ? (int)re->bits.size() : 0;
+  sa.bits_k = f.bits_form ? re->bits[1] : 0;
+  sa.tmpl = static_cast<const csvm::BackrefTemplate*>(c.tmpl_dev);
+  sa.gtags = f.brefs ? ptr<const int32_t>(re->d_gtags) : nullptr;
+  sa.gt_off = (int)z.tbl_lds;
+  sa.gt_words = f.brefs && !f.bchain ? (int)re->gtags.size() : 0;
+  sa.debug = cs::cfg_int("CS_TILE_DEBUG", 0);
+  sa.outliers = sh.outliers ? 1 : 0;
+  sa.lit = f.literal ? c.literal : 0;
+  sa.litn = f.literal ? c.literal_len : 0;
+  return sa;
+}
+
+#if defined(CS_PHASE_PROF)
+// CS_REPLACE_TRACE: a time stamp buffer for every 1024th sub-tile (cstile::g_tile_trace), null without the switch
+Buf phase_prof_begin(int64_t nsub, hipStream_t s) {
+  Buf tracebuf;
+  const long long ntrace = (nsub >> 10) + 1;
+  unsigned long long* tp_ = nullptr;
+  if (cs::cfg("CS_REPLACE_TRACE")) {
+    tracebuf = dev_alloc(sizeof(unsigned long long) * 4 * ntrace, s);
+    CS_HIP(hipMemsetAsync(tracebuf->p, 0, sizeof(unsigned long long) * 4 * ntrace, s));
+    tp_ = ptr<unsigned long long>(tracebuf);
+  }
+  CS_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(cstile::g_tile_trace), &tp_, sizeof(tp_), 0, hipMemcpyHostToDevice, s));
+  return tracebuf;
+}
+void phase_prof_report(const StreamArgs& sa, const Buf& tracebuf, unsigned grid) {
+  const long long nsub1 = sa.nsub, ntrace = (nsub1 >> 10) + 1;
+  unsigned long long ph[12];
+  CS_HIP(hipMemcpy(ph, reinterpret_cast<unsigned long long*>(sa.error) + 1, sizeof(ph), hipMemcpyDeviceToHost));
+  if (tracebuf) {
+    std::vector<unsigned long long> tr(4 * ntrace);
+    CS_HIP(hipMemcpy(tr.data(), tracebuf->p, sizeof(unsigned long long) * 4 * ntrace, hipMemcpyDeviceToHost));
+    unsigned long long t0 = ~0ull;
+    for (long long i = 0; i < ntrace; ++i)
+      if (tr[4 * i]) t0 = std::min(t0, tr[4 * i]);
+    fprintf(stderr, "trace (us since the first publish; every 1024th sub-tile): tile published scanned start-of-finish prefix-seen\n");
+    for (long long i = 0; i < ntrace; i += std::max<long long>(1, ntrace / 40))
+      fprintf(stderr, "trace %8lld %9.1f %9.1f %9.1f %9.1f\n", i << 10, (double)(tr[4 * i] - t0) / 100.0, (double)(tr[4 * i + 1] - t0) / 100.0,
+              (double)(tr[4 * i + 2] - t0) / 100.0, (double)(tr[4 * i + 3] - t0) / 100.0);
+  }
+  unsigned long long lb[4] = {0, 0, 0, 0};
+  CS_HIP(hipMemcpyFromSymbol(lb, HIP_SYMBOL(cstile::g_lb_stats), sizeof(lb)));
+  fprintf(stderr, "look-back (cumulative): %llu calls, %.2f windows per call, %.2f re-polls per call\n", lb[0], (double)lb[1] / (double)(lb[0] ? lb[0] : 1),
+          (double)lb[2] / (double)(lb[0] ? lb[0] : 1));
+  const double waves = (double)grid * 4;
+  fprintf(stderr, "stage split: wait+lds %.0f classify %.0f rest %.0f | ", ph[9] / waves / (nsub1 / waves), ph[10] / waves / (nsub1 / waves), ph[0] / waves / (nsub1 / waves));
+  fprintf(stderr, "phase cycles/wave-iteration: stage %.0f scan %.0f (units: discovery %.0f rounds %.0f) wscan+publish %.0f finish_prev(offsets+flush) %.0f assemble %.0f tail %.0f lookback %.0f (iters/wave %.1f)\n",
+          ph[0] / waves / (nsub1 / waves), ph[1] / waves / (nsub1 / waves), ph[7] / waves / (nsub1 / waves), ph[8] / waves / (nsub1 / waves), ph[2] / waves / (nsub1 / waves),
+          ph[3] / waves / (nsub1 / waves), ph[4] / waves / (nsub1 / waves), ph[5] / waves / (nsub1 / waves), ph[6] / waves / (nsub1 / waves), nsub1 / waves);
+}
+#endif
+
+// CS_STREAM_INFO: what was launched
+void print_stream_info(const ReplaceRun& r, const ReplaceShape& sh, const ReplaceForm& f, const StreamSizing& z, bool roomy, unsigned grid) {
+  fprintf(stderr, "replace stream: grid %u lds %zu (tables %zu, tile %d + %d) rows/tile %d units %d chain %d wide %d brefs %d roomy %d growth %d rb %d\n", grid, z.lds1, z.tbl_lds + z.gt_bytes, sh.cap,
+          z.cap_out, sh.tc.R, (int)f.units, f.bchain ? 3 : f.chain_form ? (z.chain_global ? 2 : 1) : 0, (int)sh.wide_stream, (int)f.brefs, (int)roomy, (int)sh.growth, r.c.rb);
+}
+
+// CS_DUMP_STATUS, development aid: where did the prefix chain stop?
+void dump_stream_status(const StreamArgs& sa, int err, unsigned grid) {
+  const int64_t nsub1 = sa.nsub;
+  std::vector<cstile::u64> st((size_t)nsub1), ex((size_t)nsub1);
+  CS_HIP(hipMemcpy(st.data(), sa.status, sizeof(cstile::u64) * nsub1, hipMemcpyDeviceToHost));
+  CS_HIP(hipMemcpy(ex.data(), sa.excl, sizeof(cstile::u64) * nsub1, hipMemcpyDeviceToHost));
+  unsigned long long tk[8];
+  CS_HIP(hipMemcpy(tk, sa.tickets, sizeof(tk), hipMemcpyDeviceToHost));
+  fprintf(stderr, "status dump: err %d nsub %lld grid %u ticket0 %llu\n", err, (long long)nsub1, grid, tk[0]);
+  for (int64_t t = 0; t < nsub1 && t < 64; ++t)
+    fprintf(stderr, "  tile %lld: agg flag %u val %llu | excl flag %u val %llu\n", (long long)t, (unsigned)(st[t] >> 62), (unsigned long long)(st[t] & cstile::kValMask),
+            (unsigned)(ex[t] >> 62), (unsigned long long)(ex[t] & cstile::kValMask));
+}
+
+// what gave up, in words: the error word's bits and the column's shape (profiles/r04/soak.txt showed "error word 33"
+// without saying that it is the backrefs form meeting a sub-tile with more than 128 matches); counted: cs_fallback_count
+void note_stream_fallback(const ReplaceRun& r, int err) {
+  const cs_column* col = r.c.col;
+  char what[256];
+  snprintf(what, sizeof(what), "%s (error word %d:%s%s%s%s%s%s; %lld rows, longest %lld bytes, largest 64-row span %lld)",
+           r.c.tmpl_dev ? "replace_with_backrefs" : "replace_re", err, (err & 1) ? " launch abandoned" : "", (err & 2) ? " out of output room" : "",
+           (err & 4) ? " a sub-tile beyond the staging buffer" : "", (err & 8) ? " no prefix for a tile" : "", (err & 16) ? " the scanners timed out" : "",
+           (err & 32) ? " a sub-tile with more than 128 matches or a row handed over by the unit route (the template needs the unit route's masks)" : "",
+           (long long)col->rows, (long long)col->max_row, (long long)col->max_span64);
+  note_fallback(what);
+}
+
+// The output of a launch that succeeded becomes the column's, with metadata as a by-product: the largest 64-row span is
+// the largest sub-tile total the kernel saw; a replacement no longer than the shortest match cannot lengthen a row (an
+// upper bound serves: the numbers size staging buffers and pick routes); plain input + plain replacement stays plain
+void adopt_stream_output(const ReplaceRun& r, const ReplaceShape& sh, const ReplaceForm& f, cs_column* o, const Buf& out_off, const Buf& out_chars, const int64_t* host) {
+  const cs_column* col = r.c.col;
+  o->offsets = out_off;
+  o->chars = out_chars;
+  o->nbytes = host[0];
+  if (sh.tc.R == 64) o->max_span64 = host[2];
+  if (sh.growth == 0 && col->max_row >= 0) o->max_row = col->max_row;
+  if (col->high_sample == 0 && !f.brefs) {
+    bool ascii = true;
+    for (int i = 0; i < r.c.rb; ++i) ascii = ascii && (unsigned char)r.c.repl[i] < 0x80 && r.c.repl[i] != 0;
+    if (ascii) o->high_sample = 0;
+  }
+}
+
+// One launch of the persistent stream kernel (grid = what is resident at once).  Returns its error word (0: `o` holds the
+// column), or -1 when the sizing does not fit.  `hole_lens` is taken once: a second, roomier attempt uses them again.
+int replace_stream_attempt(const ReplaceRun& r, const ReplaceShape& sh, const ReplaceForm& f, bool roomy, Buf& hole_lens, cs_column* o) {
+  const cs_column* col = r.c.col;
+  const hipStream_t s = r.c.s;
+  const StreamSizing z = replace_sizing(r, sh, f, roomy);
+  if (z.lds1 > 150 * 1024) return -1;
+  const int64_t rows = col->rows, nsub1 = (rows + sh.tc.R - 1) / sh.tc.R;
+  Buf out_off = dev_alloc(sizeof(int64_t) * (rows + 1), s);
+  Buf out_chars = dev_alloc((size_t)col->nbytes + (size_t)z.extra + 64, s);
+  Buf status = dev_alloc(stream_status_bytes(nsub1), s);
+  CS_HIP(hipMemsetAsync(status->p, 0, stream_status_bytes(nsub1), s));
+  StreamArgs sa = replace_stream_args(r, sh, f, z, out_off, out_chars, status);
+  const OddRows* od = sh.holes_ok && !f.literal && !f.brefs ? odd_rows(col, s) : nullptr;
+  const bool with_holes = od && od->count > 0;
+  if (with_holes) {
+    if (!hole_lens) {
+      hole_lens = dev_alloc(sizeof(int32_t) * (size_t)od->count, s);
+      launch_hole_rows(r, od, ptr<int32_t>(hole_lens), nullptr, nullptr);
+    }
+    sa.hole_mask = ptr<const unsigned long long>(od->mask);
+    sa.hole_first = ptr<const int64_t>(od->first);
+    sa.hole_len = ptr<const int32_t>(hole_lens);
+  }
+  const StreamKernel kern = replace_stream_kernel(sh, f, z.chain_global, with_holes, roomy);
+  note_route(replace_stream_route(sh, f));
+  if (with_holes) note_route_put_off();
+#if defined(CS_PHASE_PROF)
+  Buf tracebuf = phase_prof_begin(nsub1, s);
+#endif
+  unsigned grid;
+  {
+    ProfScope ps("k_replace_re", s);
+    grid = launch_resident(kern, z.lds1, (nsub1 + 3) / 4, s, sa);
+  }
+  if (cs::cfg("CS_STREAM_INFO")) print_stream_info(r, sh, f, z, roomy, grid);
+  int64_t* host = (int64_t*)pinned_scratch(24);
+  CS_HIP(hipMemcpyAsync(host, ptr<int64_t>(out_off) + rows, 8, hipMemcpyDeviceToHost, s));
+  CS_HIP(hipMemcpyAsync(host + 1, sa.error, 4, hipMemcpyDeviceToHost, s));
+  CS_HIP(hipMemcpyAsync(host + 2, reinterpret_cast<unsigned long long*>(sa.error) + 14, 8, hipMemcpyDeviceToHost, s));
+  CS_HIP(hipStreamSynchronize(s));
+#if defined(CS_PHASE_PROF)
+  phase_prof_report(sa, tracebuf, grid);
+#endif
+  const int err = (int)(uint32_t)host[1];
+  if (err != 0 && cs::cfg("CS_DUMP_STATUS")) dump_stream_status(sa, err, grid);
+  if (err != 0) return err;  // (a launch whose error word is set never yields a column, measurement switches or not)
+  if (with_holes) {  // the holes' bytes
+    launch_hole_rows(r, od, nullptr, ptr<const int64_t>(out_off), ptr<uint8_t>(out_chars));
+  }
+  adopt_stream_output(r, sh, f, o, out_off, out_chars, host);
+  return 0;
+}
+
+// The single pass (when a match cannot be empty, or its replacement is short): shape, form, one attempt or two.
+// An oversize sub-tile or a look-back timeout is counted as a fallback; the caller goes on to the two-pass kernels.
+cs_column* replace_single_pass(const ReplaceRun& r, Built& b) {
+  ReplaceShape sh;
+  if (!replace_shape(r, &sh)) return nullptr;
+  // (a DFA whose tables do not fit the LDS budget: the two-pass kernels read them from memory)
+  if (!r.tp.d.in_lds) return nullptr;
+  ReplaceForm f;
+  if (!replace_form(r, sh, &f)) return nullptr;
+  Buf hole_lens;
+  int err = replace_stream_attempt(r, sh, f, sh.roomy_first, hole_lens, b.col.get());
+  if (err == 2 && !sh.roomy_first) err = replace_stream_attempt(r, sh, f, true, hole_lens, b.col.get());  // only ran out of room: once more, roomier
+  if (err == 0) return b.col.release();
+  if (err > 0) note_stream_fallback(r, err);
+  return nullptr;
+}
+
+// The two-pass kernels, a thread a row: `lens` for the size pass, `off` and `chars` for the write pass -- one pick by
+// executor (wide DFA, DFA, list simulator) and by where its tables are serves both.
+void launch_two_pass(const ReplaceRun& r, int32_t* lens, const int64_t* off, uint8_t* chars) {
+  const cs::ReplaceCall& c = r.c;
+  const TPlan& tp = r.tp;
+  const Plan& pl = r.pl;
+  // [the wide DFA, tables in LDS / in memory; the DFA, in LDS / in memory]  [the list simulator: small programs / the others]
+  static constexpr decltype(&k_tdfa_replace_size<true>) dfa_size[4] = {&k_tdfa_replace_size<true, true>, &k_tdfa_replace_size<false, true>, &k_tdfa_replace_size<true>, &k_tdfa_replace_size<false>};
+  static constexpr decltype(&k_replace_re_size<true>) vm_size[2] = {&k_replace_re_size<true>, &k_replace_re_size<false>};
+  static constexpr decltype(&k_tdfa_replace_write<true>) dfa_write[4] = {&k_tdfa_replace_write<true, true>, &k_tdfa_replace_write<false, true>, &k_tdfa_replace_write<true>, &k_tdfa_replace_write<false>};
+  static constexpr decltype(&k_replace_re_write<true>) vm_write[2] = {&k_replace_re_write<true>, &k_replace_re_write<false>};
+  {
+    ProfScope ps(lens ? "k_replace_re_size" : "k_replace_re_write", c.s);
+    if (r.wide || r.tdfa) {
+      const int k = (r.wide ? 0 : 2) + (tp.d.in_lds ? 0 : 1);
+      const size_t lds = tp.d.in_lds ? tp.lds_bytes : 0;
+      if (lens) hipLaunchKernelGGL(dfa_size[k], dim3(tp.grid), dim3(256), lds, c.s, r.src, tp.d, c.rb, c.maxrepl, lens);
+      else hipLaunchKernelGGL(dfa_write[k], dim3(tp.grid), dim3(256), lds, c.s, r.src, tp.d, ptr<const uint8_t>(r.d_repl), c.rb, c.maxrepl, off, chars);
+    } else {
+      const int k = pl.small ? 0 : 1;
+      if (lens) hipLaunchKernelGGL(vm_size[k], dim3(pl.grid), dim3(pl.threads), pl.lds_bytes, c.s, r.src, pl.d, c.rb, c.maxrepl, lens);
+      else hipLaunchKernelGGL(vm_write[k], dim3(pl.grid), dim3(pl.threads), pl.lds_bytes, c.s, r.src, pl.d, ptr<const uint8_t>(r.d_repl), c.rb, c.maxrepl, off, chars);
+    }
+  }
+  CS_HIP(hipGetLastError());
+}
+cs_column* replace_two_pass(const ReplaceRun& r, Built& b) {
+  Buf lens = dev_alloc(sizeof(int32_t) * r.c.col->rows, r.c.s);
+  launch_two_pass(r, ptr<int32_t>(lens), nullptr, nullptr);
+  b.scan(ptr<int32_t>(lens));
+  b.alloc_chars();
+  launch_two_pass(r, nullptr, b.off, b.chars);
+  CS_HIP(hipStreamSynchronize(r.c.s));  // d_repl / arena lifetime
+  return b.col.release();
+}
+
+}  // namespace
+
+namespace cs {
+cs_column* replace_re_column(const ReplaceCall& c) {
+  if (c.col->rows == 0) return make_all_null(0, c.s);
+  note_route("");
+  cs_regex* re = const_cast<cs_regex*>(c.re);
+  ReplaceRun r{c, re, use_tdfa(re), use_tdfa_wide(re)};
+  r.d_repl = dev_alloc((size_t)c.rb + 1, c.s);
+  CS_HIP(hipMemcpyAsync(r.d_repl->p, c.repl, (size_t)c.rb + 1, hipMemcpyHostToDevice, c.s));
+  if (r.tdfa || r.wide) r.tp = tplan(re, c.col->rows, c.s);
+  else r.pl = plan(re, c.col->rows, c.s);
+  if (cs_column* o = replace_on_pieces(r)) return o;
+  if (cs_column* o = replace_by_class_runs(r)) return o;
+  r.src = RowSrc{view_of(c.col), d_unicode_flags(), c.col->nbytes + (c.col->chars && c.col->chars->capacity ? 64 : 0)};
+  Built b(c.col, c.s);  // (the single pass fills it itself: it allocates before it knows the sizes)
+  if (cs_column* o = replace_single_pass(r, b)) return o;
+  if (c.single_pass_only) fail(CS_ERR_INTERNAL, "literal replace: single-pass kernel not applicable");  // (the caller's own kernels are the fallback)
+  return replace_two_pass(r, b);
+}
+}  // namespace cs
+
+extern "C" {
+
 // NVStrings::replace_re -- replace.cu:110-189
 int cs_replace_re(const cs_column* col, const cs_regex* cre, const char* repl, int maxrepl, cs_stream stream,
                   cs_column** out) {
@@ -3322,526 +3974,9 @@ int cs_replace_re(const cs_column* col, const cs_regex* cre, const char* repl, i
     if (!col || !cre || !out) fail(CS_ERR_INVALID_ARG, "replace_re: null argument");
     if (cre->empty_pattern)
       fail(CS_ERR_INVALID_ARG, "nvstrings::replace_re parameter cannot be null or empty");  // replace.cu:112-113
-    cs_regex* re = const_cast<cs_regex*>(cre);
-    hipStream_t s = S(stream);
     require_device();
-    if (col->rows == 0) {
-      *out = make_all_null(0, s);
-      return;
-    }
     if (!repl) repl = "";
-    const int rb = (int)strlen(repl);
-    note_route("");
-    Buf d_repl = dev_alloc((size_t)rb + 1, s);
-    CS_HIP(hipMemcpyAsync(d_repl->p, repl, (size_t)rb + 1, hipMemcpyHostToDevice, s));
-    const bool tdfa = use_tdfa(re);
-    const bool wide = use_tdfa_wide(re);  // (five to eight live threads: the two-pass kernels on TdfaWide)
-    Plan pl{};
-    TPlan tp{};
-    if (tdfa || wide) tp = tplan(re, col->rows, s);
-    else pl = plan(re, col->rows, s);
-    // rows beyond the 96-bit masks, white space a safe cut for this program: the pieces' replace_re is the rows' (cs_virtual.hip)
-    if (!cs::g_backrefs_dev && !cs::g_replace_plain_only && maxrepl < 0 && tdfa && !cs::cfg("CS_CLASS_RUNS_ALWAYS")) {
-      if (const VirtualRows* vr = pieces_for(col, re, s, true)) {
-        cs_column* po = nullptr;
-        const int rc = cs_replace_re(vr->col.get(), cre, repl, maxrepl, stream, &po);
-        if (rc != 0) fail(rc, cs_last_error());
-        note_route_pieces();
-        *out = virtual_rows_to_rows(col, vr, std::unique_ptr<cs_column>(po), s);
-        return;
-      }
-    }
-    // One character class, once or in a `+` loop, on a column the 96-bit-mask forms do not take -- rows beyond 93 bytes,
-    // tiles of fewer than 64 rows, non-ASCII text -- and whose candidates are everywhere: byte-parallel stream compaction
-    // (cs_runs.hip; BASELINE.json C5: replace_re([aeiou]+) on 40-150-byte rows, 82.8 ms on the long-row automaton forms).
-    if (!cs::g_backrefs_dev && !cs::g_replace_plain_only && maxrepl < 0 && col->rows > 0 && !re->bits.empty() && (re->bits[2] & (csbits::F_BYTE_CLASS | csbits::F_FLAG_CLASS)) &&
-        re->d_bits) {
-      const TileChoice tc0 = choose_tile(col, s, true);
-      const bool masks_form = tc0.R == 64 && !tc0.lng && (!sample_has_high_bytes(col, s) || odd_rows_few(col, s));  // (few rows with such bytes: holes)
-      // (a class with builtins -- `\w+` -- sends every tile with a byte >= 0x80 row by row: worth it against the automaton's
-      // long-row and dense forms -- `\w+` on the C5 column 97.7 -> 11.2 ms, on C2 16.2 -> 5.1 --, not against the chain
-      // arithmetic where that runs: `\s+` on C2 4.4 there, 6.7 here)
-      const bool chain_there = !re->tdfa.empty() && ((re->tdfa[30] >> 16) & 15) != 0 && tc0.R == 64 && !tc0.lng;
-      const bool flag_class = (re->bits[2] & csbits::F_BYTE_CLASS) == 0;
-      const bool wanted = cs::cfg("CS_CLASS_RUNS_ALWAYS") || (!masks_form && !(flag_class && chain_there) && candidate_share(re, col, s) >= 0.05);
-      cs_column* r = nullptr;
-      if (wanted && replace_class_runs(col, ptr<const int32_t>(re->d_bits), re->bits, repl, rb, s, &r)) {
-        note_route("runs");
-        *out = r;
-        return;
-      }
-    }
-    RowSrc src{view_of(col), d_unicode_flags(), col->nbytes + (col->chars && col->chars->capacity ? 64 : 0)};
-    Built b(col, s);  // (the single pass below fills it itself: it allocates before it knows the sizes)
-    cs_column* const o = b.col.get();
-    const int minlen = (tdfa || wide) ? re->tdfa[13] : 0;
-    // Single pass when a match cannot be empty: a match is at least `minlen` bytes, so a row grows
-    // by at most (rb - minlen) bytes per match; rb <= minlen means "never grows" and the rows are
-    // rewritten in place.  A growing replacement is provisioned for kMaxRec matches per row first
-    // (or, for one- and two-byte patterns, which tend to match often, for up to the worst case);
-    // a launch that runs out of room says so in its error word and is repeated once with the
-    // roomier sizing.  A pattern that matches the empty string with a non-empty replacement is
-    // unbounded (the zero-length repeat rule) and takes the two-pass kernels.
-    const int growth = rb > minlen ? rb - minlen : 0;
-    // (a pattern that matches the empty string inserts at most one replacement per character and one at the row's end:
-    // short replacements are provisioned for exactly that -- `x*` -> '-' doubles the column -- and stay on the single pass)
-    const bool empties = minlen == 0 && growth > 0;
-    const int minlen_p = std::max(minlen, 1);
-    const bool bounded = growth == 0 || minlen >= 1 || rb <= 8;  // (longer ones: the out tile of 1 + rb times the input does not fit the LDS)
-    // (programs of five to eight threads: the stream kernel's WIDE forms -- tables in LDS, replacements of up to 16 bytes)
-    const bool wide_stream = wide && tp.d.in_lds && rb <= 16 && !cs::g_backrefs_dev && !cs::cfg("CS_WIDE_TWO_PASS");
-    if ((tdfa || wide_stream) && bounded && !cs::cfg("CS_REGEX_TWO_PASS")) {
-      const int64_t rows = col->rows;
-      const int64_t ntiles = (rows + cstile::kTileRows - 1) / cstile::kTileRows;
-      const int64_t nsub = ntiles * 4;
-      TileChoice tc = choose_tile(col, s, !cs::cfg("CS_NO_SMALL_TILES"));
-      // (the column's largest 64-row span does not fit, all but a few do: buffers for those, the kernel handles the rest)
-      bool outliers = false;
-      constexpr int64_t kOutlierSpan = cstile::kPfBytes - 176;  // (its capacity is kPfBytes)
-      if (!tc.R && tdfa && tp.d.in_lds && rb <= 16 && !cs::g_backrefs_dev && !cs::cfg("CS_NO_OUTLIER_TILES") && max_span64(col, s) <= (16 << 20) &&
-          few_spans64_over(col, kOutlierSpan, s)) {
-        tc = TileChoice{64, (int)((kOutlierSpan + 15 + 32 + 127) & ~(int64_t)127), false, kOutlierSpan};
-        outliers = true;
-      }
-      const int cap = tc.cap;
-      const size_t tbl = tp.d.in_lds ? tp.lds_bytes : 0;
-      size_t lds = tbl + (size_t)(cap + cap + 64 + (cap >> 3) + 32) * 4 + 16;
-      // persistent stream kernel (grid = what is resident at once); returns its error word, or -1
-      // when the sizing does not fit
-      int64_t sized_total = -1, sized_tilemax = 0;  // matches in the column / in its busiest tile, when they were counted first
-      // a column whose sample holds a few bytes >= 0x80: the unit forms run as on plain ASCII, the rows that hold such bytes are
-      // sized beforehand and written afterwards, a thread a row (StreamArgs::hole_mask) -- replace_re of the gtest pattern on the C5
-      // column's pieces: 34 ms when a third of the sub-tiles went to the row-by-row scan for the sake of one row each
-      const bool holes_ok = tdfa && tp.d.in_lds && maxrepl < 0 && !cs::g_backrefs_dev && !cs::g_replace_plain_only && !wide_stream && !outliers && tc.R == 64 && !tc.lng &&
-                            sample_has_high_bytes(col, s) && odd_rows_few(col, s);
-      Buf hole_lens;  // (taken once: a second, roomier attempt uses them again)
-      auto stream_attempt = [&](bool roomy) -> int {
-        // (a DFA whose tables do not fit the LDS budget: the two-pass kernels read them from memory)
-        if (!tp.d.in_lds) return -1;
-        const int64_t few = (int64_t)rows * kMaxRec * growth;  // extra bytes if no row has more than kMaxRec matches
-        int cap_out = cap + ((64 * kMaxRec * growth + 127) & ~127);
-        // (no growth: the out tile holds at most the in tile's span -- rounded up to 16, not to the in tile's 128: a form of
-        // 54 496 bytes of LDS ran two workgroups per CU where 54 240 run three)
-        if (growth == 0 && !outliers) cap_out = (int)std::min<int64_t>(cap, (tc.span + 15 + 32 + 15) & ~(int64_t)15);
-        int64_t extra = std::min<int64_t>(few, col->nbytes + (1ll << 30));
-        if (roomy && sized_total >= 0) {
-          // (the matches were counted first: the busiest tile's growth and the column's, exactly)
-          const int64_t span_room = std::min<int64_t>(cap, (tc.span + 15 + 32 + 15) & ~(int64_t)15);
-          cap_out = (int)((span_room + sized_tilemax * growth + 127) & ~(int64_t)127);
-          extra = sized_total * growth + 64;
-        } else if (roomy) {
-          const int64_t worst = ((int64_t)cap * rb + minlen_p - 1) / minlen_p;
-          cap_out = std::max(cap_out, (int)((std::min<int64_t>(worst, 3ll * cap) + 127) & ~(int64_t)127));
-          const int64_t worst_extra = (col->nbytes * growth + minlen_p - 1) / minlen_p;
-          extra = std::min(worst_extra, std::max<int64_t>(extra, col->nbytes));
-          if (empties) {  // every character and every row end may take a replacement
-            cap_out = (int)(((int64_t)cap * (1 + rb) + 64 * rb + 127) & ~(int64_t)127);
-            extra = col->nbytes * rb + rows * rb;
-          }
-        }
-        // the unit scan (k_tdfa_replace_stream<.., UNITS>): patterns whose tagged DFA offers the decomposition, no limit
-        // on the number of replacements, rows within the 96-byte masks
-        // (not for the literal needles of cs_replace: short needles match densely, and then the per-row kernel with its
-        // in-place compaction is the faster one -- 'ab' -> 'x' on the C2 column: 1.25 against 1.77 ms)
-        // replace_with_backrefs on this kernel (cs_replace_with_backrefs left its template in g_backrefs_dev): the unit
-        // scan, groups carried by the DFA (four at most), tables in LDS
-        const bool brefs = cs::g_backrefs_dev != nullptr;
-        // (a chain without a unit decomposition has no route for sub-tiles with bytes >= 0x80 in this form: only on columns whose sample is plain ASCII)
-        if (brefs && !(((re->tdfa[31] & 1) != 0 || (((re->tdfa[30] >> 16) & 15) != 0 && ((re->tdfa[30] >> 20) & 1) != 0 && !sample_has_high_bytes(col, s))) && !tc.lng && tc.R == 64 && tp.d.in_lds && !re->gtags.empty() && re->prog.num_groups <= cstd::Tdfa::kGroupBatch &&
-                       re->gtags.size() * 4 <= 8 * 1024))
-          return -1;
-        const bool literal = !brefs && !outliers && cs::g_replace_plain_only && cs::g_replace_literal_len > 0 && maxrepl < 0 && !tc.lng && tc.R == 64 && !cs::cfg("CS_NO_LITERAL_SCAN");
-        const bool offers = (re->tdfa[31] & 1) != 0 || ((re->tdfa[30] >> 16) & 15) != 0;  // (units, or a chain pattern without them: one with a suffix)
-        // the bit-parallel form (regex_bits.h): patterns whose candidates are everywhere -- a bitmap per character class (it
-        // builds on the unit forms' layout and assembly, whether or not the pattern offers a unit decomposition)
-        const bool bits_form = !literal && !brefs && !wide_stream && tdfa && maxrepl < 0 && !tc.lng && tc.R == 64 && !outliers && !cs::g_replace_plain_only && tp.d.in_lds &&
-                               bits_route(re, col, s, BITS_REPLACE, holes_ok);
-        // replace_with_backrefs on a chain whose groups are runs of items, the sample plain ASCII: the form that keeps neither
-        // tables nor group tags in LDS (k_tdfa_replace_stream<.., BREFS, .., CHAIN>).  Its out tile is sized from the
-        // template: an expansion is the template's literal bytes plus the groups it names, so a match grows by at most
-        //   G = literal bytes + sum over items of (times the item is named - 1) * its length
-        // -- with every item named at most once, G = literal bytes - the least length of the items NOT named, often <= 0
-        // (`\4.\3.\2.\1` on four dotted groups: 3 - 3).  An item named twice and unbounded leaves the old "twice the input".
-        bool bchain = false;
-        int64_t brefs_grow = -1;  // per match; -1: unknown
-        if (brefs && ((re->tdfa[30] >> 16) & 15) != 0 && ((re->tdfa[30] >> 20) & 1) != 0 && !tc.lng && tc.R == 64 && maxrepl < 0 &&
-            cs::g_backrefs_host && !cs::cfg("CS_NO_BREFS_CHAIN") && !sample_has_high_bytes(col, s)) {
-          const auto* ht = static_cast<const csvm::BackrefTemplate*>(cs::g_backrefs_host);
-          const cstd::View hv = cstd::make_view(re->tdfa.data());
-          const int ni = (int)((hv.chain >> 16) & 15u);
-          const unsigned long long hcrep = cstd::chain_crep(re->tdfa.data());
-          const uint32_t gmap = (uint32_t)re->tdfa[re->tdfa[15] - 1];
-          int named[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-          for (int j = 0; j < ht->nrefs; ++j) {
-            const int g = ht->idx[j];
-            int lo = 0, hi = 0;
-            if (g == 0) hi = ni;
-            else if (g <= 4 && g <= ht->groups) lo = (int)((gmap >> (8 * (g - 1))) & 15u), hi = (int)((gmap >> (8 * (g - 1) + 4)) & 15u);
-            for (int k = lo; k < hi && k < 8; ++k) ++named[k];
-          }
-          int64_t G = ht->bytes;
-          bool bounded_g = true;
-          for (int k = 0; k < ni && k < 8; ++k) {
-            const int least = (int)(cstd::chain_rep(hcrep, k) & 15u), most = (int)(cstd::chain_rep(hcrep, k) >> 4);
-            if (named[k] == 0) G -= least;
-            else if (named[k] > 1) {
-              if (most == 0) bounded_g = false;
-              else G += (int64_t)(named[k] - 1) * most;
-            }
-          }
-          bchain = true;
-          if (bounded_g) brefs_grow = std::max<int64_t>(G, 0);
-        }
-        const bool units = literal || brefs || bits_form || (offers && maxrepl < 0 && !tc.lng && tc.R == 64 && !outliers && !cs::g_replace_plain_only && !cs::cfg("CS_NO_UNITS"));
-        const int bits_k = bits_form ? std::max(re->bits[1], 2) : 2;
-        const size_t bits_lds = bits_form ? (size_t)bits_lds_bytes((int)re->bits.size()) : 0;
-        // (a chain pattern on a column whose sample is plain ASCII: the form without the unit / lean scans)
-        const bool chain_form = !bits_form && !brefs && !wide_stream && !outliers && units && cap <= 5 * 1024 && tp.d.in_lds && !literal && maxrepl < 0 &&
-                                ((re->tdfa[30] >> 16) & 15) != 0 && (!sample_has_high_bytes(col, s) || holes_ok) && !cs::cfg("CS_NO_CHAIN_FORM");
-        // (the kernel's layout, k_tdfa_replace_stream: a bitmap's bytes, what stands behind the first one)
-        const size_t bm = (size_t)(cap >> 3) + (bits_form ? 16 : 32);
-        const size_t unit_bytes = bchain                      ? bm + 16 + kUnitQueue * 12
-                                  : (chain_form || bits_form) ? (size_t)(bits_k - 1) * bm + 16
-                                  : units                     ? (size_t)(bits_k - 1) * bm + kUnitQueue * 4 + 16 + (cs::g_backrefs_dev ? kUnitQueue * 12 + 64 * 4 : 0)
-                                                              : 0;
-        // (backrefs: the group tags and the template text sit behind the DFA table; the template may grow a row by any
-        // amount: room for twice the input, a launch that needs more says so and the two-pass form takes over)
-        const size_t gt_bytes = brefs ? (bchain ? 0 : ((re->gtags.size() * 4 + 15) & ~size_t(15))) + (((size_t)cs::g_backrefs_text_bytes + 31) & ~size_t(15)) : 0;
-        if (brefs && brefs_grow >= 0) {
-          // (at most span / minlen matches in a sub-tile, each growing by at most brefs_grow bytes -- the roomy sizing; the first
-          // attempt provisions a quarter of the input instead when that is less: `(\d+)` -> `<\1>` may triple a row of digits
-          // and spaces, and adds a sixth to a log line -- at the worst case's 84 KB of LDS one workgroup fits a CU, 48.8 ms on the
-          // C3 column; a launch that runs out of room says so and the roomy one follows)
-          const int64_t span_room = std::min<int64_t>(cap, (tc.span + 15 + 32 + 15) & ~(int64_t)15);
-          int64_t tile_grow = (tc.span / minlen_p + 1) * brefs_grow, col_grow = (col->nbytes / minlen_p + 1) * brefs_grow;
-          if (!roomy) {
-            tile_grow = std::min<int64_t>(tile_grow, std::max<int64_t>(tc.span / 4, 256));
-            col_grow = std::min<int64_t>(col_grow, col->nbytes / 4 + (1 << 20));
-          }
-          cap_out = (int)((span_room + tile_grow + (tile_grow ? 127 : 0)) & ~(int64_t)(tile_grow ? 127 : 15));
-          extra = col_grow;
-        } else if (brefs) {
-          cap_out = std::max(cap_out, 2 * cap);
-          extra = std::max<int64_t>(extra, col->nbytes);
-        }
-        // The chain arithmetic reads no table: when the tables are what keeps a third workgroup off the CU (the 26-instruction
-        // dotted quad with `\b` and {1,3}: 36 states, 19 KB), they stay in memory -- only a sub-tile the arithmetic does not take
-        // (bytes >= 0x80, a row beyond the masks) walks them there, and the sample says those are rare.
-        const size_t tile_lds = gt_bytes + bits_lds + (size_t)(cap + cap_out + 64 + bm + unit_bytes) * 4 + 16;
-        constexpr size_t kThird = 160 * 1024 / 3;
-        // (the bit form likewise: its kernel with the tables in memory is built for three workgroups a CU -- 168 registers)
-        // (... whenever its tile leaves room for three, whatever the tables' size: the form with the tables in LDS is the 189-register
-        // one -- for patterns of up to five classes: the gtest pattern's seven fit a third workgroup too once the layout was trimmed,
-        // but its evaluation then spills where it hurts: 8.4 against 7.1 ms)
-        const bool chain_global = ((chain_form && tbl + tile_lds > kThird && tile_lds + cstd::kHeadTailWords * 4 <= kThird) ||
-                                   (bits_form && re->bits[1] <= 5 && tile_lds + cstd::kHeadTailWords * 4 <= kThird) || ((chain_form || bits_form) && cs::cfg("CS_CHAIN_TABLES_IN_MEMORY"))) &&
-                                  !cs::cfg("CS_CHAIN_TABLES_IN_LDS");
-        const size_t tbl_lds = (chain_global || bchain) ? (size_t)cstd::kHeadTailWords * 4 : tbl;  // (header + tail words: tsetup)
-        const size_t lds1 = tbl_lds + tile_lds;
-        if (lds1 > 150 * 1024) return -1;
-        StreamArgs sa{};
-        sa.in = view_of(col);
-        sa.flags = d_unicode_flags();
-        sa.L = tp.d;
-        if (chain_global || bchain) sa.L.in_lds = 2;
-        sa.repl = ptr<const uint8_t>(d_repl);
-        sa.rb = rb;
-        sa.maxrepl = maxrepl;
-        Buf out_off = dev_alloc(sizeof(int64_t) * (rows + 1), s);
-        Buf out_chars = dev_alloc((size_t)col->nbytes + (size_t)extra + 64, s);
-        sa.out_off = ptr<int64_t>(out_off);
-        sa.out_chars = ptr<uint8_t>(out_chars);
-        sa.out_cap = col->nbytes + extra;
-        const int64_t nsub1 = (rows + tc.R - 1) / tc.R;
-        sa.rows_per_tile = tc.R;
-        // [aggregates nsub1][error word + phase counters 16][tickets 128: sixteen counters][exclusive prefixes nsub1]
-        // (+ kScanBatch windows of slack: the scanner wave fetches whole batches)
-        const size_t status_bytes = sizeof(cstile::u64) * (2 * (size_t)nsub1 + 16 + 128 + 64 * cstile::kScanBatch);
-        Buf status = dev_alloc(status_bytes, s);
-        CS_HIP(hipMemsetAsync(status->p, 0, status_bytes, s));
-        sa.status = ptr<cstile::u64>(status);
-        sa.error = reinterpret_cast<unsigned*>(ptr<cstile::u64>(status) + nsub1);
-        sa.tickets = ptr<cstile::u64>(status) + nsub1 + 16;
-        sa.excl = ptr<cstile::u64>(status) + nsub1 + 16 + 128;
-        sa.nsub = nsub1;
-        sa.cap_in = cap;
-        sa.cap_out = cap_out;
-        sa.tbl_bytes = (int)(tbl_lds + gt_bytes + bits_lds);
-        sa.bits = bits_form ? ptr<const int32_t>(re->d_bits) : nullptr;
-        sa.bits_off = (int)(tbl_lds + gt_bytes);
-        sa.bits_words = bits_form ? (int)re->bits.size() : 0;
-        sa.bits_k = bits_form ? re->bits[1] : 0;
-        sa.tmpl = static_cast<const csvm::BackrefTemplate*>(cs::g_backrefs_dev);
-        sa.gtags = brefs ? ptr<const int32_t>(re->d_gtags) : nullptr;
-        sa.gt_off = (int)tbl_lds;
-        sa.gt_words = brefs && !bchain ? (int)re->gtags.size() : 0;
-        sa.debug = cs::cfg_int("CS_TILE_DEBUG", 0);
-        sa.outliers = outliers ? 1 : 0;
-        sa.lit = literal ? cs::g_replace_literal : 0;
-        sa.litn = literal ? cs::g_replace_literal_len : 0;
-        const OddRows* od = holes_ok && !literal && !brefs ? odd_rows(col, s) : nullptr;
-        const bool with_holes = od && od->count > 0;
-        const unsigned hole_grid = with_holes ? (unsigned)std::min<int64_t>((od->count + 255) / 256, 2048) : 0;
-        const size_t list_lds = tp.lds_bytes + (size_t)256 * kListRowBytes;  // (the tables and a row a thread)
-        if (with_holes) {
-          if (list_lds > 48 * 1024) {
-            CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tdfa_replace_list<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)list_lds));
-            CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tdfa_replace_list<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)list_lds));
-          }
-          if (!hole_lens) {
-            hole_lens = dev_alloc(sizeof(int32_t) * (size_t)od->count, s);
-            ProfScope ps("k_tdfa_replace_list", s);
-            hipLaunchKernelGGL(k_tdfa_replace_list<false>, dim3(hole_grid), dim3(256), list_lds, s, src, tp.d, ptr<const int32_t>(od->list), od->count, ptr<const uint8_t>(d_repl), rb,
-                               ptr<int32_t>(hole_lens), (const int64_t*)nullptr, (uint8_t*)nullptr);
-            CS_HIP(hipGetLastError());
-          }
-          sa.hole_mask = ptr<const unsigned long long>(od->mask);
-          sa.hole_first = ptr<const int64_t>(od->first);
-          sa.hole_len = ptr<const int32_t>(hole_lens);
-        }
-        // (tables in LDS: a DFA beyond the LDS budget left this function above -- the forms with the tables in memory that are
-        // not chain forms were never reached by a test and spilled 20-60 registers: out since round 6, kernel_coverage.txt)
-        auto pick2 = [&](auto inplace, auto rescan, auto lng) {
-          constexpr bool IP = decltype(inplace)::value, RS = decltype(rescan)::value, LG = decltype(lng)::value;
-          return rb > 8 ? &k_tdfa_replace_stream<true, true, IP, RS, LG> : &k_tdfa_replace_stream<true, false, IP, RS, LG>;
-        };
-        // rows beyond the 96-byte candidate masks (and up to 255 bytes) take the sliding-window form
-        const bool lng = tc.lng;
-        auto pick = [&](auto inplace, auto rescan) {
-          return lng ? pick2(inplace, rescan, std::true_type{}) : pick2(inplace, rescan, std::false_type{});
-        };
-        auto kern = growth == 0 ? pick(std::true_type{}, std::false_type{})
-                                : roomy ? pick(std::false_type{}, std::true_type{}) : pick(std::false_type{}, std::false_type{});
-        if (outliers) {  // (the forms that handle oversize sub-tiles: in place, or with the rescan assembly)
-          constexpr int P6 = cstile::kPfChunks;
-          if (growth == 0) kern = rb > 8 ? &k_tdfa_replace_stream<true, true, true, false, false, false, P6, false, false, true>
-                                         : &k_tdfa_replace_stream<true, false, true, false, false, false, P6, false, false, true>;
-          else kern = rb > 8 ? &k_tdfa_replace_stream<true, true, false, true, false, false, P6, false, false, true>
-                             : &k_tdfa_replace_stream<true, false, false, true, false, false, P6, false, false, true>;
-        } else if (wide_stream) {
-          constexpr int P6 = cstile::kPfChunks;
-          if (rb <= 8) {
-            if (growth == 0) kern = lng ? &k_tdfa_replace_stream<true, false, true, false, true, false, P6, false, true> : &k_tdfa_replace_stream<true, false, true, false, false, false, P6, false, true>;
-            else kern = lng ? &k_tdfa_replace_stream<true, false, false, true, true, false, P6, false, true> : &k_tdfa_replace_stream<true, false, false, true, false, false, P6, false, true>;
-          } else {
-            if (growth == 0) kern = lng ? &k_tdfa_replace_stream<true, true, true, false, true, false, P6, false, true> : &k_tdfa_replace_stream<true, true, true, false, false, false, P6, false, true>;
-            else kern = lng ? &k_tdfa_replace_stream<true, true, false, true, true, false, P6, false, true> : &k_tdfa_replace_stream<true, true, false, true, false, false, P6, false, true>;
-          }
-        } else if (bchain)
-          kern = cap <= 5 * 1024 ? &k_tdfa_replace_stream<false, false, false, true, false, true, 5, true, false, false, true>
-                                 : &k_tdfa_replace_stream<false, false, false, true, false, true, cstile::kPfChunks, true, false, false, true>;
-        else if (brefs)
-          kern = cap <= 5 * 1024 ? &k_tdfa_replace_stream<true, false, false, true, false, true, 5, true> : &k_tdfa_replace_stream<true, false, false, true, false, true, cstile::kPfChunks, true>;
-        else if (bits_form && chain_global)
-          kern = rb > 8 ? &k_tdfa_replace_stream<false, true, false, true, false, true, cstile::kPfChunks, false, false, false, true, true>
-                        : &k_tdfa_replace_stream<false, false, false, true, false, true, cstile::kPfChunks, false, false, false, true, true>;
-        else if (bits_form)
-          kern = rb > 8 ? &k_tdfa_replace_stream<true, true, false, true, false, true, cstile::kPfChunks, false, false, false, true, true>
-                        : &k_tdfa_replace_stream<true, false, false, true, false, true, cstile::kPfChunks, false, false, false, true, true>;
-        else if (chain_form && chain_global)
-          kern = rb > 8 ? &k_tdfa_replace_stream<false, true, false, true, false, true, 5, false, false, false, true>
-                        : &k_tdfa_replace_stream<false, false, false, true, false, true, 5, false, false, false, true>;
-        else if (chain_form)
-          kern = rb > 8 ? &k_tdfa_replace_stream<true, true, false, true, false, true, 5, false, false, false, true>
-                        : &k_tdfa_replace_stream<true, false, false, true, false, true, 5, false, false, false, true>;
-        else if (units && cap <= 5 * 1024 && with_holes)
-          kern = rb > 8 ? &k_tdfa_replace_stream<true, true, false, true, false, true, 5> : &k_tdfa_replace_stream<true, false, false, true, false, true, 5>;
-        else if (units && with_holes)
-          kern = rb > 8 ? &k_tdfa_replace_stream<true, true, false, true, false, true> : &k_tdfa_replace_stream<true, false, false, true, false, true>;
-        else if (units && cap <= 5 * 1024)
-          kern = rb > 8 ? &k_tdfa_replace_stream<true, true, false, true, false, true, 5, false, false, false, false, false, false>
-                        : &k_tdfa_replace_stream<true, false, false, true, false, true, 5, false, false, false, false, false, false>;
-        else if (units)
-          kern = rb > 8 ? &k_tdfa_replace_stream<true, true, false, true, false, true, cstile::kPfChunks, false, false, false, false, false, false>
-                        : &k_tdfa_replace_stream<true, false, false, true, false, true, cstile::kPfChunks, false, false, false, false, false, false>;
-        note_route(bits_form ? "bits" : bchain ? "brefs-chain" : brefs ? "brefs" : literal ? "literal" : wide_stream ? "wide" : units ? (((re->tdfa[30] >> 16) & 15) != 0 ? "chain" : "units") : "plain");
-        if (with_holes) note_route_put_off();
-#if defined(CS_PHASE_PROF)
-        Buf tracebuf;
-        const long long ntrace = (nsub1 >> 10) + 1;
-        {
-          unsigned long long* tp_ = nullptr;
-          if (cs::cfg("CS_REPLACE_TRACE")) {
-            tracebuf = dev_alloc(sizeof(unsigned long long) * 4 * ntrace, s);
-            CS_HIP(hipMemsetAsync(tracebuf->p, 0, sizeof(unsigned long long) * 4 * ntrace, s));
-            tp_ = ptr<unsigned long long>(tracebuf);
-          }
-          CS_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(cstile::g_tile_trace), &tp_, sizeof(tp_), 0, hipMemcpyHostToDevice, s));
-        }
-#endif
-        unsigned grid;
-        {
-          ProfScope ps("k_replace_re", s);
-          grid = launch_resident(kern, lds1, (nsub1 + 3) / 4, s, sa);
-        }
-        if (cs::cfg("CS_STREAM_INFO"))
-          fprintf(stderr, "replace stream: grid %u lds %zu (tables %zu, tile %d + %d) rows/tile %d units %d chain %d wide %d brefs %d roomy %d growth %d rb %d\n", grid, lds1, tbl_lds + gt_bytes, cap, cap_out,
-                  tc.R, (int)units, bchain ? 3 : chain_form ? (chain_global ? 2 : 1) : 0, (int)wide_stream, (int)brefs, (int)roomy, (int)growth, rb);
-        int64_t* host = (int64_t*)pinned_scratch(24);
-        CS_HIP(hipMemcpyAsync(host, ptr<int64_t>(out_off) + rows, 8, hipMemcpyDeviceToHost, s));
-        CS_HIP(hipMemcpyAsync(host + 1, sa.error, 4, hipMemcpyDeviceToHost, s));
-        CS_HIP(hipMemcpyAsync(host + 2, reinterpret_cast<unsigned long long*>(sa.error) + 14, 8, hipMemcpyDeviceToHost, s));
-        CS_HIP(hipStreamSynchronize(s));
-#if defined(CS_PHASE_PROF)
-        {
-          unsigned long long ph[12];
-          CS_HIP(hipMemcpy(ph, reinterpret_cast<unsigned long long*>(sa.error) + 1, sizeof(ph), hipMemcpyDeviceToHost));
-          if (tracebuf) {
-            std::vector<unsigned long long> tr(4 * ntrace);
-            CS_HIP(hipMemcpy(tr.data(), tracebuf->p, sizeof(unsigned long long) * 4 * ntrace, hipMemcpyDeviceToHost));
-            unsigned long long t0 = ~0ull;
-            for (long long i = 0; i < ntrace; ++i)
-              if (tr[4 * i]) t0 = std::min(t0, tr[4 * i]);
-            fprintf(stderr, "trace (us since the first publish; every 1024th sub-tile): tile published scanned start-of-finish prefix-seen\n");
-            for (long long i = 0; i < ntrace; i += std::max<long long>(1, ntrace / 40))
-              fprintf(stderr, "trace %8lld %9.1f %9.1f %9.1f %9.1f\n", i << 10, (double)(tr[4 * i] - t0) / 100.0, (double)(tr[4 * i + 1] - t0) / 100.0,
-                      (double)(tr[4 * i + 2] - t0) / 100.0, (double)(tr[4 * i + 3] - t0) / 100.0);
-          }
-          unsigned long long lb[4] = {0, 0, 0, 0};
-          CS_HIP(hipMemcpyFromSymbol(lb, HIP_SYMBOL(cstile::g_lb_stats), sizeof(lb)));
-          fprintf(stderr, "look-back (cumulative): %llu calls, %.2f windows per call, %.2f re-polls per call\n", lb[0], (double)lb[1] / (double)(lb[0] ? lb[0] : 1),
-                  (double)lb[2] / (double)(lb[0] ? lb[0] : 1));
-          const double waves = (double)grid * 4;
-          fprintf(stderr, "stage split: wait+lds %.0f classify %.0f rest %.0f | ", ph[9] / waves / (nsub1 / waves), ph[10] / waves / (nsub1 / waves), ph[0] / waves / (nsub1 / waves));
-          fprintf(stderr, "phase cycles/wave-iteration: stage %.0f scan %.0f (units: discovery %.0f rounds %.0f) wscan+publish %.0f finish_prev(offsets+flush) %.0f assemble %.0f tail %.0f lookback %.0f (iters/wave %.1f)\n",
-                  ph[0] / waves / (nsub1 / waves), ph[1] / waves / (nsub1 / waves), ph[7] / waves / (nsub1 / waves), ph[8] / waves / (nsub1 / waves), ph[2] / waves / (nsub1 / waves),
-                  ph[3] / waves / (nsub1 / waves), ph[4] / waves / (nsub1 / waves), ph[5] / waves / (nsub1 / waves), ph[6] / waves / (nsub1 / waves), nsub1 / waves);
-        }
-#endif
-        const int err = (int)(uint32_t)host[1];
-        if (err != 0 && cs::cfg("CS_DUMP_STATUS")) {  // development aid: where did the prefix chain stop?
-          std::vector<cstile::u64> st((size_t)nsub1), ex((size_t)nsub1);
-          CS_HIP(hipMemcpy(st.data(), sa.status, sizeof(cstile::u64) * nsub1, hipMemcpyDeviceToHost));
-          CS_HIP(hipMemcpy(ex.data(), sa.excl, sizeof(cstile::u64) * nsub1, hipMemcpyDeviceToHost));
-          unsigned long long tk[8];
-          CS_HIP(hipMemcpy(tk, sa.tickets, sizeof(tk), hipMemcpyDeviceToHost));
-          fprintf(stderr, "status dump: err %d nsub %lld grid %u ticket0 %llu\n", err, (long long)nsub1, grid, tk[0]);
-          for (int64_t t = 0; t < nsub1 && t < 64; ++t)
-            fprintf(stderr, "  tile %lld: agg flag %u val %llu | excl flag %u val %llu\n", (long long)t, (unsigned)(st[t] >> 62), (unsigned long long)(st[t] & cstile::kValMask),
-                    (unsigned)(ex[t] >> 62), (unsigned long long)(ex[t] & cstile::kValMask));
-        }
-        if (err == 0 && with_holes) {  // the holes' bytes
-          ProfScope ps("k_tdfa_replace_list", s);
-          hipLaunchKernelGGL(k_tdfa_replace_list<true>, dim3(hole_grid), dim3(256), list_lds, s, src, tp.d, ptr<const int32_t>(od->list), od->count, ptr<const uint8_t>(d_repl), rb,
-                             (int32_t*)nullptr, ptr<const int64_t>(out_off), ptr<uint8_t>(out_chars));
-          CS_HIP(hipGetLastError());
-          CS_HIP(hipStreamSynchronize(s));
-        }
-        if (err == 0) {  // (a launch whose error word is set never yields a column, measurement switches or not)
-          o->offsets = out_off;
-          o->chars = out_chars;
-          o->nbytes = host[0];
-          // column metadata as a by-product: the largest 64-row span is the largest sub-tile total the kernel saw; a
-          // replacement no longer than the shortest match cannot lengthen a row (an upper bound serves: the numbers size
-          // staging buffers and pick routes); plain input + plain replacement stays plain
-          if (tc.R == 64) o->max_span64 = host[2];
-          if (growth == 0 && col->max_row >= 0) o->max_row = col->max_row;
-          if (col->high_sample == 0 && !brefs) {
-            bool ascii = true;
-            for (int i = 0; i < rb; ++i) ascii = ascii && (unsigned char)repl[i] < 0x80 && repl[i] != 0;
-            if (ascii) o->high_sample = 0;
-          }
-          *out = b.col.release();
-          return 0;
-        }
-        return err;
-      };
-      // (replacements of 17 .. kMaxStreamRepl bytes ride the four-register variants, their text read from memory at assembly)
-      // (... where a match is long enough for the row not to outgrow the out tile: a 19-byte replacement of one-digit matches
-      // goes to the two-pass kernels at once instead of failing the single pass twice first)
-      // (... or where the sample says matches are few: at most about three candidate bytes a row -- the first attempt is
-      // provisioned for kMaxRec matches a row; `-` -> 35 bytes on the log lines, two or three dashes each: 58 ms on the two-pass
-      // kernels.  A column that has more after all loses one launch before them)
-      const bool few_matches = rb <= kMaxStreamRepl && minlen >= 1 && col->rows > 0 &&
-                               candidate_share(re, col, s) * ((double)col->nbytes / (double)col->rows) <= (double)(kMaxRec - 1);
-      if (lds <= 150 * 1024 && (rb <= 16 || (rb <= kMaxStreamRepl && rb <= 4 * minlen) || few_matches) && tc.R) {
-        const bool roomy_first = growth > 0 && (minlen <= 2 || wide_stream || outliers || cs::cfg("CS_REPLACE_ROOMY"));
-        // A growing replacement for a pattern of one or two bytes (`\d+` -> '<number>', `\d` -> '##'): provisioned for the worst
-        // case the out tile is three times the in tile -- two workgroups a CU -- and the output twice the column (18 ms on the
-        // C3 column where `\d+` -> '#' takes 5.9).  count_re first (2.4 ms) says how many matches the column and its busiest
-        // tile hold: the out tile and the output are sized exactly: 17.9 -> 12.1 ms.
-        // (where the worst case is within three times the in tile anyway -- `\d` -> '##' -- the count only costs: 15.6 -> 17.9 ms)
-        if (roomy_first && rb >= 3 * minlen_p && tdfa && !wide_stream && !outliers && !cs::g_backrefs_dev && !cs::g_replace_plain_only && maxrepl < 0 && !empties && tp.d.in_lds &&
-            !cs::cfg("CS_NO_COUNT_SIZING")) {
-          Buf counts = dev_alloc(sizeof(int32_t) * (size_t)rows, s), stats = dev_alloc(16, s);
-          scan<2>(col, re, nullptr, ptr<int32_t>(counts), 1, s, nullptr, "k_count_re");
-          CS_HIP(hipMemsetAsync(stats->p, 0, 16, s));
-          hipLaunchKernelGGL(k_match_stats, dim3(1024), dim3(256), 0, s, ptr<const int32_t>(counts), rows, tc.R, ptr<unsigned long long>(stats), reinterpret_cast<unsigned*>(ptr<unsigned long long>(stats) + 1));
-          CS_HIP(hipGetLastError());
-          unsigned long long* h = (unsigned long long*)pinned_scratch(16);
-          CS_HIP(hipMemcpyAsync(h, stats->p, 16, hipMemcpyDeviceToHost, s));
-          CS_HIP(hipStreamSynchronize(s));
-          sized_total = (int64_t)h[0];
-          sized_tilemax = (int64_t)(unsigned)h[1];
-          note_route("");
-        }
-        int err = stream_attempt(roomy_first);
-        if (err == 2 && !roomy_first) err = stream_attempt(true);  // only ran out of room: once more, roomier
-        if (err == 0) return;
-        if (err > 0) {  // (counted: cs_fallback_count)
-          // what gave up, in words: the error word's bits and the column's shape (profiles/r04/soak.txt showed "error word 33"
-          // without saying that it is the backrefs form meeting a sub-tile with more than 128 matches)
-          char what[256];
-          snprintf(what, sizeof(what), "%s (error word %d:%s%s%s%s%s%s; %lld rows, longest %lld bytes, largest 64-row span %lld)",
-                   cs::g_backrefs_dev ? "replace_with_backrefs" : "replace_re", err, (err & 1) ? " launch abandoned" : "", (err & 2) ? " out of output room" : "",
-                   (err & 4) ? " a sub-tile beyond the staging buffer" : "", (err & 8) ? " no prefix for a tile" : "", (err & 16) ? " the scanners timed out" : "",
-                   (err & 32) ? " a sub-tile with more than 128 matches or a row handed over by the unit route (the template needs the unit route's masks)" : "",
-                   (long long)col->rows, (long long)col->max_row, (long long)col->max_span64);
-          note_fallback(what);
-        }
-      }
-      // an oversize sub-tile or a look-back timeout: fall through to the two-pass kernels
-    }
-    if (cs::g_replace_plain_only) fail(CS_ERR_INTERNAL, "literal replace: single-pass kernel not applicable");  // cs_replace falls back to its own kernels
-    Buf lens = dev_alloc(sizeof(int32_t) * col->rows, s);
-    {
-      ProfScope ps("k_replace_re_size", s);
-      if (wide && tp.d.in_lds)
-        hipLaunchKernelGGL((k_tdfa_replace_size<true, true>), dim3(tp.grid), dim3(256), tp.lds_bytes, s, src, tp.d, rb, maxrepl,
-                           ptr<int32_t>(lens));
-      else if (wide)
-        hipLaunchKernelGGL((k_tdfa_replace_size<false, true>), dim3(tp.grid), dim3(256), 0, s, src, tp.d, rb, maxrepl,
-                           ptr<int32_t>(lens));
-      else if (tdfa && tp.d.in_lds)
-        hipLaunchKernelGGL(k_tdfa_replace_size<true>, dim3(tp.grid), dim3(256), tp.lds_bytes, s, src, tp.d, rb, maxrepl,
-                           ptr<int32_t>(lens));
-      else if (tdfa)
-        hipLaunchKernelGGL(k_tdfa_replace_size<false>, dim3(tp.grid), dim3(256), 0, s, src, tp.d, rb, maxrepl,
-                           ptr<int32_t>(lens));
-      else if (pl.small)
-        hipLaunchKernelGGL((k_replace_re_size<true>), dim3(pl.grid), dim3(pl.threads), pl.lds_bytes, s, src, pl.d, rb,
-                           maxrepl, ptr<int32_t>(lens));
-      else
-        hipLaunchKernelGGL((k_replace_re_size<false>), dim3(pl.grid), dim3(pl.threads), pl.lds_bytes, s, src, pl.d, rb,
-                           maxrepl, ptr<int32_t>(lens));
-    }
-    CS_HIP(hipGetLastError());
-    b.scan(ptr<int32_t>(lens));
-    b.alloc_chars();
-    {
-      ProfScope ps("k_replace_re_write", s);
-      if (wide && tp.d.in_lds)
-        hipLaunchKernelGGL((k_tdfa_replace_write<true, true>), dim3(tp.grid), dim3(256), tp.lds_bytes, s, src, tp.d,
-                           ptr<const uint8_t>(d_repl), rb, maxrepl, b.off, b.chars);
-      else if (wide)
-        hipLaunchKernelGGL((k_tdfa_replace_write<false, true>), dim3(tp.grid), dim3(256), 0, s, src, tp.d,
-                           ptr<const uint8_t>(d_repl), rb, maxrepl, b.off, b.chars);
-      else if (tdfa && tp.d.in_lds)
-        hipLaunchKernelGGL(k_tdfa_replace_write<true>, dim3(tp.grid), dim3(256), tp.lds_bytes, s, src, tp.d,
-                           ptr<const uint8_t>(d_repl), rb, maxrepl, b.off, b.chars);
-      else if (tdfa)
-        hipLaunchKernelGGL(k_tdfa_replace_write<false>, dim3(tp.grid), dim3(256), 0, s, src, tp.d,
-                           ptr<const uint8_t>(d_repl), rb, maxrepl, b.off, b.chars);
-      else if (pl.small)
-        hipLaunchKernelGGL((k_replace_re_write<true>), dim3(pl.grid), dim3(pl.threads), pl.lds_bytes, s, src, pl.d,
-                           ptr<const uint8_t>(d_repl), rb, maxrepl, b.off, b.chars);
-      else
-        hipLaunchKernelGGL((k_replace_re_write<false>), dim3(pl.grid), dim3(pl.threads), pl.lds_bytes, s, src, pl.d,
-                           ptr<const uint8_t>(d_repl), rb, maxrepl, b.off, b.chars);
-    }
-    CS_HIP(hipGetLastError());
-    CS_HIP(hipStreamSynchronize(s));  // d_repl / arena lifetime
-    *out = b.col.release();
+    *out = cs::replace_re_column(cs::ReplaceCall{col, cre, repl, (int)strlen(repl), maxrepl, S(stream)});
   });
 }
 
@@ -4266,20 +4401,13 @@ int cs_replace_with_backrefs(const cs_column* col, const cs_regex* cre, const ch
       Buf d_t = dev_alloc(sizeof(csvm::BackrefTemplate), s);
       CS_HIP(hipMemcpyAsync(d_t->p, &t, sizeof(t), hipMemcpyHostToDevice, s));
       CS_HIP(hipStreamSynchronize(s));  // (`t` lives on this stack frame)
-      cs::g_backrefs_dev = d_t->p;
-      cs::g_backrefs_text_bytes = t.bytes;
-      cs::g_backrefs_host = &t;
-      cs::g_replace_plain_only = 1;  // (single-pass kernel or nothing)
-      cs_column* fast = nullptr;
-      const int rc = cs_replace_re(col, re, "", -1, stream, &fast);
-      cs::g_backrefs_dev = nullptr;
-      cs::g_backrefs_text_bytes = 0;
-      cs::g_backrefs_host = nullptr;
-      cs::g_replace_plain_only = 0;
-      if (rc == CS_OK) {
-        *out = fast;
-        return;
-      }
+      cs::ReplaceCall call{col, re, "", 0, -1, s};
+      call.tmpl_host = &t;
+      call.tmpl_dev = d_t->p;
+      call.tmpl_text_bytes = t.bytes;
+      call.single_pass_only = true;
+      // (whatever fails in there -- declined, out of room, a HIP error --, the two-pass form below answers)
+      if (guard([&] { *out = cs::replace_re_column(call); }) == CS_OK) return;
     }
     BackrefArgs a{};
     a.src = RowSrc{view_of(col), d_unicode_flags(), col->nbytes + (col->chars && col->chars->capacity ? 64 : 0)};
