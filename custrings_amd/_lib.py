@@ -71,6 +71,9 @@ _PROTOS = {
     "cs_column_null_bitarray": (i32, [vp, vp, i32, i32, vp, P(i64)]),
     "cs_column_from_index": (i32, [vp, i64, i32, i32, vp, P(vp)]),
     "cs_column_create_index": (i32, [vp, vp, i32, vp]),
+    "cs_column_from_csv_buffer": (i32, [vp, i64, i32, C.c_uint, C.c_uint, C.c_uint, vp, P(vp)]),
+    "cs_column_from_csv": (i32, [cp, C.c_uint, C.c_uint, C.c_uint, vp, P(vp)]),
+    "cs_csv_tile_bytes": (i32, []),
     "cs_len": (i32, [vp, vp, i32, vp, P(i64)]),
     "cs_gather": (i32, [vp, vp, i64, i32, vp, P(vp)]),
     "cs_gather_mask": (i32, [vp, vp, i32, vp, P(vp)]),

@@ -115,6 +115,26 @@ __global__ void k_index_make(ColView in, IndexPair* __restrict__ ix) {
   ix[r].n = ok ? (size_t)(in.offsets[r + 1] - in.offsets[r]) : 0;
 }
 
+// the span copy behind create_from_index and from_csv: `spans` are `count` (pointer, length) pairs in device memory
+cs_column* column_from_spans(const void* spans, int64_t count, int sorttype, hipStream_t s) {
+  const IndexPair* ix = static_cast<const IndexPair*>(spans);
+  Buf lens = dev_alloc(sizeof(int32_t) * count, s);
+  hipLaunchKernelGGL(k_index_lengths, dim3(blocks_for(count)), dim3(kBlock), 0, s, ix, count, ptr<int32_t>(lens));
+  Built b = column_from_lengths(ptr<int32_t>(lens), count, true, s);
+  hipLaunchKernelGGL(k_index_copy, dim3(blocks_for(count)), dim3(kBlock), 0, s, ix, count, b.off, ptr<uint8_t>(b.col->chars));
+  CS_HIP(hipGetLastError());
+  hipError_t e = hipStreamSynchronize(s);
+  if (e != hipSuccess) fail(CS_ERR_INVALID_ARG, "nvstrings::create_from_index bad_device_ptr");
+  prefer_offsets32(b.col.get(), s);
+  if (sorttype) {  // NVStringsImpl.cu:252-266: ascending, nulls first
+    cs_column* sorted = nullptr;
+    int st = cs_sort(b.col.get(), sorttype, 1, 1, static_cast<cs_stream>(s), &sorted);
+    if (st != CS_OK) fail(st, cs_last_error());
+    return sorted;
+  }
+  return b.col.release();
+}
+
 // ---- len ------------------------------------------------------------------------------------------
 __global__ void k_len(ColView in, int32_t* __restrict__ out, unsigned long long* __restrict__ total) {
   // (a capped grid, rows a grid apart: one addition to `total` per workgroup of the grid, not per 256 rows -- same-address
@@ -222,22 +242,7 @@ int cs_column_from_index(const void* pairs, int64_t count, int on_device, int so
       return;
     }
     DevArray<IndexPair> ix(static_cast<const IndexPair*>(pairs), count, on_device, s);
-    Buf lens = dev_alloc(sizeof(int32_t) * count, s);
-    hipLaunchKernelGGL(k_index_lengths, dim3(blocks_for(count)), dim3(kBlock), 0, s, ix.d, count, ptr<int32_t>(lens));
-    Built b = column_from_lengths(ptr<int32_t>(lens), count, true, s);
-    hipLaunchKernelGGL(k_index_copy, dim3(blocks_for(count)), dim3(kBlock), 0, s, ix.d, count, b.off, ptr<uint8_t>(b.col->chars));
-    CS_HIP(hipGetLastError());
-    hipError_t e = hipStreamSynchronize(s);
-    if (e != hipSuccess) fail(CS_ERR_INVALID_ARG, "nvstrings::create_from_index bad_device_ptr");
-    prefer_offsets32(b.col.get(), s);
-    if (sorttype) {  // NVStringsImpl.cu:252-266: ascending, nulls first
-      cs_column* sorted = nullptr;
-      int st = cs_sort(b.col.get(), sorttype, 1, 1, stream, &sorted);
-      if (st != CS_OK) fail(st, cs_last_error());
-      *out = sorted;
-      return;
-    }
-    *out = b.col.release();
+    *out = column_from_spans(ix.d, count, sorttype, s);
   });
 }
 

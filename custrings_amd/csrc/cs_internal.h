@@ -325,6 +325,9 @@ cs_category* category_build(const cs_column* col, hipStream_t s);
 // cs_array.hip: rows of `col` at the given device positions; with `null_when_negative` a negative
 // position yields a null row instead of CS_ERR_RANGE
 cs_column* gather_rows(const cs_column* col, const int32_t* d_pos, int64_t n, hipStream_t s, bool null_when_negative = false);
+// cs_array.hip: the column of `count` (pointer, byte length) spans in device memory (std::pair<const char*, size_t>; null
+// pointer = null row), sorted when `sorttype` says so (NVStrings::sorttype bits): create_from_index and from_csv
+cs_column* column_from_spans(const void* spans, int64_t count, int sorttype, hipStream_t s);
 // The output column of an op that sizes its rows first (int32 lengths, negative = null row): the one host tail from
 // lengths to a column.  The constructor makes the column with its row count and nulls; scan() allocates the offsets
 // and scans the lengths into them (the total is the column's nbytes, the scan's metadata goes to the column; no rows:

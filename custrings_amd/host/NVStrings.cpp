@@ -88,6 +88,13 @@ NVStrings* NVStrings::create_from_index(std::pair<const char*, size_t>* strs, un
   check(cs_column_from_index(strs, count, devmem ? 1 : 0, (int)stype, nullptr, &c));
   return adopt(c);
 }
+NVStrings* NVStrings::create_from_csv(const char* csvfile, unsigned int column, unsigned int lines, sorttype stype, bool nullIsEmpty) {  // strings/NVStrings.cu:155-163
+  ensure_device();
+  const unsigned int flags = ((unsigned int)stype & 3u) | (nullIsEmpty ? 8u : 0u);  // util.h:27-29
+  cs_column* c = nullptr;
+  check(cs_column_from_csv(csvfile, column, lines, flags, nullptr, &c));
+  return c ? adopt(c) : nullptr;  // util.cu:45-58: no file, or fewer than 2 bytes
+}
 NVStrings* NVStrings::create_from_offsets(const char* strs, int count, const int* offsets, const unsigned char* nullbitmask, int, bool devmem) {
   ensure_device();
   cs_column* c = nullptr;

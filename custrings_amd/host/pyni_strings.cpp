@@ -40,6 +40,16 @@ static PyObject* n_createFromOffsets(PyObject*, PyObject* args) {  // (sbuf, obu
     return NVStrings::create_from_offsets((const char*)chars.p, count, (const int*)offs.p, (const unsigned char*)nulls.p, ncount, dev);
   });
 }
+static PyObject* n_createFromCSV(PyObject*, PyObject* args) {  // pystrings.cpp:359-374: (csv, column, lines, flags) -> instance or None
+  const char* path = str_arg(args, 0);
+  if (!path) {
+    PyErr_SetString(PyExc_ValueError, "nvstrings: missing parameter");
+    return nullptr;
+  }
+  const std::string csv = path;
+  const unsigned int column = (unsigned int)int_arg(args, 1, 0), lines = (unsigned int)int_arg(args, 2, 0), flags = (unsigned int)int_arg(args, 3, 0);
+  return make_instance([&] { return NVStrings::create_from_csv(csv.c_str(), column, lines, (NVStrings::sorttype)(flags & 3), (flags & 8) != 0); });
+}
 static PyObject* n_create_offsets(PyObject*, PyObject* args) {  // (self, sbuf, obuf, nbuf, bdevmem)
   NVStrings* s = SELF(args);
   if (arg(args, 1) == Py_None || arg(args, 2) == Py_None) {
@@ -962,7 +972,7 @@ static PyObject* n_fillna(PyObject*, PyObject* args) {  // (self, repl): a str, 
 static PyMethodDef s_Methods[] = {
 #define M(n) {#n, n, METH_VARARGS, ""}
     M(n_dropWrapper), M(n_getIPCData), M(n_createFromIPC),
-    M(n_createFromHostStrings), M(n_destroyStrings), M(n_createHostStrings), M(n_createFromOffsets), M(n_createFromNVStrings), M(n_create_offsets),
+    M(n_createFromHostStrings), M(n_destroyStrings), M(n_createHostStrings), M(n_createFromOffsets), M(n_createFromCSV), M(n_createFromNVStrings), M(n_create_offsets),
     M(n_size), M(n_len), M(n_byte_count), M(n_null_count), M(n_set_null_bitmask), M(n_copy), M(n_split), M(n_rsplit), M(n_split_record),
     M(n_rsplit_record), M(n_partition), M(n_rpartition), M(n_replace), M(n_replace_multi), M(n_replace_with_backrefs), M(n_lstrip), M(n_strip),
     M(n_rstrip), M(n_lower), M(n_upper), M(n_find), M(n_rfind), M(n_find_from), M(n_find_multiple), M(n_compare), M(n_match_strings), M(n_startswith), M(n_endswith), M(n_contains), M(n_match), M(n_count), M(n_findall), M(n_findall_record), M(n_extract),

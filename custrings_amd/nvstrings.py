@@ -67,6 +67,37 @@ def from_offsets(sbuf, obuf, scount, nbuf=None, ncount=0, bdevmem=False):
     return nvstrings(out.value)
 
 
+def from_csv(csv, column, lines=0, flags=0):
+    """nvstrings.py:59-100 -- one column (0-based) of a CSV file as an instance (NVStrings::create_from_csv, NVStrings.h:146).
+    The first line is the header; `lines` > 0 limits the rows; flags: 1 sort by length, 2 sort by name, 8 an empty field is an
+    empty string, not a null.  None when the file cannot be opened or holds fewer than 2 bytes."""
+    _lib.ensure_init()
+    out = C.c_void_p()
+    check(lib.cs_column_from_csv(b(str(csv)), int(column), int(lines), int(flags), None, C.byref(out)))
+    return nvstrings(out.value) if out.value else None
+
+
+def from_csv_buffer(buf, column, lines=0, flags=0, count=0):
+    """from_csv over CSV text in memory: a bytes object or numpy uint8 array on the host, or a device tensor / device address
+    (an address needs `count`, its bytes); device text is read where it is, not copied."""
+    _lib.ensure_init()
+    on_device = isinstance(buf, int) or hasattr(buf, "data_ptr")
+    if isinstance(buf, (bytes, bytearray, memoryview)):
+        buf = np.frombuffer(buf, dtype=np.uint8)
+    if isinstance(buf, int):
+        n = int(count)
+    elif on_device:
+        n = int(buf.numel()) * int(buf.element_size())
+    else:
+        buf = np.ascontiguousarray(buf)
+        n = int(buf.nbytes)
+    p, keep = addr(buf) if n else (None, None)
+    out = C.c_void_p()
+    check(lib.cs_column_from_csv_buffer(p, n, 1 if on_device else 0, int(column), int(lines), int(flags), None, C.byref(out)))
+    del keep
+    return nvstrings(out.value)
+
+
 def from_offsets64(chars, offsets, rows, validity=None, bdevmem=False, copy=True):
     """Native ingest (int64 offsets); copy=False wraps caller-owned device buffers."""
     _lib.ensure_init()

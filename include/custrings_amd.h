@@ -190,6 +190,21 @@ int cs_column_null_bitarray(const cs_column* col, uint8_t* bitarray, int empty_i
  * CS_ERR_INVALID_ARG ("bad_device_ptr"). */
 int cs_column_from_index(const void* pairs, int64_t count, int on_device, int sorttype,
                          cs_stream stream, cs_column** out);
+/* NVStrings::create_from_csv (NVStrings.h:146; util.cu:42-169): one column of a CSV text as a strings column.  The
+ * text is `nbytes` bytes up to their first NUL byte, in host or device memory (on_device; device bytes are read where
+ * they are and never written); the first line is the header and yields no row; a line ends at '\r' or '\n' and every
+ * byte 1..31 behind it; `column` is 0-based, fields are cut at ',' outside double quotes; `lines` > 0 limits the rows;
+ * flags: 1 sort by length, 2 sort by name, 8 an empty field is an empty string, not a null row (util.h:27-29).  Both
+ * the line scan and the field walk run on the device.  A text with no line end in front of its first NUL gives an
+ * empty column; a row of 2^31 - 1 bytes or more gives CS_ERR_RANGE. */
+int cs_column_from_csv_buffer(const void* bytes, int64_t nbytes, int on_device, unsigned column, unsigned lines,
+                              unsigned flags, cs_stream stream, cs_column** out);
+/* The same from a file: read whole, one copy to the device.  A file that cannot be opened or holds fewer than 2 bytes
+ * gives CS_OK and *out = NULL (the reference returns a null instance). */
+int cs_column_from_csv(const char* path, unsigned column, unsigned lines, unsigned flags, cs_stream stream,
+                       cs_column** out);
+/* Bytes of the text one workgroup of the line scan takes (tests place their edge cases around multiples of it). */
+int cs_csv_tile_bytes(void);
 /* NVStrings::create_index (NVStrings.h:180; NVStrings.cu:348-400): one (pointer,
  * byte length) pair per row, the pointers addressing the column's own device
  * chars (valid until the handle is destroyed); null row = (NULL, 0). */

@@ -38,6 +38,8 @@ class NVStrings {
   /* ---- construction (NVStrings.h:86-156) ---- */
   static NVStrings* create_from_array(const char** strs, unsigned int count);
   static NVStrings* create_from_index(std::pair<const char*, size_t>* strs, unsigned int count, bool devmem = true, sorttype stype = none);
+  // one column of a CSV file (NVStrings.h:146); null when the file cannot be opened or holds fewer than 2 bytes
+  static NVStrings* create_from_csv(const char* csvfile, unsigned int column, unsigned int lines = 0, sorttype stype = none, bool nullIsEmpty = false);
   static NVStrings* create_from_offsets(const char* strs, int count, const int* offsets, const unsigned char* nullbitmask = 0, int nulls = 0,
                                         bool devmem = true);
   static NVStrings* create_from_strings(std::vector<NVStrings*> strs);

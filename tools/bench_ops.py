@@ -61,7 +61,7 @@ def report(config, op, rows, in_bytes, alg_bytes, dt):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scale", type=float, default=1.0, help="row-count multiplier (1.0 = BASELINE.json single-GPU sizes)")
-    ap.add_argument("--only", default="C2,C3,C4,C5", help="comma-separated configs to run (CONV: the conversion ops, TS: the timestamp ones, PAD: substring / padding / wrapping, CHR: character types and swapcase / capitalize / title, TXT: the NVText matches, edit distance, stemmer measure and scatter_count, URL: url_encode / url_decode / translate / fillna, NUM: the numeric categories -- from_numbers, to_numbers, merge_and_remap -- beside two yardsticks)")
+    ap.add_argument("--only", default="C2,C3,C4,C5", help="comma-separated configs to run (CONV: the conversion ops, TS: the timestamp ones, PAD: substring / padding / wrapping, CHR: character types and swapcase / capitalize / title, TXT: the NVText matches, edit distance, stemmer measure and scatter_count, URL: url_encode / url_decode / translate / fillna, NUM: the numeric categories -- from_numbers, to_numbers, merge_and_remap -- beside two yardsticks, CSV: from_csv -- the line-start kernels, the field locator and the whole call)")
     a = ap.parse_args()
     only = set(a.only.split(","))
     ov = 8.125  # native offset + validity bytes per row
@@ -88,6 +88,8 @@ def main():
         run_url(a)
     if "NUM" in only:
         run_num(a)
+    if "CSV" in only:
+        run_csv(a)
 
 
 def run_c2(a, ov):
@@ -460,6 +462,51 @@ def run_txt(a):
     L.cs_config_set(b"CS_TEXT_ROWWISE", None)
 
 
+
+
+def run_csv(a):
+    """from_csv_buffer on generated text of 2M lines (x --scale): C3-like log lines (one column, no quotes) and a 9-column shape
+    like the reference's tweets file (column 7 quoted, "" pairs inside).  Per shape: the line-start kernels and the field locator
+    by themselves (cs_prof: HIP events around their launches; the locator's figure includes its tile plan), the whole call on
+    device bytes and on host bytes (with its upload), and to_device of the same rows as a Python list.  Beside them, from the
+    same run, the box's read-only stream rate (cs_box_rates)."""
+    import numpy as np
+
+    rates = (C.c_double * 6)()
+    _lib.check(L.cs_box_rates(2048, 3, None, rates))
+    print(json.dumps({"config": "CSV box", "copy_GBps": round(rates[0] * 1e3, 1), "read_GBps": round(rates[1] * 1e3, 1),
+                      "write_GBps": round(rates[2] * 1e3, 1)}), flush=True)
+    lines = int(2_000_000 * a.scale)
+    words = ["alpha", "GET", "/index.html", "HTTP/1.1", "200", "10.0.0.7", "Mozilla/5.0", "nice to know", "paper is the best", "http://t.co/x"]
+    log = ["%d.%d.%d.%d - - [10/Oct/2000:13:55:%02d -0700] \"GET /%s/%s HTTP/1.1\" %d %d" % (k % 223 + 1, k % 251, k % 241, k % 239, k % 60, words[k % 10], words[k % 7], 200 + k % 5, k * 37 % 9973)
+           for k in range(1000)]
+    tweets = ["%d,%d,%s,%s,%d,%d,%s,\"@%s %s, and a \"\"%s\"\" page of %d words\",%s" % (k, k * 7919 % 100003, words[k % 10], words[k % 3], k % 97, k % 89, words[k % 5], words[k % 4], words[7 + k % 2], words[k % 6],
+                                                                                 k % 53, words[k % 8]) for k in range(1000)]
+    for name, block, column in (("log lines", log, 0), ("9 columns, quoted", tweets, 7)):
+        text = ("h0,h1,h2,h3,h4,h5,h6,h7,h8\n" + "\n".join(block * max(1, lines // 1000)) + "\n").encode()
+        n = len(text)
+        host = np.frombuffer(text, dtype=np.uint8)
+        dev = torch.from_numpy(host.copy()).cuda()
+        col = nvstrings.from_csv_buffer(dev, column)
+        rows, out_b = col.size(), nbytes(col)
+        L.cs_prof_reset()
+        L.cs_prof_enable(1)
+        reps = 3
+        for _ in range(reps):
+            nvstrings.from_csv_buffer(dev, column)
+        torch.cuda.synchronize()
+        L.cs_prof_enable(0)
+        for kern, what in ((b"k_csv_line_starts", "line starts (summary + scan + write)"), (b"k_csv_fields", "field locator (with its tile plan)")):
+            ms, k = C.c_double(), C.c_int64()
+            L.cs_prof_get(kern, C.byref(ms), C.byref(k))
+            dt = ms.value / reps / 1e3
+            print(json.dumps({"config": "CSV " + name, "op": what, "rows": rows, "text_bytes": n, "ms": round(dt * 1e3, 3), "text_GBps": round(n / dt / 1e9, 1),
+                              "frac_of_box_read": round(n / dt / 1e9 / (rates[1] * 1e3), 3), "route": L.cs_debug_last_route().decode()}), flush=True)
+        report("CSV " + name, "from_csv_buffer (device bytes)", rows, n, n + out_b + 8.125 * rows, timed(lambda: nvstrings.from_csv_buffer(dev, column)))
+        report("CSV " + name, "from_csv_buffer (host bytes, with the upload)", rows, n, n + out_b + 8.125 * rows, timed(lambda: nvstrings.from_csv_buffer(host, column)))
+        strs = col.to_host()
+        report("CSV " + name, "to_device (the same rows as a list)", rows, out_b, out_b + 8.125 * rows, timed(lambda: nvstrings.to_device(strs), reps=1))
+        del col, dev, strs
 
 
 def run_num(a):
