@@ -253,16 +253,10 @@ int cs_column_create_index(const cs_column* col, void* pairs, int on_device, cs_
     hipStream_t s = S(stream);
     const int64_t rows = col->rows;
     if (rows == 0) return;
-    Buf tmp;
-    IndexPair* d = static_cast<IndexPair*>(pairs);
-    if (!on_device) {
-      tmp = dev_alloc(sizeof(IndexPair) * rows, s);
-      d = ptr<IndexPair>(tmp);
-    }
-    hipLaunchKernelGGL(k_index_make, dim3(blocks_for(rows)), dim3(kBlock), 0, s, view_of(col), d);
+    const ResultsOut res(pairs, sizeof(IndexPair) * rows, on_device, s);
+    hipLaunchKernelGGL(k_index_make, dim3(blocks_for(rows)), dim3(kBlock), 0, s, view_of(col), static_cast<IndexPair*>(res.dev));
     CS_HIP(hipGetLastError());
-    if (!on_device) CS_HIP(hipMemcpyAsync(pairs, d, sizeof(IndexPair) * rows, hipMemcpyDeviceToHost, s));
-    CS_HIP(hipStreamSynchronize(s));
+    res.finish(s);
   });
 }
 
@@ -272,20 +266,12 @@ int cs_len(const cs_column* col, int32_t* lengths, int on_device, cs_stream stre
     hipStream_t s = S(stream);
     if (total) *total = col->rows;  // attrs.cu:35-36: without an output array the call returns the row count
     if (!lengths || col->rows == 0) return;
-    Buf tmp;
-    int32_t* d_out = lengths;
-    if (!on_device) {
-      tmp = dev_alloc(sizeof(int32_t) * col->rows, s);
-      d_out = ptr<int32_t>(tmp);
-    }
-    Buf acc = dev_alloc(8, s);
-    CS_HIP(hipMemsetAsync(acc->p, 0, 8, s));
-    hipLaunchKernelGGL(k_len, dim3(std::min(blocks_for(col->rows), 8192u)), dim3(kBlock), 0, s, view_of(col), d_out, ptr<unsigned long long>(acc));
-    if (!on_device) CS_HIP(hipMemcpyAsync(lengths, d_out, sizeof(int32_t) * col->rows, hipMemcpyDeviceToHost, s));
-    int64_t* host = (int64_t*)pinned_scratch(8);
-    CS_HIP(hipMemcpyAsync(host, acc->p, 8, hipMemcpyDeviceToHost, s));
-    CS_HIP(hipStreamSynchronize(s));
-    if (total) *total = host[0];
+    const ResultsOut res(lengths, sizeof(int32_t) * col->rows, on_device, s);
+    const Buf acc = zeroed_count(s);
+    hipLaunchKernelGGL(k_len, dim3(std::min(blocks_for(col->rows), 8192u)), dim3(kBlock), 0, s, view_of(col), static_cast<int32_t*>(res.dev), ptr<unsigned long long>(acc));
+    res.copy_back(s);
+    const int64_t n = read_count(acc, s);
+    if (total) *total = n;
   });
 }
 

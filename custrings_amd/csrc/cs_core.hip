@@ -1688,17 +1688,11 @@ int cs_column_byte_count(const cs_column* col, int32_t* lengths, int on_device, 
     hipStream_t s = S(stream);
     if (total) *total = 0;
     if (col->rows == 0) return;
-    Buf tmp;
-    int32_t* d_out = lengths;
-    if (!on_device || !lengths) {
-      tmp = dev_alloc(sizeof(int32_t) * col->rows, s);
-      d_out = ptr<int32_t>(tmp);
-    }
+    const ResultsOut res(lengths, sizeof(int32_t) * col->rows, on_device && lengths, s);  // (without `lengths`: a temporary nobody fills)
     // (null rows have zero extent, so the total is the column's byte count: no reduction)
     if (lengths) {
-      hipLaunchKernelGGL(k_lengths_from_offsets, dim3(blocks_for(col->rows)), dim3(kBlock), 0, s, view_of(col), d_out);
-      if (!on_device) copy_out(lengths, d_out, sizeof(int32_t) * col->rows, 0, s);
-      CS_HIP(hipStreamSynchronize(s));
+      hipLaunchKernelGGL(k_lengths_from_offsets, dim3(blocks_for(col->rows)), dim3(kBlock), 0, s, view_of(col), static_cast<int32_t*>(res.dev));
+      res.finish(s);
     }
     if (total) *total = col->nbytes;
   });
@@ -1712,21 +1706,13 @@ int cs_column_null_bitarray(const cs_column* col, uint8_t* bitarray, int empty_i
     if (null_count) *null_count = 0;
     if (col->rows == 0) return;
     size_t nb = (size_t)((col->rows + 7) / 8);
-    Buf tmp;
-    uint8_t* d_bits = bitarray;
-    if (!on_device) {
-      tmp = dev_alloc(nb, s);
-      d_bits = ptr<uint8_t>(tmp);
-    }
-    Buf cnt = dev_alloc(8, s);
-    CS_HIP(hipMemsetAsync(cnt->p, 0, 8, s));
+    const ResultsOut res(bitarray, nb, on_device, s);
+    const Buf cnt = zeroed_count(s);
     hipLaunchKernelGGL(k_null_bitarray, dim3(blocks_for((int64_t)nb)), dim3(kBlock), 0, s, view_of(col),
-                       empty_is_null, d_bits, ptr<unsigned long long>(cnt));
-    if (!on_device) copy_out(bitarray, d_bits, nb, 0, s);
-    int64_t* host = (int64_t*)pinned_scratch(8);
-    CS_HIP(hipMemcpyAsync(host, cnt->p, 8, hipMemcpyDeviceToHost, s));
-    CS_HIP(hipStreamSynchronize(s));
-    if (null_count) *null_count = host[0];
+                       empty_is_null, static_cast<uint8_t*>(res.dev), ptr<unsigned long long>(cnt));
+    res.copy_back(s);
+    const int64_t n = read_count(cnt, s);
+    if (null_count) *null_count = n;
   });
 }
 

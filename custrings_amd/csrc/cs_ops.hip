@@ -499,13 +499,9 @@ int cs_find(const cs_column* col, const char* str, int start, int end, int32_t* 
     require_device();
     hipStream_t s = S(stream);
     Needle nd = upload(str, s);
-    Buf tmp, cnt = dev_alloc(8, s);
-    CS_HIP(hipMemsetAsync(cnt->p, 0, 8, s));
-    int32_t* d_out = results;
-    if (!on_device) {
-      tmp = dev_alloc(sizeof(int32_t) * col->rows, s);
-      d_out = ptr<int32_t>(tmp);
-    }
+    const Buf cnt = zeroed_count(s);
+    const ResultsOut res(results, sizeof(int32_t) * col->rows, on_device, s);
+    int32_t* d_out = static_cast<int32_t*>(res.dev);
     {
       ProfScope ps("k_find", s);
       if (!find_tiles(col, reinterpret_cast<const unsigned char*>(str), nd.n, 0, start, end, d_out, nullptr,
@@ -513,9 +509,8 @@ int cs_find(const cs_column* col, const char* str, int start, int end, int32_t* 
         hipLaunchKernelGGL(k_find, dim3(std::min(blocks_for(col->rows), 8192u)), dim3(kBlock), 0, s, view_of(col), nd.d(),
                            nd.n, start, end, d_out, ptr<unsigned long long>(cnt));
     }
-    if (!on_device)
-      CS_HIP(hipMemcpyAsync(results, d_out, sizeof(int32_t) * col->rows, hipMemcpyDeviceToHost, s));
-    int64_t n = read_back<int64_t>(cnt, s);
+    res.copy_back(s);
+    const int64_t n = read_count(cnt, s);
     if (found) *found = n;
   });
 }
@@ -595,14 +590,10 @@ static void find_family(const cs_column* col, int op, const char* str, int start
   const int64_t rows = col->rows;
   const bool bools = op >= 3;
   Needle nd = upload(str, s);
-  Buf tmp, cnt = dev_alloc(8, s), sbuf, ebuf;
-  CS_HIP(hipMemsetAsync(cnt->p, 0, 8, s));
-  void* d_out = results;
-  const size_t esz = bools ? 1 : sizeof(int32_t);
-  if (!on_device) {
-    tmp = dev_alloc(esz * rows, s);
-    d_out = tmp->p;
-  }
+  const Buf cnt = zeroed_count(s);
+  Buf sbuf, ebuf;
+  const ResultsOut res(results, (bools ? 1 : sizeof(int32_t)) * rows, on_device, s);
+  void* d_out = res.dev;
   if (starts && !bounds_on_device) {
     sbuf = dev_alloc(sizeof(int32_t) * rows, s);
     CS_HIP(hipMemcpyAsync(sbuf->p, starts, sizeof(int32_t) * rows, hipMemcpyHostToDevice, s));
@@ -619,8 +610,8 @@ static void find_family(const cs_column* col, int op, const char* str, int start
                        bools ? nullptr : static_cast<int32_t*>(d_out), bools ? static_cast<uint8_t*>(d_out) : nullptr, ptr<unsigned long long>(cnt));
   }
   CS_HIP(hipGetLastError());
-  if (!on_device) CS_HIP(hipMemcpyAsync(results, d_out, esz * rows, hipMemcpyDeviceToHost, s));
-  const int64_t n = read_back<int64_t>(cnt, s);  // (synchronises: the staged bounds and the needle may go)
+  res.copy_back(s);
+  const int64_t n = read_count(cnt, s);  // (synchronises: the staged bounds and the needle may go)
   if (found) *found = n;
 }
 
@@ -681,17 +672,13 @@ int cs_match_strings(const cs_column* col, const cs_column* other, uint8_t* resu
     if (col->rows != other->rows) fail(CS_ERR_INVALID_ARG, "sizes must match");
     require_device();
     hipStream_t s = S(stream);
-    Buf tmp, cnt = dev_alloc(8, s);
-    CS_HIP(hipMemsetAsync(cnt->p, 0, 8, s));
-    uint8_t* d_out = results;
-    if (!on_device) {
-      tmp = dev_alloc((size_t)col->rows, s);
-      d_out = ptr<uint8_t>(tmp);
-    }
-    hipLaunchKernelGGL(k_match_strings, dim3(std::min(blocks_for(col->rows), 8192u)), dim3(kBlock), 0, s, view_of(col), view_of(other), d_out, ptr<unsigned long long>(cnt));
+    const Buf cnt = zeroed_count(s);
+    const ResultsOut res(results, (size_t)col->rows, on_device, s);
+    hipLaunchKernelGGL(k_match_strings, dim3(std::min(blocks_for(col->rows), 8192u)), dim3(kBlock), 0, s, view_of(col), view_of(other), static_cast<uint8_t*>(res.dev),
+                       ptr<unsigned long long>(cnt));
     CS_HIP(hipGetLastError());
-    if (!on_device) CS_HIP(hipMemcpyAsync(results, d_out, (size_t)col->rows, hipMemcpyDeviceToHost, s));
-    const int64_t n = read_back<int64_t>(cnt, s);
+    res.copy_back(s);
+    const int64_t n = read_count(cnt, s);
     if (matches) *matches = n;
   });
 }
@@ -704,18 +691,14 @@ int cs_find_multiple(const cs_column* col, const cs_column* targets, int32_t* re
     require_device();
     hipStream_t s = S(stream);
     const int64_t total = col->rows * targets->rows;
-    Buf tmp, cnt = dev_alloc(8, s);
-    CS_HIP(hipMemsetAsync(cnt->p, 0, 8, s));
-    int32_t* d_out = results;
-    if (!on_device) {
-      tmp = dev_alloc(sizeof(int32_t) * total, s);
-      d_out = ptr<int32_t>(tmp);
-    }
+    const Buf cnt = zeroed_count(s);
+    const ResultsOut res(results, sizeof(int32_t) * total, on_device, s);
+    int32_t* d_out = static_cast<int32_t*>(res.dev);
     hipLaunchKernelGGL(k_find_multiple, dim3(blocks_for(total)), dim3(kBlock), 0, s, view_of(col), view_of(targets), d_out);
     hipLaunchKernelGGL(k_count_not_minus_one, dim3(std::min(blocks_for(col->rows), 8192u)), dim3(kBlock), 0, s, d_out, col->rows, ptr<unsigned long long>(cnt));
     CS_HIP(hipGetLastError());
-    if (!on_device) CS_HIP(hipMemcpyAsync(results, d_out, sizeof(int32_t) * total, hipMemcpyDeviceToHost, s));
-    const int64_t n = read_back<int64_t>(cnt, s);
+    res.copy_back(s);
+    const int64_t n = read_count(cnt, s);
     if (found) *found = n;
   });
 }
@@ -731,13 +714,9 @@ int cs_contains(const cs_column* col, const char* str, uint8_t* results, int on_
     require_device();
     hipStream_t s = S(stream);
     Needle nd = upload(str, s);
-    Buf tmp, cnt = dev_alloc(8, s);
-    CS_HIP(hipMemsetAsync(cnt->p, 0, 8, s));
-    uint8_t* d_out = results;
-    if (!on_device) {
-      tmp = dev_alloc((size_t)col->rows, s);
-      d_out = ptr<uint8_t>(tmp);
-    }
+    const Buf cnt = zeroed_count(s);
+    const ResultsOut res(results, (size_t)col->rows, on_device, s);
+    uint8_t* d_out = static_cast<uint8_t*>(res.dev);
     {
       ProfScope ps("k_contains", s);
       if (!find_tiles(col, reinterpret_cast<const unsigned char*>(str), nd.n, 1, 0, 0, nullptr, d_out,
@@ -745,8 +724,8 @@ int cs_contains(const cs_column* col, const char* str, uint8_t* results, int on_
         hipLaunchKernelGGL(k_contains, dim3(std::min(blocks_for(col->rows), 8192u)), dim3(kBlock), 0, s, view_of(col), nd.d(),
                            nd.n, d_out, ptr<unsigned long long>(cnt));
     }
-    if (!on_device) CS_HIP(hipMemcpyAsync(results, d_out, (size_t)col->rows, hipMemcpyDeviceToHost, s));
-    int64_t n = read_back<int64_t>(cnt, s);
+    res.copy_back(s);
+    const int64_t n = read_count(cnt, s);
     if (found) *found = n;
   });
 }

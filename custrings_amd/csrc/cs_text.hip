@@ -189,16 +189,10 @@ int cs_token_count(const cs_column* col, const char* delimiter, uint32_t* result
     if (rows == 0) return;
     Buf set_more;
     Tokenizer t = make_tokenizer(delimiter, set_more, s);
-    Buf tmp;
-    uint32_t* d = results;
-    if (!on_device) {
-      tmp = dev_alloc(sizeof(uint32_t) * rows, s);
-      d = ptr<uint32_t>(tmp);
-    }
-    hipLaunchKernelGGL(k_token_count, dim3(blocks_for(rows)), dim3(kBlock), 0, s, view_of(col), t, d);
+    const ResultsOut res(results, sizeof(uint32_t) * rows, on_device, s);
+    hipLaunchKernelGGL(k_token_count, dim3(blocks_for(rows)), dim3(kBlock), 0, s, view_of(col), t, static_cast<uint32_t*>(res.dev));
     CS_HIP(hipGetLastError());
-    if (!on_device) CS_HIP(hipMemcpyAsync(results, d, sizeof(uint32_t) * rows, hipMemcpyDeviceToHost, s));
-    CS_HIP(hipStreamSynchronize(s));
+    res.finish(s);
   });
 }
 
@@ -225,16 +219,10 @@ int cs_tokens_counts(const cs_column* col, const cs_column* tokens, const char* 
     if (!results || rows == 0 || tc == 0) return;  // tokens.cu:442-443
     Buf set_more;
     Tokenizer t = make_tokenizer(delimiter, set_more, s);
-    Buf tmp;
-    uint32_t* d = results;
-    if (!on_device) {
-      tmp = dev_alloc(sizeof(uint32_t) * rows * tc, s);
-      d = ptr<uint32_t>(tmp);
-    }
-    hipLaunchKernelGGL(k_tokens_counts, dim3(blocks_for(rows)), dim3(kBlock), 0, s, view_of(col), view_of(tokens), t, d);
+    const ResultsOut res(results, sizeof(uint32_t) * rows * tc, on_device, s);
+    hipLaunchKernelGGL(k_tokens_counts, dim3(blocks_for(rows)), dim3(kBlock), 0, s, view_of(col), view_of(tokens), t, static_cast<uint32_t*>(res.dev));
     CS_HIP(hipGetLastError());
-    if (!on_device) CS_HIP(hipMemcpyAsync(results, d, sizeof(uint32_t) * rows * tc, hipMemcpyDeviceToHost, s));
-    CS_HIP(hipStreamSynchronize(s));
+    res.finish(s);
   });
 }
 

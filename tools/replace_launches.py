@@ -1,15 +1,18 @@
-"""The launches of the replace route, case by case (dev tool): which kernels a replace call starts, on what grid and with
-how much dynamic LDS, for every case of tests/test_gpu_replace_forms.py and for bench.py's pattern on a 1M-row generated
-column.  Two builds whose listings agree start the same kernels.
+"""The launches of the replace route or of the scan route, case by case (dev tool): which kernels a call starts, on what
+grid and with how much dynamic LDS, for every case of tests/test_gpu_replace_forms.py (`run replace`: plus bench.py's
+pattern on a 1M-row generated column) or of tests/test_gpu_scan_forms.py (`run scan`: plus contains_re and count_re of
+that pattern on the same column).  Two builds whose listings agree start the same kernels.
 
-    rocprofv3 --kernel-trace --output-format json -d DIR -- python tools/replace_launches.py run 2> DIR/stream_info.txt
+    rocprofv3 --kernel-trace --output-format json -d DIR -- python tools/replace_launches.py run scan 2> DIR/stream_info.txt
     python tools/replace_launches.py list DIR > listing.txt
 
 `run` makes the calls in a fixed order with CS_STREAM_INFO set (the library's own account of every single-pass launch, on
 stderr, behind a `case` line); `list` prints the trace's dispatches in order: kernel, grid, workgroup, LDS.  The LDS is
 the dispatch packet's group segment size (`dispatch_info.group_segment_size` of the JSON trace: the kernel's static LDS
 plus the dynamic LDS of the launch); the CSV trace's `LDS_Block_Size` column shows 0 for a kernel whose LDS is all
-dynamic, so a CSV trace is listed only when there is no JSON one, and says so.
+dynamic, so a CSV trace is listed only when there is no JSON one, and says so.  The runtime's own copy and fill kernels
+(`__amd_rocclr_*`: a hipMemcpy or hipMemset each) are folded, a run of them into one line with their numbers (the listings under profiles/replaceplan were made before
+that: they show every such dispatch on a line of its own, and are otherwise what `run replace` + `list` give).
 CS_LIB_PATH picks the build."""
 import csv
 import glob
@@ -23,35 +26,74 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
         sys.path.insert(0, p)
 
 
-def run():
+def run(table):
     import gpuutil
     import test_gpu_replace_forms as forms
 
     L = gpuutil.lib()
     L.check(L.lib.cs_config_set(b"CS_STREAM_INFO", b"1"))
 
-    def call(name, g, op, pat, repl, maxrepl, switches):
+    def call(name, switches, fn):
         sys.stderr.write("case %s\n" % name)
         sys.stderr.flush()
         for v in switches:
             L.check(L.lib.cs_config_set(v.encode(), b"1"))
         try:
-            if op == forms.RE:
-                g.replace(pat, repl, maxrepl)
-            elif op == forms.LIT:
-                g.replace(pat, repl, maxrepl, regex=False)
-            else:
-                g.replace_with_backrefs(pat, repl)
+            fn()
         finally:
             for v in switches:
                 L.check(L.lib.cs_config_set(v.encode(), None))
         sys.stderr.write("route %s\n" % L.lib.cs_debug_last_route().decode())
 
-    for name, op, pat, repl, maxrepl, kind, n, switches in forms.CASES:
-        call(name, forms._col(kind, n)[1], op, pat, repl, maxrepl, switches)
-    g = gpuutil.synth(3, 0, 1_000_000)
-    for i in range(2):  # (the second call finds the column's metadata cached)
-        call("bench-1M-%d" % i, g, forms.RE, forms.IPV4, "<IP>", -1, ())
+    def replace(g, op, pat, repl, maxrepl):
+        if op == forms.RE:
+            g.replace(pat, repl, maxrepl)
+        elif op == forms.LIT:
+            g.replace(pat, repl, maxrepl, regex=False)
+        else:
+            g.replace_with_backrefs(pat, repl)
+
+    def scan(scans, g, op, pat):  # (host results: with device results the kernels are the same, only the copy back goes)
+        re = gpuutil.compile_re(pat)
+        try:
+            scans.call(L, op, g, re, False)
+        finally:
+            L.lib.cs_regex_destroy(re)
+
+    if table == "replace":
+        for name, op, pat, repl, maxrepl, kind, n, switches in forms.CASES:
+            call(name, switches, lambda: replace(forms._col(kind, n)[1], op, pat, repl, maxrepl))
+        bench = gpuutil.synth(3, 0, 1_000_000)
+        for i in range(2):  # (the second call finds the column's metadata cached)
+            call("bench-1M-%d" % i, (), lambda: replace(bench, forms.RE, forms.IPV4, "<IP>", -1))
+    else:
+        import test_gpu_scan_forms as scans
+
+        for name, op, pat, kind, n, switches in scans.CASES:
+            call(name, switches, lambda: scan(scans, scans._col(kind, n)[1], op, pat))
+        bench = gpuutil.synth(3, 0, 1_000_000)
+        for op in (scans.CONTAINS, scans.COUNT):
+            for i in range(2):
+                call("bench-1M-%s-%d" % (op, i), (), lambda: scan(scans, bench, op, forms.IPV4))
+
+
+def emit(lines):
+    """Prints the dispatches; a run of the runtime's copy / fill kernels becomes one line."""
+    run = {}
+
+    def flush():
+        if run:
+            print("(runtime: %s)" % ", ".join("%d %s" % (n, k) for k, n in sorted(run.items())))
+            run.clear()
+
+    for line in lines:
+        if line.startswith("__amd_rocclr_"):
+            k = line.split()[0][len("__amd_rocclr_"):]
+            run[k] = run.get(k, 0) + 1
+        else:
+            flush()
+            print(line)
+    flush()
 
 
 def listing_json(files):
@@ -69,8 +111,7 @@ def listing_json(files):
                 rows.append((int(r.get("start_timestamp", 0)), int(di.get("dispatch_id", 0)),
                              "%s grid %sx%sx%s wg %sx%sx%s lds %s" % (names.get(di.get("kernel_id"), di.get("kernel_id")), g.get("x"), g.get("y"), g.get("z"),
                                                                      w.get("x"), w.get("y"), w.get("z"), di.get("group_segment_size", "?"))))
-    for _, _, line in sorted(rows):
-        print(line)
+    emit(line for _, _, line in sorted(rows))
 
 
 def listing(d, force_csv=False):
@@ -86,15 +127,17 @@ def listing(d, force_csv=False):
         with open(f, newline="") as fh:
             rows += list(csv.DictReader(fh))
     rows.sort(key=lambda r: (int(r.get("Start_Timestamp", 0)), int(r.get("Dispatch_Id", 0))))
+    lines = []
     for r in rows:
         grid = "x".join(r.get(k, "?") for k in ("Grid_Size_X", "Grid_Size_Y", "Grid_Size_Z"))
         wg = "x".join(r.get(k, "?") for k in ("Workgroup_Size_X", "Workgroup_Size_Y", "Workgroup_Size_Z"))
-        print("%s grid %s wg %s lds %s" % (r.get("Kernel_Name", "?"), grid, wg, r.get("LDS_Block_Size", r.get("Group_Segment_Size", "?"))))
+        lines.append("%s grid %s wg %s lds %s" % (r.get("Kernel_Name", "?"), grid, wg, r.get("LDS_Block_Size", r.get("Group_Segment_Size", "?"))))
+    emit(lines)
 
 
 if __name__ == "__main__":
-    if len(sys.argv) >= 2 and sys.argv[1] == "run":
-        run()
+    if len(sys.argv) >= 2 and sys.argv[1] == "run" and sys.argv[2:] in ([], ["replace"], ["scan"]):
+        run(sys.argv[2] if sys.argv[2:] else "replace")
     elif len(sys.argv) >= 3 and sys.argv[1] == "list":
         listing(sys.argv[2], force_csv=sys.argv[3:] == ["csv"])
     else:
