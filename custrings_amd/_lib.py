@@ -233,6 +233,7 @@ _PROTOS = {
     "cs_prof_get": (i32, [cp, P(C.c_double), P(i64)]),
     "cs_debug_spin": (i32, [i32, i32, i32, vp]),
     "cs_debug_offsets_from_lengths": (i32, [vp, i64, i32, i32, vp, vp, vp, vp]),
+    "cs_debug_radix_sort_pairs64": (i32, [vp, vp, i64, vp]),
     "cs_stream_forget": (i32, [vp]),
 }
 for _name, (_res, _args) in _PROTOS.items():

@@ -164,3 +164,16 @@ void radix_sort_pairs64(uint64_t* keys, int32_t* items, int64_t n, hipStream_t s
 }
 
 }  // namespace cs
+
+// The sort by itself, nothing changed in it (tests/test_gpu_radix.py).
+extern "C" int cs_debug_radix_sort_pairs64(uint64_t* keys, int32_t* items, int64_t n, cs_stream stream) {
+  return guard([&] {
+    if (n < 0 || (n > 0 && (!keys || !items))) fail(CS_ERR_INVALID_ARG, "debug_radix_sort_pairs64: bad arguments");
+    if (n <= 1) return;
+    require_device();
+    hipStream_t s = S(stream);
+    radix_sort_pairs64(keys, items, n, s);
+    CS_HIP(hipGetLastError());
+    CS_HIP(hipStreamSynchronize(s));
+  });
+}

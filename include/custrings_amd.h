@@ -780,6 +780,11 @@ int cs_debug_numcat_sort_rows(const void* items, int64_t n, cs_numtype type, int
  * is not what this entry point covers.  No chars are allocated.  UNSUPPORTED, as every cs_debug_* entry point. */
 int cs_debug_offsets_from_lengths(const int32_t* lens, int64_t n, int segs, int route, int64_t* offsets, uint8_t* validity, int64_t* out,
                                   cs_stream stream);
+/* For the tests of the stable radix sort under order, sort and both category builds: sorts the n pairs (keys[i], items[i])
+ * (both device) by key, unsigned ascending, equal keys in input order, in place, with the library's own sort, and waits.
+ * n < 0, or a null pointer with n > 0: CS_ERR_INVALID_ARG; n of 0 or 1 touches nothing.  UNSUPPORTED, as every cs_debug_*
+ * entry point. */
+int cs_debug_radix_sort_pairs64(uint64_t* keys, int32_t* items, int64_t n, cs_stream stream);
 
 #ifdef __cplusplus
 }

@@ -53,17 +53,25 @@ def test_gpu_array_ops(gpu_engine, oracle_engine, seed):
     assert g.scalar_scatter(s, None, p2[:40]) == o.scalar_scatter(s, None, p2[:40])
 
 
-@pytest.mark.parametrize("n", [4095, 4096, 4097, 20_000])
-def test_gpu_order_and_sort_keep_equal_strings_in_index_order(gpu_engine, n):
+@pytest.mark.parametrize("n,distinct,longest", [pytest.param(4095, 300, 12, id="4095"), pytest.param(4096, 300, 12, id="4096"),
+                                                pytest.param(4097, 300, 12, id="4097"), pytest.param(20_000, 300, 12, id="20000"),
+                                                pytest.param(5000, 3000, 180, id="5000_rows_of_3000_strings_of_up_to_300_bytes")])
+def test_gpu_order_and_sort_keep_equal_strings_in_index_order(gpu_engine, n, distinct, longest):
     """Around one radix tile of keys and at several: rows drawn from 300 distinct strings (prefixes of one another, empty,
     multi-byte) plus nulls, so that most rows have equals.  Against Python's stable sort on (null class, [byte length],
     [bytes]), reversed as a whole for descending (which keeps equal rows in index order too): NVStrings.h "sort" and "order"
-    place nulls by `nullfirst` whatever the direction."""
+    place nulls by `nullfirst` whatever the direction.  The last parametrisation draws 5000 rows from 3000 distinct strings of
+    up to 300 bytes: the sort key (length + 1) << 32 | rank then varies in digits 0, 1, 4 AND 5 of the radix sort."""
     rnd = random.Random(n)
     pool = {"", "a", "ab", "abc", "é", "éa", "z" * 40}
-    while len(pool) < 300:
-        pool.add("".join(rnd.choice(["a", "b", "c", "Z", " ", "0", "é", "ß", "😀"]) for _ in range(rnd.randint(1, 12))))
+    if longest > 12:
+        pool |= {"é" * 150, "z" * 300, "z" * 299 + "a", "😀" * 75}  # 300 bytes each, but the one of 299 + 1
+    while len(pool) < distinct:
+        x = "".join(rnd.choice(["a", "b", "c", "Z", " ", "0", "é", "ß", "😀"]) for _ in range(rnd.randint(1, longest)))
+        if len(x.encode("utf8")) <= 300:
+            pool.add(x)
     pool = sorted(pool)
+    assert max(len(x.encode("utf8")) for x in pool) == (300 if longest > 12 else 40)
     s = [None if rnd.random() < 0.05 else rnd.choice(pool) for _ in range(n)]
     raw = [None if x is None else x.encode("utf8") for x in s]
     col = gpu_engine.col(s)
