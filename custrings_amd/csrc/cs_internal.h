@@ -318,6 +318,39 @@ struct ReplaceCall {
   bool single_pass_only = false;
 };
 cs_column* replace_re_column(const ReplaceCall& c);  // the new column (the caller's), or throws
+// cs_split.hip: one split / rsplit call on the tile kernels, all of its parameters in sight; what the kernels take of the
+// delimiter is derived here, once.  cs_ops.hip (split_impl) makes it where its gates let the call through.
+struct SplitCall {
+  const cs_column* col;
+  const unsigned char* delim;  // the delimiter (host): `dlen` = 1..8 ASCII bytes; nullptr: whitespace
+  int dlen;
+  int tokens;    // columns at most (the split limit + 1); 0 or less: no limit
+  bool reverse;  // rsplit with a limit on a one-byte delimiter (the masked kernels only)
+  hipStream_t s;
+  int mode = 0;                // 0: a one-byte delimiter, 1: whitespace, 2: a delimiter of 2..8 bytes
+  unsigned long long d64 = 0;  // the delimiter's bytes, first byte lowest
+  uint32_t dpat = 0;           // its first byte in every byte of a word
+  SplitCall(const cs_column* col_, const unsigned char* delim_, int dlen_, int tokens_, bool reverse_, hipStream_t s_)
+      : col(col_), delim(delim_), dlen(dlen_), tokens(tokens_), reverse(reverse_), s(s_) {
+    mode = !delim ? 1 : (dlen > 1 ? 2 : 0);
+    for (int i = 0; delim && i < dlen; ++i) d64 |= (unsigned long long)delim[i] << (8 * i);
+    dpat = 0x01010101u * (delim ? (uint32_t)delim[0] : 0u);
+  }
+};
+// the tiles of a split call (split_tile_plan): rows a sub-tile, its largest span and the LDS tiles that hold it
+struct SplitPlan {
+  bool fits = false;      // some tile size fits the LDS (else: the row-wise kernels)
+  int rows_per_sub = 64;  // 64, or 32 / 16 / 8: the first generation on rows of hundreds of bytes
+  bool outliers = false;  // 64-row tiles sized for all but a few sub-tiles (the first generation reads those from memory)
+  int64_t span = 0;       // bytes of the largest sub-tile (outliers: of the largest that is staged)
+  int cap_in = 0, cap_out = 0;  // the first generation's in and out tile
+  int walk_words = 0;     // mask words of the sentinel walk, 3 or 6; 0: the general token walker
+};
+// the tile kernels; false: not this path's call (nothing done), the row-wise kernels answer
+bool split_fast(const SplitCall& c, std::vector<std::unique_ptr<cs_column>>& cols);
+// cs_split1.hip (the experiments build): the single pass.  1: columns written; 0: not this path's case (nothing done);
+// -1: it gave up (fallback counted)
+int split_single(const SplitCall& c, const SplitPlan& p, std::vector<std::unique_ptr<cs_column>>& cols);
 // cs_radix.hip: stable LSD radix sort of n (64-bit key, 32-bit item) pairs by key, ascending, in place (synchronises `s`)
 void radix_sort_pairs64(uint64_t* keys, int32_t* items, int64_t n, hipStream_t s);
 // cs_category.hip: keys = sorted unique rows (null first), values[r] = index of row r's key

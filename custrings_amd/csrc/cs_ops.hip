@@ -33,12 +33,6 @@ bool find_tiles(const cs_column* in, const unsigned char* needle, int nb, int mo
 }
 using namespace csrow;
 
-namespace cs {
-// cs_split.hip: tile kernels for a single-byte delimiter; false = not applicable
-bool split_fast(const cs_column* col, const unsigned char* delim, int dlen, int tokens, hipStream_t s,
-                std::vector<std::unique_ptr<cs_column>>& cols, bool reverse = false);
-}
-
 namespace {
 
 struct Needle {  // small host string copied to the device
@@ -779,6 +773,92 @@ int cs_replace(const cs_column* col, const char* str, const char* repl, int maxr
   });
 }
 
+// Without a split limit the walk from the right meets the same tokens as the walk from the left
+// when the delimiter is whitespace, or ASCII and border-free (no proper prefix that is also a
+// suffix: occurrences cannot overlap, and the character/byte quirk of the token count
+// (row_ops.h) does not arise): those calls take the split kernels.  Everything else -- a
+// limit, a delimiter that can overlap itself, a multi-byte delimiter -- is located from the
+// right.
+static bool rsplit_walks_like_split(const char* delimiter, int maxsplit) {
+  bool same = maxsplit <= 0;
+  if (same && delimiter) {
+    const int n = (int)strlen(delimiter);
+    same = n > 0;
+    for (int i = 0; same && i < n; ++i) same = (unsigned char)delimiter[i] < 128;
+    for (int b = 1; same && b < n; ++b) same = memcmp(delimiter, delimiter + n - b, (size_t)b) != 0;
+  }
+  return same;
+}
+// The gate of the tile kernels (cs_split.hip).  From the left: whitespace, or a delimiter of 1..8 ASCII bytes.  From the
+// right -- an rsplit that does not walk like split --: a limit on a one-byte ASCII delimiter (the first delimiters of a
+// row are struck from its mask: split_parts.h TokensT).
+static bool split_on_tile_kernels(const char* delimiter, const SplitArgs& a) {
+  bool ascii_delim = delimiter && a.nb >= 1 && a.nb <= 8;
+  for (int i = 0; ascii_delim && i < a.nb; ++i) ascii_delim = (unsigned char)delimiter[i] < 128;
+  if (!a.reverse) return !delimiter || ascii_delim;
+  return ascii_delim && a.nb == 1 && a.tokens > 0 && !cs::cfg("CS_RSPLIT_ROWWISE");
+}
+// The row-wise kernels: count the tokens of every row, size every column's rows, write.
+static void split_rowwise(const cs_column* col, SplitArgs a, hipStream_t s, cs_column*** out_cols, int* ncols_out) {
+  const int64_t rows = col->rows;
+  note_route("split-rowwise");
+  int ncols = 0;
+  Buf counts;
+  const unsigned nb = blocks_for(rows);
+  if (rows) {
+    counts = dev_alloc(sizeof(int32_t) * rows, s);
+    Buf mx = dev_alloc(sizeof(int), s);
+    CS_HIP(hipMemsetAsync(mx->p, 0, sizeof(int), s));
+    {
+      ProfScope ps("k_split_count", s);
+      hipLaunchKernelGGL(k_split_count, dim3(nb), dim3(kBlock), 0, s, view_of(col), a,
+                         ptr<int32_t>(counts), ptr<int>(mx));
+    }
+    ncols = read_back<int>(mx, s);
+    a.ncols = ncols;
+  }
+  std::vector<std::unique_ptr<cs_column>> cols;
+  if (ncols == 0) {
+    // no columns: one all-null column (split.cu:756-757)
+    cols.emplace_back(make_all_null(rows, s));
+  } else {
+    Buf lens = dev_alloc(sizeof(int32_t) * rows * ncols, s);
+    Buf sums = dev_alloc(sizeof(int64_t) * (size_t)nb * ncols, s);
+    {
+      ProfScope ps("k_split_sizes", s);
+      hipLaunchKernelGGL(k_split_sizes, dim3(nb), dim3(kBlock), 0, s, view_of(col), a,
+                         ptr<int32_t>(counts), ncols, ptr<int32_t>(lens), ptr<int64_t>(sums));
+    }
+    // per-column offsets: one segmented scan over the fused block sums
+    Buf offs = dev_alloc(sizeof(int64_t) * (rows + 1) * ncols, s);
+    std::vector<int64_t> totals(ncols);
+    offsets_from_lengths_segmented(ptr<int32_t>(lens), rows, ncols, ptr<int64_t>(offs), totals.data(), s);
+    std::vector<SplitOut> outs(ncols);
+    for (int k = 0; k < ncols; ++k) {
+      auto* c = new cs_column;
+      cols.emplace_back(c);
+      c->rows = rows;
+      c->nbytes = totals[k];
+      c->chars = dev_alloc((size_t)totals[k], s);
+      // each column owns its offsets: copy its segment out of the scan buffer
+      c->offsets = dev_alloc(sizeof(int64_t) * (rows + 1), s);
+      CS_HIP(hipMemcpyAsync(c->offsets->p, ptr<int64_t>(offs) + (int64_t)k * (rows + 1),
+                            sizeof(int64_t) * (rows + 1), hipMemcpyDeviceToDevice, s));
+      c->validity = validity_from_lengths(ptr<int32_t>(lens) + (int64_t)k * rows, rows, s);
+      outs[k] = SplitOut{ptr<uint8_t>(c->chars), c->d_offsets()};
+    }
+    Buf d_outs = dev_alloc(sizeof(SplitOut) * ncols, s);
+    CS_HIP(hipMemcpyAsync(d_outs->p, outs.data(), sizeof(SplitOut) * ncols, hipMemcpyHostToDevice, s));
+    {
+      ProfScope ps("k_split_write", s);
+      hipLaunchKernelGGL(k_split_write, dim3(nb), dim3(kBlock), 0, s, view_of(col), a,
+                         ptr<int32_t>(counts), ncols, ptr<const SplitOut>(d_outs));
+    }
+    CS_HIP(hipStreamSynchronize(s));  // `outs` staging is on the host stack
+  }
+  release_columns(cols, out_cols, ncols_out);
+}
+
 // NVStrings::split(delimiter,maxsplit,results) / split(maxsplit,results) -- split.cu:734-956
 static int split_impl(const cs_column* col, const char* delimiter, int maxsplit, cs_stream stream, cs_column*** out_cols,
                       int* ncols_out, bool reverse) {
@@ -786,98 +866,22 @@ static int split_impl(const cs_column* col, const char* delimiter, int maxsplit,
     if (!col || !out_cols || !ncols_out) fail(CS_ERR_INVALID_ARG, "null argument");
     require_device();
     hipStream_t s = S(stream);
-    const int64_t rows = col->rows;
     SplitArgs a{nullptr, 0, maxsplit > 0 ? maxsplit + 1 : 0, 0, 0};
-    if (reverse) {
-      // Without a split limit the walk from the right meets the same tokens as the walk from the left
-      // when the delimiter is whitespace, or ASCII and border-free (no proper prefix that is also a
-      // suffix: occurrences cannot overlap, and the character/byte quirk of the token count
-      // (row_ops.h) does not arise): those calls take the split kernels.  Everything else -- a
-      // limit, a delimiter that can overlap itself, a multi-byte delimiter -- is located from the
-      // right by the row-wise kernels below.
-      bool same = maxsplit <= 0;
-      if (same && delimiter) {
-        const int n = (int)strlen(delimiter);
-        same = n > 0;
-        for (int i = 0; same && i < n; ++i) same = (unsigned char)delimiter[i] < 128;
-        for (int b = 1; same && b < n; ++b) same = memcmp(delimiter, delimiter + n - b, (size_t)b) != 0;
-      }
-      a.reverse = same ? 0 : 1;
-    }
+    a.reverse = reverse && !rsplit_walks_like_split(delimiter, maxsplit) ? 1 : 0;
     Needle nd;
     if (delimiter) {
       nd = upload(delimiter, s);
       a.delim = nd.d();
       a.nb = nd.n;
     }
-    bool ascii_delim = delimiter && nd.n >= 1 && nd.n <= 8;
-    for (int i = 0; ascii_delim && i < nd.n; ++i) ascii_delim = (unsigned char)delimiter[i] < 128;
-    // rsplit with a limit on a one-byte ASCII delimiter rides the split tile kernels too (the first delimiters of a
-    // row are struck from its mask: cs_split.hip TokensT)
-    const bool reverse_fast = a.reverse && ascii_delim && nd.n == 1 && a.tokens > 0 && !cs::cfg("CS_RSPLIT_ROWWISE");
-    if ((!a.reverse && (!delimiter || ascii_delim)) || reverse_fast) {
+    if (split_on_tile_kernels(delimiter, a)) {
       std::vector<std::unique_ptr<cs_column>> fast;
-      if (split_fast(col, reinterpret_cast<const unsigned char*>(delimiter), delimiter ? nd.n : 0, a.tokens, s, fast, reverse_fast)) {
+      if (split_fast(SplitCall(col, reinterpret_cast<const unsigned char*>(delimiter), a.nb, a.tokens, a.reverse != 0, s), fast)) {
         release_columns(fast, out_cols, ncols_out);
         return;
       }
     }
-    note_route("split-rowwise");
-    int ncols = 0;
-    Buf counts;
-    const unsigned nb = blocks_for(rows);
-    if (rows) {
-      counts = dev_alloc(sizeof(int32_t) * rows, s);
-      Buf mx = dev_alloc(sizeof(int), s);
-      CS_HIP(hipMemsetAsync(mx->p, 0, sizeof(int), s));
-      {
-        ProfScope ps("k_split_count", s);
-        hipLaunchKernelGGL(k_split_count, dim3(nb), dim3(kBlock), 0, s, view_of(col), a,
-                           ptr<int32_t>(counts), ptr<int>(mx));
-      }
-      ncols = read_back<int>(mx, s);
-      a.ncols = ncols;
-    }
-    std::vector<std::unique_ptr<cs_column>> cols;
-    if (ncols == 0) {
-      // no columns: one all-null column (split.cu:756-757)
-      cols.emplace_back(make_all_null(rows, s));
-    } else {
-      Buf lens = dev_alloc(sizeof(int32_t) * rows * ncols, s);
-      Buf sums = dev_alloc(sizeof(int64_t) * (size_t)nb * ncols, s);
-      {
-        ProfScope ps("k_split_sizes", s);
-        hipLaunchKernelGGL(k_split_sizes, dim3(nb), dim3(kBlock), 0, s, view_of(col), a,
-                           ptr<int32_t>(counts), ncols, ptr<int32_t>(lens), ptr<int64_t>(sums));
-      }
-      // per-column offsets: one segmented scan over the fused block sums
-      Buf offs = dev_alloc(sizeof(int64_t) * (rows + 1) * ncols, s);
-      std::vector<int64_t> totals(ncols);
-      offsets_from_lengths_segmented(ptr<int32_t>(lens), rows, ncols, ptr<int64_t>(offs), totals.data(), s);
-      std::vector<SplitOut> outs(ncols);
-      for (int k = 0; k < ncols; ++k) {
-        auto* c = new cs_column;
-        cols.emplace_back(c);
-        c->rows = rows;
-        c->nbytes = totals[k];
-        c->chars = dev_alloc((size_t)totals[k], s);
-        // each column owns its offsets: copy its segment out of the scan buffer
-        c->offsets = dev_alloc(sizeof(int64_t) * (rows + 1), s);
-        CS_HIP(hipMemcpyAsync(c->offsets->p, ptr<int64_t>(offs) + (int64_t)k * (rows + 1),
-                              sizeof(int64_t) * (rows + 1), hipMemcpyDeviceToDevice, s));
-        c->validity = validity_from_lengths(ptr<int32_t>(lens) + (int64_t)k * rows, rows, s);
-        outs[k] = SplitOut{ptr<uint8_t>(c->chars), c->d_offsets()};
-      }
-      Buf d_outs = dev_alloc(sizeof(SplitOut) * ncols, s);
-      CS_HIP(hipMemcpyAsync(d_outs->p, outs.data(), sizeof(SplitOut) * ncols, hipMemcpyHostToDevice, s));
-      {
-        ProfScope ps("k_split_write", s);
-        hipLaunchKernelGGL(k_split_write, dim3(nb), dim3(kBlock), 0, s, view_of(col), a,
-                           ptr<int32_t>(counts), ncols, ptr<const SplitOut>(d_outs));
-      }
-      CS_HIP(hipStreamSynchronize(s));  // `outs` staging is on the host stack
-    }
-    release_columns(cols, out_cols, ncols_out);
+    split_rowwise(col, a, s, out_cols, ncols_out);
   });
 }
 

@@ -23,8 +23,11 @@
 //   beyond 8 KB and sub-tiles of fewer rows.  The second and third emit generations
 //   -- k_split_emit2 / _emit3, reachable only through measurement switches since the
 //   fourth -- left the library in round 6.)
-// Rows with more than kMaxCols tokens, multi-byte delimiters and whitespace
-// splitting use the generic kernels in cs_ops.hip.
+// Whitespace and delimiters of 2..8 ASCII bytes run on the same two kernels (MODE 1 / 2: the general token walker,
+// TokensT), as do a split limit and rsplit with a limit on a one-byte delimiter.  The row-wise kernels in cs_ops.hip
+// keep the rest: delimiters of more than 8 bytes or with a non-ASCII byte, an rsplit that does not walk like split, rows
+// with more than kMaxColsWide tokens, rows that no tile size fits, columns of nulls only.
+// The host path is at the end of the file: cs::split_fast, a sequence of named steps.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -38,13 +41,6 @@
 
 using namespace cs;
 using namespace csdev;
-
-namespace cs {
-bool split_fast(const cs_column* col, const unsigned char* delim, int dlen, int tokens, hipStream_t s,
-                std::vector<std::unique_ptr<cs_column>>& cols, bool reverse = false);
-int split_single(const cs_column* col, const unsigned char* delim, int dlen, int tokens, hipStream_t s,
-                 std::vector<std::unique_ptr<cs_column>>& cols, bool reverse, int64_t span, bool plain_walk);
-}
 
 namespace {
 
@@ -760,36 +756,62 @@ __global__ void __launch_bounds__(kEmit3Threads, W > 3 ? 3 : CS_EMIT3_WAVES) k_s
   }
 }
 
-}  // namespace
+// ---- the host path ---------------------------------------------------------------------------------------------------
+// cs::split_fast (at the end) is a sequence: the tile plan (split_tile_plan, split_walk_words), the tile kernels proper
+// (split_on_tiles: k_split_measure2 + k_split_emit4 on the runs of split_runs) and, where they decline a one-byte
+// delimiter's split, the first generation (split_first_generation: k_split_measure + k_split_emit, a sub-tile a wave).
+// Both generations measure, read the counts back (read_counts) and build their columns with measured_columns.
 
-namespace cs {
+// ---- the kernel forms.  A family's instantiations are named here and nowhere else, the families and their forms in this
+// order: it is the order of the kernels in the code object.
+typedef void (*Measure2Kernel)(Measure2Args);
+Measure2Kernel measure2_kernel(int mode, int walk_words) {
+  if (mode == 1) return k_split_measure2<1>;
+  if (mode == 2) return k_split_measure2<2>;
+  if (walk_words == 6) return k_split_measure2<0, true, 6>;
+  if (walk_words == 3) return k_split_measure2<0, true, 3>;
+  return k_split_measure2<0>;
+}
+typedef void (*Emit4Kernel)(Emit3Args);
+Emit4Kernel emit4_kernel(int mode, int walk_words, bool off32) {
+  static const Emit4Kernel general[2][3] = {{k_split_emit4<0, false, false>, k_split_emit4<1, false, false>, k_split_emit4<2, false, false>},
+                                            {k_split_emit4<0, true, false>, k_split_emit4<1, true, false>, k_split_emit4<2, true, false>}};
+  if (walk_words == 6) return off32 ? k_split_emit4<0, true, true, 6, 8> : k_split_emit4<0, false, true, 6, 8>;
+  if (walk_words == 3) return off32 ? k_split_emit4<0, true, true> : k_split_emit4<0, false, true>;
+  return general[off32 ? 1 : 0][mode];
+}
+typedef void (*MeasureKernel)(MeasureArgs);
+MeasureKernel measure_kernel() { return k_split_measure<0>; }  // (the first generation: a one-byte delimiter only)
+typedef void (*EmitKernel)(EmitArgs);
+EmitKernel emit_kernel(bool off32) { return off32 ? &k_split_emit<true> : &k_split_emit<false>; }
 
-// `delim`: 1..8 ASCII bytes, or nullptr for whitespace splitting.
-// `reverse`: rsplit with a limit on a one-byte delimiter (the masked kernels only; anything else returns false).
-bool split_fast(const cs_column* col, const unsigned char* delim, int dlen, int tokens, hipStream_t s,
-                std::vector<std::unique_ptr<cs_column>>& cols, bool reverse) {
-  const bool ws = delim == nullptr;
-  const int mode = ws ? 1 : (dlen > 1 ? 2 : 0);
-  if (reverse && (mode != 0 || tokens <= 0)) return false;
-  unsigned long long d64 = 0;
-  for (int i = 0; !ws && i < dlen; ++i) d64 |= (unsigned long long)delim[i] << (8 * i);
-  const int64_t rows = col->rows;
-  if (rows == 0 || cs::cfg("CS_SPLIT_GENERIC")) return false;
-  int64_t span = max_span64(col, s);
-  int cap_in = (int)((span + 15 + 32 + 127) & ~(int64_t)127);
-  int cap_out = cap_in + 32 * kMaxColsWide;
-  // (rows of hundreds of bytes: the first-generation kernels on sub-tiles of 32 / 16 / 8 rows -- a one-byte delimiter only)
-  int rows_per_sub = kSub;
-  bool outliers = false;
-  if ((size_t)(cap_in + cap_out + 64) * 4 > 150 * 1024 && mode == 0 && !reverse && !cs::cfg("CS_NO_SMALL_TILES")) {
+// ---- the tile plan
+int tile_cap_in(int64_t span) { return (int)((span + 15 + 32 + 127) & ~(int64_t)127); }
+int tile_cap_out(int cap_in) { return cap_in + 32 * kMaxColsWide; }
+// four waves of the first generation's emit kernel, an in and an out tile each, in 150 KB of LDS
+bool tile_fits(int cap_in) { return (size_t)(cap_in + tile_cap_out(cap_in) + 64) * 4 <= 150 * 1024; }
+
+// The tiles of a call: 64 rows; where those do not fit, sub-tiles of 32 / 16 / 8 rows; where none fits or the largest
+// 64-row span is beyond 8 KB, 64-row tiles sized for all but a few.  Every question launches a pass over the offsets the
+// first time it is asked of a column (max_span64 is kept on the column): they are asked in this order and only here.
+SplitPlan split_tile_plan(const SplitCall& c) {
+  const cs_column* col = c.col;
+  const hipStream_t s = c.s;
+  const bool first_generation = c.mode == 0 && !c.reverse;  // (its kernels: sub-tiles of fewer rows and outliers are theirs)
+  SplitPlan p;
+  auto tiles_of = [&p](int rows, int64_t span) {
+    p.rows_per_sub = rows;
+    p.span = span;
+    p.cap_in = tile_cap_in(span);
+    p.cap_out = tile_cap_out(p.cap_in);
+  };
+  tiles_of(kSub, max_span64(col, s));
+  // (rows of hundreds of bytes: the first-generation kernels on sub-tiles of 32 / 16 / 8 rows)
+  if (!tile_fits(p.cap_in) && first_generation && !cs::cfg("CS_NO_SMALL_TILES")) {
     for (int r : {32, 16, 8}) {
       const int64_t sp = max_span_rows(col, r, s);
-      const int ci = (int)((sp + 15 + 32 + 127) & ~(int64_t)127);
-      if ((size_t)(ci + ci + 32 * kMaxColsWide + 64) * 4 <= 150 * 1024) {
-        rows_per_sub = r;
-        span = sp;
-        cap_in = ci;
-        cap_out = ci + 32 * kMaxColsWide;
+      if (tile_fits(tile_cap_in(sp))) {
+        tiles_of(r, sp);
         break;
       }
     }
@@ -797,202 +819,251 @@ bool split_fast(const cs_column* col, const unsigned char* delim, int dlen, int 
   // (no sub-tile size fits the largest sub-tile, all but a few 64-row ones fit: the first-generation kernels with buffers
   // for those -- they read the rows of an oversize sub-tile from memory and write its tokens straight to the columns)
   // (also when the largest sub-tile would fit, at one workgroup per CU: a 10 KB row among short ones ran 39 ms that way)
-  if (rows_per_sub == kSub && cap_in > 8 * 1024 && mode == 0 && !reverse && !cs::cfg("CS_NO_OUTLIER_TILES") && max_span64(col, s) < ((int64_t)1 << 30) &&
+  if (p.rows_per_sub == kSub && p.cap_in > 8 * 1024 && first_generation && !cs::cfg("CS_NO_OUTLIER_TILES") && max_span64(col, s) < ((int64_t)1 << 30) &&
       few_spans64_over(col, 8 * 1024 - 64, s)) {
-    rows_per_sub = kSub;
-    span = 8 * 1024 - 64;
-    cap_in = (int)((span + 15 + 32 + 127) & ~(int64_t)127);
-    cap_out = cap_in + 32 * kMaxColsWide;
-    outliers = true;
+    tiles_of(kSub, 8 * 1024 - 64);
+    p.outliers = true;
   }
-  if ((size_t)(cap_in + cap_out + 64) * 4 > 150 * 1024) return false;
-  const int64_t nsub = (rows + kSub - 1) / kSub;
-  const uint32_t dpat = 0x01010101u * (ws ? 0u : (uint32_t)delim[0]);
-  Buf mx = dev_alloc(4 * sizeof(int), s);
-  int* hmx = (int*)pinned_scratch(4 * sizeof(int));
+  p.fits = tile_fits(p.cap_in);
+  return p;
+}
+// Mask words of the sentinel walk (both passes of the tile kernels): a plain split -- a one-byte delimiter, no limit --
+// with every row's sentinel bit inside the mask; 0: the general token walker.  The longest row is column metadata, kept
+// on the immutable column like its largest 64-row span.
+int split_walk_words(const SplitCall& c) {
+  if (c.mode != 0 || c.tokens > 0 || c.reverse || cs::cfg("CS_SPLIT_GENERIC_WALK")) return 0;
+  const int64_t longest = max_row_bytes(c.col, c.s);
+  if (longest + 3 <= 95) return 3;
+  return longest + 3 <= 191 && !cs::cfg("CS_SPLIT_NO_LONG_WALK") ? 6 : 0;
+}
 
-  // ---- the tile kernels proper (k_split_measure2 + k_split_emit4): runs of sub-tiles per wave.  Rows up to 92-93 bytes on
-  // 96-bit masks and 64-row spans up to 6 KB; a plain split (one-byte delimiter, no limit) also rows up to 188 bytes on six
-  // mask words, spans up to 8 KB and 64 columns -- BASELINE's C5 column, which left these kernels until round 6
-  const bool plain_mode = mode == 0 && tokens <= 0 && !reverse && !cs::cfg("CS_SPLIT_GENERIC_WALK");
-  const int64_t longest_known = plain_mode ? max_row_bytes(col, s) : 0;  // (column metadata, kept on the immutable column like its largest 64-row span)
-  // mask words of the sentinel walk (both passes): every row's sentinel bit inside the mask; 0 = the general token walker
-  const int walk_words = !plain_mode ? 0 : (longest_known + 3 <= 95 ? 3 : (longest_known + 3 <= 191 && !cs::cfg("CS_SPLIT_NO_LONG_WALK") ? 6 : 0));
-  const bool tiles_ok = cap_in <= cstile::kPfBytes || (walk_words == 6 && cap_in <= 8 * 1024);
-  if (rows_per_sub == kSub && !outliers && tiles_ok && !cs::cfg("CS_SPLIT_OLD_EMIT")) {
-    // The run decomposition is a function of the row count alone (not of the emit kernel's
-    // residency, which depends on what the measure pass finds): emit needs no co-residency.
-    int dev = 0, cus = 0;
-    CS_HIP(hipGetDevice(&dev));
-    CS_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    int runs_per_cu = 256;  // (short runs share the tail out evenly: 16 / 64 / 128 / 256 runs per CU -> emit 7.06 / 7.05 / 6.77 / 6.61 ms)
-    runs_per_cu = std::max(1, cs::cfg_int("CS_EMIT_RUNS_PER_CU", runs_per_cu));  // (measurement)
-    int64_t runs = std::min<int64_t>(nsub, (int64_t)cus * runs_per_cu);
-    const int64_t per = (nsub + runs - 1) / runs;
-    runs = (nsub + per - 1) / per;
-    const int segs_per_run = (int)std::min<int64_t>(2, per);
-    const int64_t seg = (per + segs_per_run - 1) / segs_per_run;
-    const int64_t nseg = runs * segs_per_run;
-    const int maxc = walk_words == 6 ? kMaxColsLong : kMaxCols;
-    Buf colsum = dev_alloc(sizeof(int32_t) * nseg * maxc, s);
-    CS_HIP(hipMemsetAsync(colsum->p, 0, sizeof(int32_t) * nseg * maxc, s));
-    CS_HIP(hipMemsetAsync(mx->p, 0, 4 * sizeof(int), s));
-    const bool plain_walk = walk_words != 0;
-    // the single pass (cs_split1.hip), on request: measured slower than the two passes below (NOTES.md, round 4:
-    // 8.0 against 6.7 ms on the 100M-row column); they also take over when it gives up
+// The run decomposition of the tile kernels: an emit wave owns a run of `per` consecutive sub-tiles, a measure wave a
+// segment of `seg` of them.  A function of the row count and the CU count alone (not of the emit kernel's residency,
+// which depends on what the measure pass finds): emit needs no co-residency.
+struct SplitRuns {
+  int64_t nsub, runs, per, seg, nseg;
+  int segs_per_run;
+};
+SplitRuns split_runs(int64_t rows, int cus) {
+  SplitRuns r;
+  r.nsub = (rows + kSub - 1) / kSub;
+  int runs_per_cu = 256;  // (short runs share the tail out evenly: 16 / 64 / 128 / 256 runs per CU -> emit 7.06 / 7.05 / 6.77 / 6.61 ms)
+  runs_per_cu = std::max(1, cs::cfg_int("CS_EMIT_RUNS_PER_CU", runs_per_cu));  // (measurement)
+  r.runs = std::min<int64_t>(r.nsub, (int64_t)cus * runs_per_cu);
+  r.per = (r.nsub + r.runs - 1) / r.runs;
+  r.runs = (r.nsub + r.per - 1) / r.per;
+  r.segs_per_run = (int)std::min<int64_t>(2, r.per);
+  r.seg = (r.per + r.segs_per_run - 1) / r.segs_per_run;
+  r.nseg = r.runs * r.segs_per_run;
+  return r;
+}
+
+// ---- what a measure pass leaves, and its way to the host
+struct SplitCounts {
+  Buf dev;    // int[4], zeroed in front of a measure launch
+  int* host;  // pinned scratch (whatever asks for scratch next re-uses it: read_counts copies)
+};
+struct Measured {
+  int ncols;        // most tokens in a row: the columns
+  int bound;        // a bound on the bytes a column gets from one sub-tile
+  int longest_row;
+  int generic;      // set: a sub-tile needs the row-wise kernels (a row beyond the masks)
+};
+Measured read_counts(const SplitCounts& m, hipStream_t s) {
+  CS_HIP(hipGetLastError());
+  CS_HIP(hipMemcpyAsync(m.host, m.dev->p, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
+  CS_HIP(hipStreamSynchronize(s));
+  return Measured{m.host[0], m.host[1], m.host[2], m.host[3]};
+}
+
+// ---- the columns of a measured split, for both generations.  `colsum`: int32[ncols][n], the bytes column k gets from
+// segment (sub-tile) j of n.  Their scan gives every column its size and `base` (int64[ncols][n + 1]: where a segment
+// begins in the column's chars); int32 offsets when every column stays below 2 GiB: half the offset bytes.  Rec is the
+// emit kernel's record of a column, ColOut or ColOut2 -- chars, offsets, validity, the column's row of `base` --,
+// uploaded to `dev` out of `host`: both, and `base`, live until the emit kernel's stream is synchronised.
+// Column metadata for free (upper bounds: they size staging buffers and pick routes): `max_span64` and `max_row` come
+// from the caller's measure pass; tokens cut at ASCII delimiters out of a plain column are plain.
+template <class Rec>
+struct MeasuredColumns {
+  bool off32 = false;
+  Buf base;
+  std::vector<Rec> host;
+  Buf dev;
+};
+template <class Rec>
+MeasuredColumns<Rec> measured_columns(const SplitCall& c, const int32_t* colsum, int64_t n, int ncols, int64_t max_span64, int64_t max_row,
+                                      std::vector<std::unique_ptr<cs_column>>& cols) {
+  const hipStream_t s = c.s;
+  const int64_t rows = c.col->rows;
+  MeasuredColumns<Rec> out;
+  out.base = dev_alloc(sizeof(int64_t) * (n + 1) * ncols, s);
+  std::vector<int64_t> totals(ncols);
+  offsets_from_lengths_segmented(colsum, n, ncols, ptr<int64_t>(out.base), totals.data(), s);
+  out.off32 = !cs::cfg("CS_SPLIT_OFF64");
+  for (int k = 0; k < ncols; ++k) out.off32 = out.off32 && totals[k] < ((int64_t)1 << 31);
+  out.host.resize(ncols);
+  for (int k = 0; k < ncols; ++k) {
+    auto col = std::make_unique<cs_column>();
+    col->rows = rows;
+    col->nbytes = totals[k];
+    col->chars = dev_alloc((size_t)totals[k], s);
+    if (out.off32) col->offsets32 = dev_alloc(sizeof(int32_t) * (rows + 1), s);
+    else col->offsets = dev_alloc(sizeof(int64_t) * (rows + 1), s);
+    col->validity = dev_alloc(validity_bytes(rows), s);
+    col->max_span64 = max_span64;
+    col->max_row = max_row;
+    if (c.col->plain_bytes == 1) col->plain_bytes = 1;
+    if (c.col->high_sample == 0) col->high_sample = 0;
+    out.host[k] = Rec{ptr<uint8_t>(col->chars), out.off32 ? col->offsets32->p : col->offsets->p, ptr<uint8_t>(col->validity),
+                      ptr<const int64_t>(out.base) + (int64_t)k * (n + 1)};
+    cols.push_back(std::move(col));
+  }
+  out.dev = dev_alloc(sizeof(Rec) * ncols, s);
+  CS_HIP(hipMemcpyAsync(out.dev->p, out.host.data(), sizeof(Rec) * ncols, hipMemcpyHostToDevice, s));
+  return out;
+}
+
+// ---- the tile kernels proper (k_split_measure2 + k_split_emit4): runs of sub-tiles per wave.  Rows up to 92-93 bytes on
+// 96-bit masks and 64-row spans up to 6 KB; a plain split (one-byte delimiter, no limit) also rows up to 188 bytes on six
+// mask words, spans up to 8 KB and 64 columns -- BASELINE's C5 column, which left these kernels until round 6
+struct Emit4Tiles {
+  int cap_in, cap_out;  // a wave's in and out tile
+  size_t lds;           // a workgroup's
+};
+Emit4Tiles emit4_tiles(int64_t span, int ncols) {
+  Emit4Tiles t;
+  // regions of the out tile: every token byte once, up to 15 carried bytes and up to 15 bytes of padding per column, 20 bytes of OR slack
+  t.cap_out = (int)((span + 31 * ncols + 48 + 15) & ~(int64_t)15);
+  // (the in tile also holds the flush tables once the column loop is over)
+  t.cap_in = std::max((int)((span + 15 + 32 + 15) & ~(int64_t)15), kEmit4TableBytes);
+  t.lds = 288 + (size_t)(16 + t.cap_in + 32 + t.cap_out) * (kEmit3Threads / 64);
+  return t;
+}
+// the emit pass of split_on_tiles: the columns, the launch, the wait
+void split_emit_tiles(const SplitCall& c, const SplitPlan& p, const SplitRuns& r, const Measured& got, const Emit4Tiles& t, const Buf& colsum,
+                      std::vector<std::unique_ptr<cs_column>>& cols) {
+  const hipStream_t s = c.s;
+  // (a column gets at most `bound` bytes from one sub-tile -- the measure pass: every row's longest token, summed --, no
+  // token is longer than its row)
+  const MeasuredColumns<ColOut2> out =
+      measured_columns<ColOut2>(c, ptr<int32_t>(colsum), r.nseg, got.ncols, got.bound, std::min<int64_t>(got.longest_row, got.bound), cols);
+  for (const ColOut2& o : out.host)  // (a column's state in the kernel is its position)
+    if (((uintptr_t)o.chars & 15) != 0) fail(CS_ERR_INTERNAL, "split: a column's chars buffer is not 16-byte aligned");
+  Emit2Args e2{view_of(c.col), c.dpat, c.d64, c.dlen, c.tokens, p.cap_in, 0, got.ncols, r.nsub, r.per, r.segs_per_run, ptr<const ColOut2>(out.dev), nullptr,
+               c.reverse ? 1 : 0, cs::cfg_int("CS_SPLIT_DEBUG", 0)};
+#if defined(CS_PHASE_PROF)
+  Buf profbuf = dev_alloc(64, s);
+  CS_HIP(hipMemsetAsync(profbuf->p, 0, 64, s));
+  e2.prof = ptr<unsigned long long>(profbuf);
+#endif
+  const Emit4Kernel kern = emit4_kernel(c.mode, p.walk_words, out.off32);
+  if (t.lds > 48 * 1024) CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)t.lds));
+  Emit3Args e3{e2, t.cap_in, t.cap_out};
+  constexpr int wpg = kEmit3Threads / 64;
+  const unsigned grid = (unsigned)((r.runs + wpg - 1) / wpg);
+  {
+    ProfScope ps("k_split_emit", s);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kEmit3Threads), t.lds, s, e3);
+  }
+  note_route(p.walk_words == 6 ? "split-tiles-188" : (p.walk_words == 3 ? "split-tiles-92" : "split-tiles"));
+  CS_HIP(hipGetLastError());
+  CS_HIP(hipStreamSynchronize(s));  // `out` lifetime
+#if defined(CS_PHASE_PROF)
+  unsigned long long ph[6];
+  CS_HIP(hipMemcpy(ph, e2.prof, sizeof(ph), hipMemcpyDeviceToHost));
+  const double it = (double)r.nsub;
+  fprintf(stderr, "emit cycles/wave-iteration (emit4: stage, masks, column loop, column lanes, flush, store drain): %.0f %.0f %.0f %.0f %.0f %.0f | grid %u lds %zu\n",
+          ph[0] / it, ph[1] / it, ph[2] / it, ph[3] / it, ph[4] / it, ph[5] / it, grid, t.lds);
+#endif
+}
+enum class Tiles {
+  done,      // the columns are written
+  no,        // a column of nulls only, or more columns than any tile kernel keeps: the row-wise kernels
+  declined,  // what the measure pass found is not for k_split_emit4: the first generation, where it takes the call
+};
+Tiles split_on_tiles(const SplitCall& c, const SplitPlan& p, const SplitCounts& m, std::vector<std::unique_ptr<cs_column>>& cols) {
+  const hipStream_t s = c.s;
+  int dev = 0, cus = 0;
+  CS_HIP(hipGetDevice(&dev));
+  CS_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  const SplitRuns r = split_runs(c.col->rows, cus);
+  const int maxc = p.walk_words == 6 ? kMaxColsLong : kMaxCols;
+  Buf colsum = dev_alloc(sizeof(int32_t) * r.nseg * maxc, s);
+  CS_HIP(hipMemsetAsync(colsum->p, 0, sizeof(int32_t) * r.nseg * maxc, s));
+  CS_HIP(hipMemsetAsync(m.dev->p, 0, 4 * sizeof(int), s));
+  // the single pass (cs_split1.hip), on request: measured slower than the two passes below (NOTES.md, round 4:
+  // 8.0 against 6.7 ms on the 100M-row column); they also take over when it gives up
 #if defined(CS_EXPERIMENTS)  // (cs_split1.hip is in the experiments build only: `make exp`)
-    if (walk_words != 6 && cs::cfg("CS_SPLIT_SINGLE") && !cs::cfg("CS_SPLIT_OFF64") && split_single(col, delim, dlen, tokens, s, cols, reverse, span, walk_words == 3) == 1) return true;
+  if (p.walk_words != 6 && cs::cfg("CS_SPLIT_SINGLE") && !cs::cfg("CS_SPLIT_OFF64") && split_single(c, p, cols) == 1) return Tiles::done;
 #endif
-    cols.clear();
-    Measure2Args ma{view_of(col), dpat, d64, dlen, tokens, cap_in, nsub, per, seg, nseg, segs_per_run, reverse ? 1 : 0, ptr<int32_t>(colsum), ptr<int>(mx)};
-    {
-      ProfScope ps("k_split_measure", s);
-      const unsigned g = (unsigned)((nseg + 3) / 4);
-      const size_t lds = (size_t)(cap_in + 32) * 4;
-      if (mode == 1) hipLaunchKernelGGL(k_split_measure2<1>, dim3(g), dim3(256), lds, s, ma);
-      else if (mode == 2) hipLaunchKernelGGL(k_split_measure2<2>, dim3(g), dim3(256), lds, s, ma);
-      else if (walk_words == 6) hipLaunchKernelGGL((k_split_measure2<0, true, 6>), dim3(g), dim3(256), lds, s, ma);
-      else if (walk_words == 3) hipLaunchKernelGGL((k_split_measure2<0, true, 3>), dim3(g), dim3(256), lds, s, ma);
-      else hipLaunchKernelGGL(k_split_measure2<0>, dim3(g), dim3(256), lds, s, ma);
-    }
-    CS_HIP(hipGetLastError());
-    CS_HIP(hipMemcpyAsync(hmx, mx->p, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
-    CS_HIP(hipStreamSynchronize(s));
-    const int ncols = hmx[0], bound = hmx[1], longest_row = hmx[2];
-    if (ncols == 0 || ncols > kMaxColsWide) return false;  // all-null column / too many columns: generic path
-    // regions of the out tile: every token byte once, up to 15 carried bytes and up to 15 bytes of padding per column, 20 bytes of OR slack
-    const int cap_out3 = (int)((span + 31 * ncols + 48 + 15) & ~(int64_t)15);
-    // (the in tile also holds the flush tables once the column loop is over)
-    const int cap_in3 = std::max((int)((span + 15 + 32 + 15) & ~(int64_t)15), kEmit4TableBytes);
-    const size_t lds3 = 288 + (size_t)(16 + cap_in3 + 32 + cap_out3) * (kEmit3Threads / 64);
-    const bool emit4_ok = !hmx[3] && ncols <= maxc && longest_row + 3 <= (plain_walk ? 32 * walk_words - 1 : 96) && cap_out3 <= kEmit4MaxOut && lds3 <= 64 * 1024;
-    if (emit4_ok) {
-      // per column: position of every segment in the column's chars buffer
-      Buf base = dev_alloc(sizeof(int64_t) * (nseg + 1) * ncols, s);
-      std::vector<int64_t> totals(ncols);
-      offsets_from_lengths_segmented(ptr<int32_t>(colsum), nseg, ncols, ptr<int64_t>(base), totals.data(), s);
-      bool off32 = !cs::cfg("CS_SPLIT_OFF64");
-      for (int k = 0; k < ncols; ++k) off32 = off32 && totals[k] < ((int64_t)1 << 31);
-      std::vector<ColOut2> outs(ncols);
-      for (int k = 0; k < ncols; ++k) {
-        auto c = std::make_unique<cs_column>();
-        c->rows = rows;
-        c->nbytes = totals[k];
-        c->chars = dev_alloc((size_t)totals[k], s);
-        if (off32) c->offsets32 = dev_alloc(sizeof(int32_t) * (rows + 1), s);
-        else c->offsets = dev_alloc(sizeof(int64_t) * (rows + 1), s);
-        c->validity = dev_alloc(validity_bytes(rows), s);
-        // column metadata for free (upper bounds: they size staging buffers and pick routes): a column gets at most `bound`
-        // bytes from one sub-tile (the measure pass: every row's longest token, summed), no token is longer than its row;
-        // tokens cut at ASCII delimiters out of a plain column are plain
-        c->max_span64 = bound;
-        c->max_row = std::min<int64_t>(longest_row, bound);
-        if (col->plain_bytes == 1) c->plain_bytes = 1;
-        if (col->high_sample == 0) c->high_sample = 0;
-        if (((uintptr_t)ptr<uint8_t>(c->chars) & 15) != 0) fail(CS_ERR_INTERNAL, "split: a column's chars buffer is not 16-byte aligned");  // (a column's state is its position)
-        outs[k] = ColOut2{ptr<uint8_t>(c->chars), off32 ? c->offsets32->p : c->offsets->p, ptr<uint8_t>(c->validity),
-                          ptr<const int64_t>(base) + (int64_t)k * (nseg + 1)};
-        cols.push_back(std::move(c));
-      }
-      Buf d_outs = dev_alloc(sizeof(ColOut2) * ncols, s);
-      CS_HIP(hipMemcpyAsync(d_outs->p, outs.data(), sizeof(ColOut2) * ncols, hipMemcpyHostToDevice, s));
-      Emit2Args e2{view_of(col), dpat, d64, dlen, tokens, cap_in, 0, ncols, nsub, per, segs_per_run, ptr<const ColOut2>(d_outs), nullptr,
-                   reverse ? 1 : 0, cs::cfg_int("CS_SPLIT_DEBUG", 0)};
-#if defined(CS_PHASE_PROF)
-      Buf profbuf = dev_alloc(64, s);
-      CS_HIP(hipMemsetAsync(profbuf->p, 0, 64, s));
-      e2.prof = ptr<unsigned long long>(profbuf);
-#endif
-      typedef void (*Emit3Kernel)(Emit3Args);
-      static const Emit3Kernel kerns4[2][3] = {{k_split_emit4<0, false, false>, k_split_emit4<1, false, false>, k_split_emit4<2, false, false>},
-                                               {k_split_emit4<0, true, false>, k_split_emit4<1, true, false>, k_split_emit4<2, true, false>}};
-      const Emit3Kernel kern3 = walk_words == 6   ? (off32 ? k_split_emit4<0, true, true, 6, 8> : k_split_emit4<0, false, true, 6, 8>)
-                                : walk_words == 3 ? (off32 ? k_split_emit4<0, true, true> : k_split_emit4<0, false, true>)
-                                                  : kerns4[off32 ? 1 : 0][mode];
-      if (lds3 > 48 * 1024) CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern3), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3));
-      Emit3Args e3{e2, cap_in3, cap_out3};
-      constexpr int wpg = kEmit3Threads / 64;
-      const unsigned g2 = (unsigned)((runs + wpg - 1) / wpg);
-      {
-        ProfScope ps("k_split_emit", s);
-        hipLaunchKernelGGL(kern3, dim3(g2), dim3(kEmit3Threads), lds3, s, e3);
-      }
-      note_route(walk_words == 6 ? "split-tiles-188" : (walk_words == 3 ? "split-tiles-92" : "split-tiles"));
-      CS_HIP(hipGetLastError());
-      CS_HIP(hipStreamSynchronize(s));  // `outs` / `base` lifetime
-#if defined(CS_PHASE_PROF)
-      {
-        unsigned long long ph[6];
-        CS_HIP(hipMemcpy(ph, e2.prof, sizeof(ph), hipMemcpyDeviceToHost));
-        const double it = (double)nsub;
-        fprintf(stderr, "emit cycles/wave-iteration (emit4: stage, masks, column loop, column lanes, flush, store drain): %.0f %.0f %.0f %.0f %.0f %.0f | grid %u lds %zu\n",
-                ph[0] / it, ph[1] / it, ph[2] / it, ph[3] / it, ph[4] / it, ph[5] / it, g2, lds3);
-      }
-#endif
-      return true;
-    }
-    if (mode != 0 || reverse) return false;  // whitespace, multi-byte delimiters and rsplit exist in the masked kernels only
-  } else if (mode != 0 || reverse) {
-    return false;
-  }
-
-  // ---- first generation (one-byte delimiter; rows beyond 188 bytes, wide tiles, more than 32 / 64 columns): one sub-tile per wave
-  const int64_t nsub1 = (rows + rows_per_sub - 1) / rows_per_sub;  // (sub-tiles of rows_per_sub rows)
-  const unsigned grid = (unsigned)((nsub1 + 3) / 4);
-  Buf colsum = dev_alloc(sizeof(int32_t) * nsub1 * kMaxColsWide, s);
-  CS_HIP(hipMemsetAsync(colsum->p, 0, sizeof(int32_t) * nsub1 * kMaxColsWide, s));  // columns a sub-tile never reaches
-  CS_HIP(hipMemsetAsync(mx->p, 0, 4 * sizeof(int), s));
-  MeasureArgs ma{view_of(col), dpat, d64, dlen, tokens, cap_in, nsub1, rows_per_sub, ptr<int32_t>(colsum), ptr<int>(mx)};
+  cols.clear();
+  Measure2Args ma{view_of(c.col), c.dpat, c.d64, c.dlen, c.tokens, p.cap_in, r.nsub, r.per, r.seg, r.nseg, r.segs_per_run, c.reverse ? 1 : 0, ptr<int32_t>(colsum),
+                  ptr<int>(m.dev)};
   {
     ProfScope ps("k_split_measure", s);
-    hipLaunchKernelGGL(k_split_measure<0>, dim3(grid), dim3(256), (size_t)(cap_in + 32) * 4, s, ma);
+    hipLaunchKernelGGL(measure2_kernel(c.mode, p.walk_words), dim3((unsigned)((r.nseg + 3) / 4)), dim3(256), (size_t)(p.cap_in + 32) * 4, s, ma);
   }
-  CS_HIP(hipGetLastError());
-  CS_HIP(hipMemcpyAsync(hmx, mx->p, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
-  CS_HIP(hipStreamSynchronize(s));
-  const int ncols = hmx[0], widest1 = hmx[1], longest1 = hmx[2];  // (copied: the scratch is re-used by the scan below)
-  if (ncols == 0 || ncols > kMaxColsWide) return false;  // all-null column / too many columns: generic path
+  const Measured got = read_counts(m, s);
+  if (got.ncols == 0 || got.ncols > kMaxColsWide) return Tiles::no;
+  const Emit4Tiles t = emit4_tiles(p.span, got.ncols);
+  const bool emit4_ok = !got.generic && got.ncols <= maxc && got.longest_row + 3 <= (p.walk_words ? 32 * p.walk_words - 1 : 96) && t.cap_out <= kEmit4MaxOut &&
+                        t.lds <= 64 * 1024;
+  if (!emit4_ok) return Tiles::declined;
+  split_emit_tiles(c, p, r, got, t, colsum, cols);
+  return Tiles::done;
+}
 
-  // per column: position of every sub-tile in the column's chars buffer
-  Buf base = dev_alloc(sizeof(int64_t) * (nsub1 + 1) * ncols, s);
-  std::vector<int64_t> totals(ncols);
-  offsets_from_lengths_segmented(ptr<int32_t>(colsum), nsub1, ncols, ptr<int64_t>(base), totals.data(), s);
-
-  // int32 offsets (as the later generations write them) when every column stays below 2 GiB: half the offset bytes
-  bool off32 = !cs::cfg("CS_SPLIT_OFF64");
-  for (int k = 0; k < ncols; ++k) off32 = off32 && totals[k] < ((int64_t)1 << 31);
-  std::vector<ColOut> outs(ncols);
-  for (int k = 0; k < ncols; ++k) {
-    auto c = std::make_unique<cs_column>();
-    c->rows = rows;
-    c->nbytes = totals[k];
-    c->chars = dev_alloc((size_t)totals[k], s);
-    if (off32) c->offsets32 = dev_alloc(sizeof(int32_t) * (rows + 1), s);
-    else c->offsets = dev_alloc(sizeof(int64_t) * (rows + 1), s);
-    c->validity = dev_alloc(validity_bytes(rows), s);
-    // (upper bounds: hmx[1] is the most bytes any column gets from one sub-tile of rows_per_sub rows)
-    c->max_span64 = (int64_t)widest1 * (kSub / rows_per_sub);
-    c->max_row = std::min<int64_t>(longest1, widest1);
-    if (col->plain_bytes == 1) c->plain_bytes = 1;
-    if (col->high_sample == 0) c->high_sample = 0;
-    outs[k] = ColOut{ptr<uint8_t>(c->chars), off32 ? c->offsets32->p : c->offsets->p, ptr<uint8_t>(c->validity),
-                     ptr<const int64_t>(base) + (int64_t)k * (nsub1 + 1)};
-    cols.push_back(std::move(c));
+// ---- first generation (one-byte delimiter; rows beyond 188 bytes, wide tiles, more than 32 / 64 columns): one sub-tile
+// of p.rows_per_sub rows per wave.  false: a column of nulls only or too many columns, the row-wise kernels
+bool split_first_generation(const SplitCall& c, const SplitPlan& p, const SplitCounts& m, std::vector<std::unique_ptr<cs_column>>& cols) {
+  const hipStream_t s = c.s;
+  const int64_t nsub = (c.col->rows + p.rows_per_sub - 1) / p.rows_per_sub;
+  const unsigned grid = (unsigned)((nsub + 3) / 4);
+  Buf colsum = dev_alloc(sizeof(int32_t) * nsub * kMaxColsWide, s);
+  CS_HIP(hipMemsetAsync(colsum->p, 0, sizeof(int32_t) * nsub * kMaxColsWide, s));  // columns a sub-tile never reaches
+  CS_HIP(hipMemsetAsync(m.dev->p, 0, 4 * sizeof(int), s));
+  MeasureArgs ma{view_of(c.col), c.dpat, c.d64, c.dlen, c.tokens, p.cap_in, nsub, p.rows_per_sub, ptr<int32_t>(colsum), ptr<int>(m.dev)};
+  {
+    ProfScope ps("k_split_measure", s);
+    hipLaunchKernelGGL(measure_kernel(), dim3(grid), dim3(256), (size_t)(p.cap_in + 32) * 4, s, ma);
   }
-  Buf d_outs = dev_alloc(sizeof(ColOut) * ncols, s);
-  CS_HIP(hipMemcpyAsync(d_outs->p, outs.data(), sizeof(ColOut) * ncols, hipMemcpyHostToDevice, s));
-  EmitArgs ea{view_of(col), dpat, rows_per_sub, tokens, cap_in, cap_out, ncols, nsub1, ptr<const ColOut>(d_outs)};
-  const size_t lds = (size_t)(cap_in + cap_out + 64) * 4;
-  auto kern = off32 ? &k_split_emit<true> : &k_split_emit<false>;
+  const Measured got = read_counts(m, s);
+  if (got.ncols == 0 || got.ncols > kMaxColsWide) return false;
+  // (upper bounds: `bound` is the most bytes any column gets from one sub-tile of rows_per_sub rows)
+  const MeasuredColumns<ColOut> out = measured_columns<ColOut>(c, ptr<int32_t>(colsum), nsub, got.ncols, (int64_t)got.bound * (kSub / p.rows_per_sub),
+                                                              std::min<int64_t>(got.longest_row, got.bound), cols);
+  EmitArgs ea{view_of(c.col), c.dpat, p.rows_per_sub, c.tokens, p.cap_in, p.cap_out, got.ncols, nsub, ptr<const ColOut>(out.dev)};
+  const size_t lds = (size_t)(p.cap_in + p.cap_out + 64) * 4;
+  const EmitKernel kern = emit_kernel(out.off32);
   if (lds > 48 * 1024) CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   {
     ProfScope ps("k_split_emit", s);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, ea);
   }
   CS_HIP(hipGetLastError());
-  CS_HIP(hipStreamSynchronize(s));  // `outs` / `base` lifetime
+  CS_HIP(hipStreamSynchronize(s));  // `out` lifetime
   note_route("split-first-generation");
   return true;
+}
+
+}  // namespace
+
+namespace cs {
+
+bool split_fast(const SplitCall& c, std::vector<std::unique_ptr<cs_column>>& cols) {
+  if (c.reverse && (c.mode != 0 || c.tokens <= 0)) return false;  // (rsplit: with a limit on a one-byte delimiter, or not here)
+  if (c.col->rows == 0 || cs::cfg("CS_SPLIT_GENERIC")) return false;
+  SplitPlan p = split_tile_plan(c);
+  if (!p.fits) return false;
+  const SplitCounts m{dev_alloc(4 * sizeof(int), c.s), (int*)pinned_scratch(4 * sizeof(int))};
+  p.walk_words = split_walk_words(c);
+  const bool tiles_ok = p.cap_in <= cstile::kPfBytes || (p.walk_words == 6 && p.cap_in <= 8 * 1024);
+  if (p.rows_per_sub == kSub && !p.outliers && tiles_ok && !cs::cfg("CS_SPLIT_OLD_EMIT")) {
+    const Tiles t = split_on_tiles(c, p, m, cols);
+    if (t != Tiles::declined) return t == Tiles::done;
+  }
+  if (c.mode != 0 || c.reverse) return false;  // whitespace, multi-byte delimiters and rsplit exist in the masked kernels only
+  return split_first_generation(c, p, m, cols);
 }
 
 }  // namespace cs

@@ -39,12 +39,6 @@
 using namespace cs;
 using namespace csdev;
 
-namespace cs {
-// returns 1: columns written; 0: not this path's case (nothing done); -1: the single pass gave up (fallback counted)
-int split_single(const cs_column* col, const unsigned char* delim, int dlen, int tokens, hipStream_t s,
-                 std::vector<std::unique_ptr<cs_column>>& cols, bool reverse, int64_t span, bool plain_walk);
-}
-
 namespace {
 
 constexpr int kCols1 = 24;          // columns the single pass provisions at most (a register per pair of columns, three times)
@@ -720,20 +714,35 @@ __global__ void __launch_bounds__(256) k_split_fixup(FixupArgs a) {
   }
 }
 
+// the kernel forms: the instantiations of a family are named here and nowhere else, in the order of the code object
+typedef void (*SampleKernel)(SampleArgs);
+SampleKernel sample_kernel(int mode) {
+  if (mode == 1) return k_split_sample<1>;
+  if (mode == 2) return k_split_sample<2>;
+  return k_split_sample<0>;
+}
+typedef void (*Emit5Kernel)(Emit5Args);
+Emit5Kernel emit5_kernel(int mode, bool plain_walk) {
+  static const Emit5Kernel general[3] = {k_split_emit5<0, false>, k_split_emit5<1, false>, k_split_emit5<2, false>};
+  return plain_walk ? k_split_emit5<0, true> : general[mode];
+}
+
 }  // namespace
 
 namespace cs {
 
-int split_single(const cs_column* col, const unsigned char* delim, int dlen, int tokens, hipStream_t s,
-                 std::vector<std::unique_ptr<cs_column>>& cols, bool reverse, int64_t span, bool plain_walk) {
-  const bool ws = delim == nullptr;
-  const int mode = ws ? 1 : (dlen > 1 ? 2 : 0);
+// `p`: split_fast's plan -- 64-row tiles of at most p.span bytes; the sentinel walk where it is the three-word one
+int split_single(const SplitCall& c, const SplitPlan& p, std::vector<std::unique_ptr<cs_column>>& cols) {
+  const cs_column* col = c.col;
+  const hipStream_t s = c.s;
+  const int mode = c.mode, dlen = c.dlen, tokens = c.tokens;
+  const bool reverse = c.reverse, plain_walk = p.walk_words == 3;
+  const unsigned long long d64 = c.d64;
+  const uint32_t dpat = c.dpat;
+  const int64_t span = p.span;
   const int64_t rows = col->rows;
   if (rows + 1 >= ((int64_t)1 << 31)) return 0;
   if (max_row_bytes(col, s) + 3 > 96) return 0;  // (every row inside the 96-bit masks)
-  unsigned long long d64 = 0;
-  for (int i = 0; !ws && i < dlen; ++i) d64 |= (unsigned long long)delim[i] << (8 * i);
-  const uint32_t dpat = 0x01010101u * (ws ? 0u : (uint32_t)delim[0]);
   const int64_t nsub = (rows + kSub - 1) / kSub;
   const int cap_in = (int)((span + 15 + 32 + 15) & ~(int64_t)15);
 
@@ -748,9 +757,7 @@ int split_single(const cs_column* col, const unsigned char* delim, int dlen, int
     ProfScope ps("k_split_sample", s);
     const unsigned g = (unsigned)((std::min<int64_t>(nsamp, 4096) + 3) / 4);
     const size_t lds = (size_t)(cap_in + 32) * 4;
-    if (mode == 1) hipLaunchKernelGGL(k_split_sample<1>, dim3(g), dim3(256), lds, s, sa);
-    else if (mode == 2) hipLaunchKernelGGL(k_split_sample<2>, dim3(g), dim3(256), lds, s, sa);
-    else hipLaunchKernelGGL(k_split_sample<0>, dim3(g), dim3(256), lds, s, sa);
+    hipLaunchKernelGGL(sample_kernel(mode), dim3(g), dim3(256), lds, s, sa);
   }
   CS_HIP(hipGetLastError());
   struct HostSample {
@@ -789,9 +796,7 @@ int split_single(const cs_column* col, const unsigned char* delim, int dlen, int
   wave_bytes = (wave_bytes + 15) & ~15;
   const size_t lds = 288 + (size_t)wave_bytes * (kThreads1 / 64);
   if (lds > 160 * 1024) return 0;
-  typedef void (*Kernel)(Emit5Args);
-  static const Kernel kerns[3] = {k_split_emit5<0, false>, k_split_emit5<1, false>, k_split_emit5<2, false>};
-  const Kernel kern = plain_walk ? k_split_emit5<0, true> : kerns[mode];
+  const Emit5Kernel kern = emit5_kernel(mode, plain_walk);
   if (lds > 48 * 1024) CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   int dev = 0, cus = 0, per_cu = 0;
   CS_HIP(hipGetDevice(&dev));

@@ -1,7 +1,9 @@
-"""The launches of the replace route or of the scan route, case by case (dev tool): which kernels a call starts, on what
-grid and with how much dynamic LDS, for every case of tests/test_gpu_replace_forms.py (`run replace`: plus bench.py's
-pattern on a 1M-row generated column) or of tests/test_gpu_scan_forms.py (`run scan`: plus contains_re and count_re of
-that pattern on the same column).  Two builds whose listings agree start the same kernels.
+"""The launches of the replace route, of the scan route or of the split route, case by case (dev tool): which kernels a
+call starts, on what grid and with how much dynamic LDS, for every case of tests/test_gpu_replace_forms.py (`run
+replace`: plus bench.py's pattern on a 1M-row generated column), of tests/test_gpu_scan_forms.py (`run scan`: plus
+contains_re and count_re of that pattern on the same column) or of tests/test_gpu_split_forms.py (`run split`: plus
+split(' ') on that column; the single pass's cases where the library has the experiments).  Two builds whose listings
+agree start the same kernels.
 
     rocprofv3 --kernel-trace --output-format json -d DIR -- python tools/replace_launches.py run scan 2> DIR/stream_info.txt
     python tools/replace_launches.py list DIR > listing.txt
@@ -66,6 +68,24 @@ def run(table):
         bench = gpuutil.synth(3, 0, 1_000_000)
         for i in range(2):  # (the second call finds the column's metadata cached)
             call("bench-1M-%d" % i, (), lambda: replace(bench, forms.RE, forms.IPV4, "<IP>", -1))
+    elif table == "split":
+        import test_gpu_split_forms as splits
+
+        def split(g, op, delim, maxsplit, switches):  # (the table's switches may carry a value: NAME=VALUE)
+            pairs = [(v.split("=") + ["1"])[:2] for v in switches]
+            for k, v in pairs:
+                L.check(L.lib.cs_config_set(k.encode(), v.encode()))
+            try:
+                getattr(g, op)(delim, maxsplit)
+            finally:
+                for k, _ in pairs:
+                    L.check(L.lib.cs_config_set(k.encode(), None))
+
+        for name, op, delim, maxsplit, kind, n, switches in splits.CASES + (splits.SINGLE if L.lib.cs_has_experiments() else []):
+            call(name, (), lambda: split(splits._col(kind, n)[1], op, delim, maxsplit, switches))
+        bench = gpuutil.synth(3, 0, 1_000_000)
+        for i in range(2):  # (the second call finds the column's metadata cached)
+            call("bench-1M-%d" % i, (), lambda: bench.split(" "))
     else:
         import test_gpu_scan_forms as scans
 
@@ -136,7 +156,7 @@ def listing(d, force_csv=False):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) >= 2 and sys.argv[1] == "run" and sys.argv[2:] in ([], ["replace"], ["scan"]):
+    if len(sys.argv) >= 2 and sys.argv[1] == "run" and sys.argv[2:] in ([], ["replace"], ["scan"], ["split"]):
         run(sys.argv[2] if sys.argv[2:] else "replace")
     elif len(sys.argv) >= 3 and sys.argv[1] == "list":
         listing(sys.argv[2], force_csv=sys.argv[3:] == ["csv"])
