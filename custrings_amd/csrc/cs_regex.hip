@@ -2987,6 +2987,29 @@ const VirtualRows* pieces_for(const cs_column* col, const cs_regex* re, hipStrea
   return virtual_rows(col, s);
 }
 
+// ---- shared by the scans and the span ops (extract, findall, replace_with_backrefs) -------------------------------------
+// The column's rows for a kernel that reads them from memory: chars from the pool carry 64 bytes of slack that may be read.
+// (cs_replace_re_multi passes col->nbytes without the slack; left as it is.)
+RowSrc row_src(const cs_column* col) { return RowSrc{view_of(col), d_unicode_flags(), col->nbytes + (col->chars && col->chars->capacity ? 64 : 0)}; }
+// The group tags' share of a stream launch's LDS: 0 when there are none or they take more than 16 KB (they stay in memory
+// then), else their size rounded up to 16.
+size_t gtags_lds_bytes(const cs_regex* re) {
+  const size_t bytes = re->gtags.size() * 4;
+  return bytes && bytes <= 16 * 1024 ? (bytes + 15) & ~size_t(15) : 0;
+}
+// What every launch of k_tdfa_scan_stream says about its input: the column, the tables, the tiles.  The caller adds its own
+// fields (tbl_bytes, the group tags, the outputs, L.in_lds = 2 for tables in memory).
+ScanStreamArgs stream_args(const cs_column* col, const TPlan& tp, const TileChoice& tc) {
+  ScanStreamArgs sa{};
+  sa.in = view_of(col);
+  sa.flags = d_unicode_flags();
+  sa.L = tp.d;
+  sa.nsub = (col->rows + tc.R - 1) / tc.R;
+  sa.rows_per_tile = tc.R;
+  sa.cap_in = tc.cap;
+  return sa;
+}
+
 // ---- contains_re / match_re / count_re: the host route ------------------------------------------------------------------
 // scan<MODE> (MODE 0 contains_re, 1 match_re, 2 count_re) runs a ScanCall as the sequence it is -- the column's pieces,
 // contains by counts, class runs, the stream kernel and the rows it put off, the row-wise kernels -- each step a function
@@ -3206,17 +3229,11 @@ bool scan_stream(const ScanRun& r) {
   const TileChoice tc = choose_tile(col, s);
   const ScanForm f = scan_form<MODE>(r, tc);
   if (!tc.R || f.lds > 150 * 1024) return false;
-  ScanStreamArgs sa{};
-  sa.in = view_of(col);
-  sa.flags = d_unicode_flags();
-  sa.L = r.tp.d;
+  ScanStreamArgs sa = stream_args(col, r.tp, tc);
   if (f.chain_global) sa.L.in_lds = 2;
   sa.out8 = out8_of<MODE>(r);
   sa.out32 = out32_of<MODE>(r);
   sa.found = r.found;
-  sa.nsub = (col->rows + tc.R - 1) / tc.R;
-  sa.rows_per_tile = tc.R;
-  sa.cap_in = tc.cap;
   sa.tbl_bytes = (int)(f.scan_tbl + f.bits_lds);
   sa.bits = f.bits_form ? ptr<const int32_t>(re->d_bits) : nullptr;
   sa.bits_off = (int)f.scan_tbl;
@@ -3282,8 +3299,7 @@ void scan(const ScanCall& c) {
   const ResultsOut res(c.results, c.esz * (size_t)col->rows, c.on_device, s);  // (before the class-runs attempt; the count after it)
   if (count_by_class_runs<MODE>(c, res)) return;
   const Buf cnt = zeroed_count(s);
-  const ScanRun r{c, tdfa, wide, tp, pl, res.dev, ptr<unsigned long long>(cnt),
-                  RowSrc{view_of(col), d_unicode_flags(), col->nbytes + (col->chars && col->chars->capacity ? 64 : 0)}};
+  const ScanRun r{c, tdfa, wide, tp, pl, res.dev, ptr<unsigned long long>(cnt), row_src(col)};
   if (!scan_stream<MODE>(r)) scan_rowwise<MODE>(r);
   CS_HIP(hipGetLastError());
   res.copy_back(s);
@@ -4139,150 +4155,485 @@ void columns_from_packed_spans(const cs_column* col, int ncols, const uint32_t* 
   CS_HIP(hipStreamSynchronize(s));  // `base` / span buffers
 }
 
+}  // extern "C"
+
+// ---- extract / findall / replace_with_backrefs: the host routes ---------------------------------------------------------
+// Each entry below reads as its sequence: the checks, the stream kernel (its FORM -- which variant of k_tdfa_scan_stream
+// runs, on how much LDS --, the launch), otherwise the row-wise kernels, then the output columns.  Every kernel family's
+// instantiations are named in one function.  As in the scans, choose_tile, sample_has_high_bytes, plan and scan<2> may
+// launch a metadata pass the first time they are asked of a column: the order of the questions is kept.
+namespace {
+
+// The spans a scan leaves for the column writers: begins / lens [k * rows + row], or -- packed -- one word a span and the
+// bytes every 64-row tile gives to each column (ScanStreamArgs::spans).
+struct SpanBufs {
+  Buf begins, lens, spans, tile_tot;
+  bool packed = false;
+  int cap = 0;  // packed: the tile size the scan staged its rows by (k_spans_write_tile2 stages by the same)
+  void alloc(int64_t rows, int width, bool pack, hipStream_t s) {
+    packed = pack;
+    if (packed) {
+      spans = dev_alloc(sizeof(uint32_t) * rows * width, s);
+      tile_tot = dev_alloc(sizeof(int32_t) * ((rows + 63) / 64) * width, s);
+    } else {
+      begins = dev_alloc(sizeof(int32_t) * rows * width, s);
+      lens = dev_alloc(sizeof(int32_t) * rows * width, s);
+    }
+  }
+  // the outputs of a stream launch of `width` columns: the pair in use, the other null
+  void give(ScanStreamArgs& sa, int width) const {
+    sa.begins = packed ? nullptr : ptr<int32_t>(begins);
+    sa.lens = packed ? nullptr : ptr<int32_t>(lens);
+    sa.spans = packed ? ptr<uint32_t>(spans) : nullptr;
+    sa.tile_tot = packed ? ptr<int32_t>(tile_tot) : nullptr;
+    sa.ncols = width;
+  }
+};
+
+// A call and what its steps share: the tagged DFA's launch plan is asked once, by the first step that needs it.
+struct SpanRun {
+  const cs_column* col;
+  cs_regex* re;
+  hipStream_t s;
+  TPlan tp{};
+  bool planned = false;
+  const TPlan& plan_once() {
+    if (!planned) tp = tplan(re, col->rows, s);
+    planned = true;
+    return tp;
+  }
+};
+
+// The output columns from begins / lens, kMaxGroups at a time through the shared write kernel: a column's offsets from its
+// lengths, its chars, then the spans' bytes.  Waits for the stream: the span buffers (and the list simulator's arena) are
+// the caller's to release.
+void columns_from_spans(const cs_column* col, int ncols, const int32_t* begins, const int32_t* lens, hipStream_t s,
+                        std::vector<std::unique_ptr<cs_column>>& cols) {
+  const int64_t rows = col->rows;
+  for (int k0 = 0; k0 < ncols; k0 += kMaxGroups) {
+    const int nk = std::min(kMaxGroups, ncols - k0);
+    ExtractOut eo{};
+    for (int k = 0; k < nk; ++k) {
+      Built b(rows, Nulls::fused, s);
+      b.scan(lens + (size_t)(k0 + k) * rows);
+      eo.off[k] = b.off;
+      eo.chars[k] = b.alloc_chars();
+      cols.push_back(std::move(b.col));
+    }
+    write_spans(col, nk, begins + (size_t)k0 * rows, lens + (size_t)k0 * rows, eo, s);
+  }
+  CS_HIP(hipGetLastError());
+  CS_HIP(hipStreamSynchronize(s));
+}
+void columns_from(const cs_column* col, int ncols, const SpanBufs& sp, hipStream_t s, std::vector<std::unique_ptr<cs_column>>& cols) {
+  if (sp.packed) columns_from_packed_spans(col, ncols, ptr<const uint32_t>(sp.spans), ptr<const int32_t>(sp.tile_tot), sp.cap, s, cols);
+  else columns_from_spans(col, ncols, ptr<int32_t>(sp.begins), ptr<int32_t>(sp.lens), s, cols);
+}
+
+// ---- extract ----
+// Which variant of k_tdfa_scan_stream<4, ..> runs, and on how much LDS.
+struct ExtractForm {
+  // a chain pattern whose groups are runs of items, on a column whose sample is plain ASCII: the match and the group ranges
+  // by mask arithmetic; it keeps the "equals x" bitmap and the unit form's layout
+  bool chain_form;
+  // ... with the tables in memory: a fourth workgroup per CU -- the kernel is built for 128 registers then
+  bool chain_mem;
+  bool packed;      // 64-row tiles: packed spans and tile totals, no pass over the lengths
+  size_t tbl_x;     // bytes of the automaton's tables in LDS: all of them, or -- chain_mem -- header + tail words
+  size_t gt_bytes;  // the group tags behind them
+  size_t lds;       // dynamic LDS of a workgroup; beyond 150 KB there is no stream launch
+  ScanStreamKernel kern;
+};
+// The instantiations of k_tdfa_scan_stream extract holds: <4, IN_LDS, LONG, UNITS, CHAIN>.
+ScanStreamKernel extract_stream_kernel(bool lng, bool chain_form, bool chain_mem) {
+  if (!chain_form) return lng ? &k_tdfa_scan_stream<4, true, true> : &k_tdfa_scan_stream<4, true, false>;
+  return chain_mem ? &k_tdfa_scan_stream<4, false, false, true, true> : &k_tdfa_scan_stream<4, true, false, true, true>;
+}
+ExtractForm extract_form(const SpanRun& r, int groups, const TileChoice& tc) {
+  const cs_regex* re = r.re;
+  const int cap = tc.cap;
+  ExtractForm f{};
+  f.gt_bytes = gtags_lds_bytes(re);
+  f.chain_form = r.tp.d.in_lds && tc.R == 64 && !tc.lng && !cs::cfg("CS_SPANS_UNPACKED") && ((re->tdfa[30] >> 16) & 15) != 0 && ((re->tdfa[30] >> 20) & 1) != 0 &&
+                 groups <= 4 && !cs::cfg("CS_NO_CHAIN_FORM") && !sample_has_high_bytes(r.col, r.s);
+  f.chain_mem = f.chain_form && !cs::cfg("CS_CHAIN_TABLES_IN_LDS");
+  f.tbl_x = f.chain_mem ? (size_t)cstd::kHeadTailWords * 4 : r.tp.lds_bytes;
+  f.lds = f.chain_form ? f.tbl_x + f.gt_bytes + (size_t)(cap + 32 + 2 * ((cap >> 3) + 32) + kUnitQueue * 4 + 64 * 4 + 16) * 4
+                       : r.tp.lds_bytes + f.gt_bytes + (size_t)(cap + 32 + (cap >> 3) + 32 + cstd::Tdfa::kBackSteps * 64 + kMaxGroups * 4) * 4;
+  f.packed = tc.R == 64 && !cs::cfg("CS_SPANS_UNPACKED");
+  f.kern = extract_stream_kernel(tc.lng, f.chain_form, f.chain_mem);
+  return f;
+}
+
+// The stream kernel: rows staged through LDS tiles, the DFA carries the group ranges.
+bool extract_stream(SpanRun& r, int groups, SpanBufs& sp) {
+  const hipStream_t s = r.s;
+  const TPlan& tp = r.plan_once();
+  const TileChoice tc = choose_tile(r.col, s);
+  const ExtractForm f = extract_form(r, groups, tc);
+  if (!tp.d.in_lds || !tc.R || f.lds > 150 * 1024) return false;
+  sp.alloc(r.col->rows, groups, f.packed, s);
+  sp.cap = tc.cap;
+  const Buf cnt = zeroed_count(s);
+  ScanStreamArgs sa = stream_args(r.col, tp, tc);
+  sa.found = ptr<unsigned long long>(cnt);
+  sa.tbl_bytes = (int)(f.tbl_x + f.gt_bytes);
+  sa.gt_off = (int)f.tbl_x;
+  if (f.chain_mem) sa.L.in_lds = 2;
+  sa.gt_words = f.gt_bytes ? (int)r.re->gtags.size() : 0;
+  sp.give(sa, groups);
+  sa.gtags = ptr<const int32_t>(r.re->d_gtags);
+  ProfScope ps("k_extract_spans", s);
+  launch_resident(f.kern, f.lds, (sa.nsub + 3) / 4, s, sa);
+  return true;
+}
+
+// The row-wise kernels' instantiations, a family each: the DFA with the group ranges, the DFA for the match and the list
+// simulator for the groups, the list simulator alone (SMALL: at most 64 instructions).
+using ExtractDfaKernel = void (*)(RowSrc, TLaunch, const int32_t*, int, int32_t*, int32_t*);
+using ExtractTdfaKernel = void (*)(RowSrc, TLaunch, Launch, int, int, int32_t*, int32_t*);
+using ExtractListKernel = void (*)(RowSrc, Launch, int, int32_t*, int32_t*);
+ExtractDfaKernel extract_dfa_kernel(bool in_lds) { return in_lds ? &k_extract_spans_dfa<true> : &k_extract_spans_dfa<false>; }
+ExtractTdfaKernel extract_tdfa_kernel(bool in_lds, bool small) {
+  if (in_lds) return small ? &k_extract_spans_tdfa<true, true> : &k_extract_spans_tdfa<true, false>;
+  return small ? &k_extract_spans_tdfa<false, true> : &k_extract_spans_tdfa<false, false>;
+}
+ExtractListKernel extract_list_kernel(bool small) { return small ? &k_extract_spans<true> : &k_extract_spans<false>; }
+
+// A thread a row, begins / lens.  `arena`: the thread lists of the list simulation, not needed when the DFA carries the
+// group ranges; the caller keeps it until it has waited for the stream.
+void extract_rowwise(SpanRun& r, int groups, bool dfa_groups, Buf& arena, SpanBufs& sp) {
+  const hipStream_t s = r.s;
+  const int64_t rows = r.col->rows;
+  const int ninst = (int)r.re->prog.insts.size();
+  Launch L{};
+  L.image = ptr<const int32_t>(r.re->d_image);
+  L.image_words = (int)r.re->image.size();
+  L.slots = csvm::gvm_slots(ninst);
+  const size_t img_bytes = (((size_t)L.image_words + 3) & ~size_t(3)) * 4;
+  L.image_in_lds = img_bytes <= kLdsBudget / 2;
+  const unsigned grid = (unsigned)std::min<int64_t>((rows + 255) / 256, 256 * 4);
+  if (!dfa_groups) {
+    arena = dev_alloc((size_t)grid * 256 * L.slots * 4, s);
+    L.arena = ptr<uint32_t>(arena);
+  }
+  const RowSrc src = row_src(r.col);
+  sp.alloc(rows, groups, false, s);
+  int32_t* const begins = ptr<int32_t>(sp.begins);
+  int32_t* const lens = ptr<int32_t>(sp.lens);
+  if (dfa_groups) {
+    const TPlan& tp = r.plan_once();
+    ProfScope ps("k_extract_spans", s);
+    hipLaunchKernelGGL(extract_dfa_kernel(tp.d.in_lds), dim3(tp.grid), dim3(256), tp.lds_bytes, s, src, tp.d, ptr<const int32_t>(r.re->d_gtags), groups, begins, lens);
+  } else if (use_tdfa(r.re)) {
+    const TPlan& tp = r.plan_once();
+    size_t fast_bytes = (size_t)256 * csvm::GroupVm<true>::kFastSlots * 4;
+    const int use_fast = tp.lds_bytes + fast_bytes <= kLdsBudget;
+    if (!use_fast) fast_bytes = 0;
+    L.image_in_lds = tp.lds_bytes + fast_bytes + img_bytes <= kLdsBudget;
+    const size_t lds = tp.lds_bytes + fast_bytes + (L.image_in_lds ? img_bytes : 0);
+    ProfScope ps("k_extract_spans", s);
+    hipLaunchKernelGGL(extract_tdfa_kernel(tp.d.in_lds, ninst <= 64), dim3(grid), dim3(256), lds, s, src, tp.d, L, groups, use_fast, begins, lens);
+  } else {
+    ProfScope ps("k_extract_spans", s);
+    hipLaunchKernelGGL(extract_list_kernel(ninst <= 64), dim3(grid), dim3(256), L.image_in_lds ? img_bytes : 0, s, src, L, groups, begins, lens);
+  }
+}
+
+// ---- findall ----
+// Which variant of k_tdfa_scan_stream<3, ..> runs, and on how much LDS (as count_re's: scan_form).
+struct FindallForm {
+  bool units;         // the unit scan where the tagged DFA offers the decomposition
+  bool chain_scan;    // a chain pattern on a column whose sample is plain ASCII
+  bool chain_global;  // ... its tables in memory where that makes room for a fourth workgroup per CU
+  size_t lds;         // dynamic LDS of a workgroup; beyond 150 KB there is no stream launch
+  size_t scan_tbl;    // bytes of the automaton's tables in LDS: all of them, or -- chain_global -- header + tail words
+  ScanStreamKernel kern;
+};
+// (the instantiations of k_tdfa_scan_stream findall holds are named here: <3, IN_LDS, LONG, UNITS, CHAIN>)
+FindallForm findall_form(const SpanRun& r, const TileChoice& tc) {
+  const cs_regex* re = r.re;
+  const TPlan& tp = r.tp;
+  const int cap = tc.cap;
+  FindallForm f{};
+  f.units = ((re->tdfa[31] & 1) != 0 || ((re->tdfa[30] >> 16) & 15) != 0) && !tc.lng && tc.R == 64 && !cs::cfg("CS_NO_UNITS");
+  f.lds = tp.lds_bytes + (size_t)(cap + 32 + (cap >> 3) + 32 + (f.units ? (cap >> 3) + 32 + kUnitQueue * 4 + 64 * 4 + 16 : 0)) * 4;
+  f.chain_scan = f.units && ((re->tdfa[30] >> 16) & 15) != 0 && !sample_has_high_bytes(r.col, r.s) && !cs::cfg("CS_NO_CHAIN_FORM");
+  f.chain_global = f.chain_scan && tp.d.in_lds && f.lds > 40 * 1024 && f.lds - tp.lds_bytes + cstd::kHeadTailWords * 4 <= 40 * 1024 && !cs::cfg("CS_CHAIN_TABLES_IN_LDS");
+  f.scan_tbl = f.chain_global ? (size_t)cstd::kHeadTailWords * 4 : tp.lds_bytes;
+  if (f.chain_global) f.lds -= tp.lds_bytes - f.scan_tbl;
+  if (!f.units) f.kern = tc.lng ? &k_tdfa_scan_stream<3, true, true> : &k_tdfa_scan_stream<3, true, false>;
+  else if (!f.chain_scan) f.kern = &k_tdfa_scan_stream<3, true, false, true>;
+  else if (!f.chain_global) f.kern = &k_tdfa_scan_stream<3, true, false, true, true>;
+  else f.kern = &k_tdfa_scan_stream<3, false, false, true, true>;
+  return f;
+}
+
+// The largest match count of a row: an int the kernels raise, zeroed before every launch that reports it and read as the
+// four bytes it is (read_count copies a 64-bit count: another copy, so findall keeps its reader).
+int read_max(const Buf& dmax, hipStream_t s) {
+  int* hmax = (int*)pinned_scratch(8);
+  CS_HIP(hipMemcpyAsync(hmax, dmax->p, 4, hipMemcpyDeviceToHost, s));
+  CS_HIP(hipStreamSynchronize(s));
+  return hmax[0];
+}
+
+// The stream kernel reports spans and the largest match count in ONE pass when the rows hold at most kProvisional matches
+// (the span arrays are laid out [k * rows + row], so unused columns cost only memory); a column with busier rows is scanned
+// a second time with the exact column count, into span buffers of its own.  Returns the column count, -1: not taken.
+int findall_stream(SpanRun& r, const Buf& dmax, SpanBufs& sp) {
+  constexpr int kProvisional = 4;
+  const hipStream_t s = r.s;
+  const int64_t rows = r.col->rows;
+  const TPlan& tp = r.plan_once();
+  const TileChoice tc = choose_tile(r.col, s);
+  const FindallForm f = findall_form(r, tc);
+  if (!tp.d.in_lds || !tc.R || f.lds > 150 * 1024) return -1;
+  const Buf hits = zeroed_count(s);
+  ScanStreamArgs sa = stream_args(r.col, tp, tc);
+  sa.found = ptr<unsigned long long>(hits);  // (hit counter: nobody reads it, the kernel writes through it)
+  sa.tbl_bytes = (int)f.scan_tbl;
+  if (f.chain_global) sa.L.in_lds = 2;
+  sa.maxp = ptr<int>(dmax);
+  sp.cap = tc.cap;
+  int ncols = 0, width = kProvisional;
+  for (int pass = 0; pass < 2; ++pass) {
+    // (the provisional pass on 64-row tiles leaves packed spans and tile totals: k_spans_write_tile2 needs no pass
+    // over the lengths; a second pass -- rows with more than kProvisional matches -- writes begins / lens)
+    sp.alloc(rows, width, tc.R == 64 && width <= kMaxGroups && (pass == 0 || !cs::cfg("CS_SPANS_EXACT_UNPACKED")) && !cs::cfg("CS_SPANS_UNPACKED"), s);
+    CS_HIP(hipMemsetAsync(dmax->p, 0, 8, s));
+    sp.give(sa, width);
+    {
+      ProfScope ps("k_findall_spans", s);
+      launch_resident(f.kern, f.lds, (sa.nsub + 3) / 4, s, sa);
+    }
+    ncols = read_max(dmax, s);
+    if (ncols <= width) break;
+    width = ncols;  // busier rows than provisioned for: once more, exactly
+  }
+  return ncols;
+}
+
+// Matches per row (count_re: scan<2>), their maximum = the number of columns.
+int findall_count_rows(const SpanRun& r, const Buf& dmax) {
+  const hipStream_t s = r.s;
+  const int64_t rows = r.col->rows;
+  Buf counts = dev_alloc(sizeof(int32_t) * rows, s);
+  scan<2>(ScanCall{r.col, r.re, counts->p, sizeof(int32_t), 1, s, nullptr, "k_count_re"});
+  CS_HIP(hipMemsetAsync(dmax->p, 0, 8, s));
+  hipLaunchKernelGGL(k_max_i32, dim3((unsigned)std::min<int64_t>((rows + 255) / 256, 2048)), dim3(256), 0, s, ptr<int32_t>(counts), rows,
+                     ptr<int>(dmax));
+  return read_max(dmax, s);
+}
+
+// The row-wise kernels' instantiations: the tagged DFA (tables in LDS or in memory), the list simulator (SMALL: at most 64
+// instructions).
+using FindallTdfaKernel = void (*)(RowSrc, TLaunch, int, int32_t*, int32_t*);
+using FindallListKernel = void (*)(RowSrc, Launch, int, int32_t*, int32_t*);
+FindallTdfaKernel findall_tdfa_kernel(bool in_lds) { return in_lds ? &k_findall_spans_tdfa<true> : &k_findall_spans_tdfa<false>; }
+FindallListKernel findall_list_kernel(bool small) { return small ? &k_findall_spans<true> : &k_findall_spans<false>; }
+
+// A thread a row, the first `ncols` spans of every row into begins / lens.  Returns the list simulator's plan: its arena is
+// the caller's to keep until it has waited for the stream.
+Plan findall_rowwise(SpanRun& r, int ncols, SpanBufs& sp) {
+  const hipStream_t s = r.s;
+  const int64_t rows = r.col->rows;
+  const RowSrc src = row_src(r.col);
+  Plan pl{};
+  sp.alloc(rows, ncols, false, s);
+  ProfScope ps("k_findall_spans", s);
+  if (use_tdfa(r.re)) {
+    const TPlan& tp = r.plan_once();
+    hipLaunchKernelGGL(findall_tdfa_kernel(tp.d.in_lds), dim3(tp.grid), dim3(256), tp.lds_bytes, s, src, tp.d, ncols, ptr<int32_t>(sp.begins), ptr<int32_t>(sp.lens));
+  } else {
+    pl = plan(r.re, rows, s);
+    hipLaunchKernelGGL(findall_list_kernel(pl.small), dim3(pl.grid), dim3(pl.threads), pl.lds_bytes, s, src, pl.d, ncols, ptr<int32_t>(sp.begins), ptr<int32_t>(sp.lens));
+  }
+  return pl;
+}
+
+// ---- replace_with_backrefs ----
+struct BackrefTemplateText {
+  csvm::BackrefTemplate t;  // (t.text is set once the text is on the device)
+  std::string text;         // the template without its references
+};
+// backref.h:31-57: a backslash followed by digits is a reference.  Host only.
+BackrefTemplateText parse_backref_template(const char* repl, const cs_regex* re) {
+  BackrefTemplateText p{};
+  csvm::BackrefTemplate& t = p.t;
+  for (const char* c = repl; *c;) {
+    if (*c == '\\' && c[1] >= '0' && c[1] <= '9') {
+      const char* q = c + 1;
+      while (*q >= '0' && *q <= '9') ++q;
+      if (t.nrefs == csvm::BackrefTemplate::kMaxRefs) fail(CS_ERR_RANGE, "replace_with_backrefs: more than 16 references in the template");
+      t.idx[t.nrefs] = atoi(c + 1);
+      t.pos[t.nrefs] = (int)p.text.size();
+      ++t.nrefs;
+      c = q;
+    } else {
+      p.text.push_back(*c++);
+    }
+  }
+  t.bytes = (int)p.text.size();
+  t.groups = re->prog.num_groups;
+  return p;
+}
+
+// First choice: the single-pass replace kernel in its backrefs form (unit scan, one group run per match, coalesced
+// output).  It declines patterns without the unit decomposition, more than four groups, long rows; a launch that
+// runs out of output room or meets a row the unit route hands over reports it.  Says whether it answered: whatever
+// fails in there -- declined, out of room, a HIP error --, the two-pass form answers.
+bool backrefs_single_pass(const cs_column* col, cs_regex* re, const csvm::BackrefTemplate& t, bool dfa, hipStream_t s, cs_column** out) {
+  bool packs = t.bytes <= 255;  // (the kernel keeps the references' group numbers and positions packed in registers)
+  for (int j = 0; j < t.nrefs; ++j) packs = packs && t.idx[j] <= 15 && t.pos[j] <= 255;
+  if (!dfa || !packs || re->prog.num_groups < 1 || cs::cfg("CS_BACKREFS_TWO_PASS")) return false;
+  Buf d_t = dev_alloc(sizeof(csvm::BackrefTemplate), s);
+  CS_HIP(hipMemcpyAsync(d_t->p, &t, sizeof(t), hipMemcpyHostToDevice, s));
+  CS_HIP(hipStreamSynchronize(s));  // (`t` lives on the caller's stack frame)
+  cs::ReplaceCall call{col, re, "", 0, -1, s};
+  call.tmpl_host = &t;
+  call.tmpl_dev = d_t->p;
+  call.tmpl_text_bytes = t.bytes;
+  call.single_pass_only = true;
+  return guard([&] { *out = cs::replace_re_column(call); }) == CS_OK;
+}
+
+// The instantiations of the two-pass form: k_backrefs<DFA, IN_LDS, SMALL, WRITE>, a thread a row, and the stream kernel
+// k_tdfa_scan_stream<5 sizes | 6 bytes, IN_LDS, LONG>.
+using BackrefsKernel = void (*)(BackrefArgs, int32_t*, const int64_t*, uint8_t*);
+BackrefsKernel backrefs_kernel(bool dfa, bool in_lds, bool small, bool write) {
+  if (dfa && in_lds) return write ? &k_backrefs<true, true, true, true> : &k_backrefs<true, true, true, false>;
+  if (dfa) return write ? &k_backrefs<true, false, true, true> : &k_backrefs<true, false, true, false>;
+  if (small) return write ? &k_backrefs<false, false, true, true> : &k_backrefs<false, false, true, false>;
+  return write ? &k_backrefs<false, false, false, true> : &k_backrefs<false, false, false, false>;
+}
+ScanStreamKernel backrefs_stream_kernel(bool write, bool lng) {
+  if (write) return lng ? &k_tdfa_scan_stream<6, true, true> : &k_tdfa_scan_stream<6, true, false>;
+  return lng ? &k_tdfa_scan_stream<5, true, true> : &k_tdfa_scan_stream<5, true, false>;
+}
+
+// The two-pass form: sizes, offsets, bytes.  What its two launches share.
+struct BackrefsTwoPass {
+  hipStream_t s;
+  bool dfa;       // the tagged DFA carries the groups (or there are none)
+  bool small;     // the list simulator's program has at most 64 instructions
+  BackrefArgs a;  // the row-wise kernels': a thread a row
+  unsigned grid;
+  size_t lds;
+  Buf arena;      // (the list simulator's thread lists)
+  // rows staged through LDS tiles by the scan stream kernel when the DFA carries the groups and the tiles fit
+  bool stream, lng;
+  size_t slds;
+  ScanStreamArgs sa;
+  Buf d_tmpl;  // the template once more, in device memory: the stream kernel indexes it per reference
+  Buf scnt;    // the stream kernel's hit counter, made at its first launch
+};
+BackrefsTwoPass backrefs_plan(const cs_column* col, cs_regex* re, const csvm::BackrefTemplate& t, bool dfa, hipStream_t s) {
+  const int64_t rows = col->rows;
+  const int ninst = (int)re->prog.insts.size();
+  BackrefsTwoPass p{};
+  p.s = s;
+  p.dfa = dfa;
+  p.small = ninst <= 64;
+  p.a.src = row_src(col);
+  p.a.gtags = ptr<const int32_t>(re->d_gtags);
+  p.a.t = t;
+  p.grid = (unsigned)std::min<int64_t>((rows + 255) / 256, 256 * 8);
+  TPlan tp{};
+  if (dfa) {
+    tp = tplan(re, rows, s);
+    p.a.TL = tp.d;
+    p.lds = tp.lds_bytes;
+  } else {
+    p.a.L.image = ptr<const int32_t>(re->d_image);
+    p.a.L.image_words = (int)re->image.size();
+    p.a.L.slots = csvm::gvm_slots(ninst);
+    p.grid = std::min(p.grid, 1024u);
+    p.arena = dev_alloc((size_t)p.grid * 256 * p.a.L.slots * 4, s);
+    p.a.L.arena = ptr<uint32_t>(p.arena);
+  }
+  if (!(dfa && p.a.TL.in_lds && !cs::cfg("CS_REGEX_ROWWISE"))) return p;
+  const TileChoice tc = choose_tile(col, s);
+  const size_t gt_bytes = gtags_lds_bytes(re);
+  p.slds = p.lds + gt_bytes + (size_t)(tc.cap + 32 + (tc.cap >> 3) + 32) * 4;
+  if (!tc.R || p.slds > 150 * 1024) return p;
+  p.stream = true;
+  p.lng = tc.lng;
+  p.sa = stream_args(col, tp, tc);
+  p.sa.gt_off = (int)p.lds;
+  p.sa.gt_words = gt_bytes ? (int)re->gtags.size() : 0;
+  p.sa.tbl_bytes = (int)(p.lds + gt_bytes);
+  p.sa.gtags = p.a.gtags;
+  p.d_tmpl = dev_alloc(sizeof(csvm::BackrefTemplate), s);
+  CS_HIP(hipMemcpyAsync(p.d_tmpl->p, &t, sizeof(t), hipMemcpyHostToDevice, s));
+  p.sa.tmpl = ptr<const csvm::BackrefTemplate>(p.d_tmpl);
+  return p;
+}
+// One of the two launches: sizes into `lens`, or -- write -- the bytes at `off` into `chars`.
+void backrefs_launch(BackrefsTwoPass& p, bool write, int32_t* lens, const int64_t* off, uint8_t* chars) {
+  if (!p.stream) {
+    hipLaunchKernelGGL(backrefs_kernel(p.dfa, p.a.TL.in_lds, p.small, write), dim3(p.grid), dim3(256), p.lds, p.s, p.a, lens, off, chars);
+    CS_HIP(hipGetLastError());
+    return;
+  }
+  if (!p.scnt) {
+    p.scnt = zeroed_count(p.s);
+    p.sa.found = ptr<unsigned long long>(p.scnt);
+  }
+  launch_resident(backrefs_stream_kernel(write, p.lng), p.slds, (p.sa.nsub + 3) / 4, p.s, p.sa);
+}
+void backrefs_size(BackrefsTwoPass& p, int32_t* lens) {
+  p.sa.out32 = lens;
+  backrefs_launch(p, false, lens, nullptr, nullptr);
+}
+void backrefs_write(BackrefsTwoPass& p, const int64_t* off, uint8_t* chars) {
+  p.sa.out_off = off;
+  p.sa.out_chars = chars;
+  backrefs_launch(p, true, nullptr, off, chars);
+}
+
+cs_column* backrefs_two_pass(const cs_column* col, cs_regex* re, const csvm::BackrefTemplate& t, bool dfa, hipStream_t s) {
+  BackrefsTwoPass p = backrefs_plan(col, re, t, dfa, s);
+  Built b(col, s);
+  Buf lens = dev_alloc(sizeof(int32_t) * col->rows, s);
+  {
+    ProfScope ps("k_backrefs_size", s);
+    backrefs_size(p, ptr<int32_t>(lens));
+  }
+  b.scan(ptr<int32_t>(lens));
+  b.alloc_chars();
+  {
+    ProfScope ps("k_backrefs_write", s);
+    backrefs_write(p, b.off, b.chars);
+  }
+  CS_HIP(hipStreamSynchronize(s));
+  return b.col.release();
+}
+
+}  // namespace
+
+extern "C" {
+
 // NVStrings::extract(pattern, results) (NVStrings.h:682; extract.cu:69-151): one column per
 // capture group; a pattern without groups, or an empty column, yields no columns.
 int cs_extract(const cs_column* col, const cs_regex* cre, cs_stream stream, cs_column*** out_cols, int* ncols_out) {
   return guard([&] {
     if (!col || !cre || !out_cols || !ncols_out) fail(CS_ERR_INVALID_ARG, "null argument");
     require_device();
-    hipStream_t s = S(stream);
-    cs_regex* re = const_cast<cs_regex*>(cre);
+    SpanRun r{col, const_cast<cs_regex*>(cre), S(stream)};
     *out_cols = nullptr;
     *ncols_out = 0;
-    const int groups = re->prog.num_groups;
-    const int64_t rows = col->rows;
-    if (groups <= 0 || rows == 0) return;
+    const int groups = r.re->prog.num_groups;
+    if (groups <= 0 || col->rows == 0) return;
     if (groups > kMaxGroups) fail(CS_ERR_RANGE, "extract: more than 32 capture groups");
-    upload(re, s);
-    const int ninst = (int)re->prog.insts.size();
-    Launch L{};
-    L.image = ptr<const int32_t>(re->d_image);
-    L.image_words = (int)re->image.size();
-    L.slots = csvm::gvm_slots(ninst);
-    const size_t img_bytes = (((size_t)L.image_words + 3) & ~size_t(3)) * 4;
-    L.image_in_lds = img_bytes <= kLdsBudget / 2;
-    const unsigned grid = (unsigned)std::min<int64_t>((rows + 255) / 256, 256 * 4);
-    const bool dfa_groups = use_tdfa(re) && re->d_gtags && !cs::cfg("CS_EXTRACT_LISTS");
-    Buf arena;  // thread lists of the list simulation (not needed when the DFA carries the group ranges)
-    if (!dfa_groups) {
-      arena = dev_alloc((size_t)grid * 256 * L.slots * 4, s);
-      L.arena = ptr<uint32_t>(arena);
-    }
-    RowSrc src{view_of(col), d_unicode_flags(), col->nbytes + (col->chars && col->chars->capacity ? 64 : 0)};
-    Buf begins, lens, spans, tile_tot;  // (begins / lens, or packed spans + tile totals from the scan stream kernel on 64-row tiles)
-    const bool tdfa = use_tdfa(re);
-    bool streamed = false, packed = false;
-    if (dfa_groups && !cs::cfg("CS_REGEX_ROWWISE")) {  // rows staged through LDS tiles by the scan stream kernel
-      TPlan tp = tplan(re, rows, s);
-      const TileChoice tc = choose_tile(col, s);
-      const int cap = tc.cap;
-      const size_t gt_bytes = re->gtags.size() * 4 <= 16 * 1024 ? ((re->gtags.size() * 4 + 15) & ~size_t(15)) : 0;
-      // (a chain pattern whose groups are runs of items, on a column whose sample is plain ASCII: the chain form -- the match
-      // and the group ranges by mask arithmetic; it keeps the "equals x" bitmap and the unit form's layout)
-      const bool chain_form = tp.d.in_lds && tc.R == 64 && !tc.lng && !cs::cfg("CS_SPANS_UNPACKED") && ((re->tdfa[30] >> 16) & 15) != 0 && ((re->tdfa[30] >> 20) & 1) != 0 &&
-                              groups <= 4 && !cs::cfg("CS_NO_CHAIN_FORM") && !sample_has_high_bytes(col, s);
-      // (the chain form with the tables in memory: a fourth workgroup per CU -- the kernel is built for 128 registers then)
-      const bool chain_mem = chain_form && !cs::cfg("CS_CHAIN_TABLES_IN_LDS");
-      const size_t tbl_x = chain_mem ? (size_t)cstd::kHeadTailWords * 4 : tp.lds_bytes;
-      const size_t lds = chain_form ? tbl_x + gt_bytes + (size_t)(cap + 32 + 2 * ((cap >> 3) + 32) + kUnitQueue * 4 + 64 * 4 + 16) * 4
-                                    : tp.lds_bytes + gt_bytes + (size_t)(cap + 32 + (cap >> 3) + 32 + cstd::Tdfa::kBackSteps * 64 + kMaxGroups * 4) * 4;
-      if (tp.d.in_lds && tc.R && lds <= 150 * 1024) {
-        packed = tc.R == 64 && !cs::cfg("CS_SPANS_UNPACKED");
-        if (packed) {
-          spans = dev_alloc(sizeof(uint32_t) * rows * groups, s);
-          tile_tot = dev_alloc(sizeof(int32_t) * ((rows + 63) / 64) * groups, s);
-        } else {
-          begins = dev_alloc(sizeof(int32_t) * rows * groups, s);
-          lens = dev_alloc(sizeof(int32_t) * rows * groups, s);
-        }
-        Buf cnt = dev_alloc(8, s);
-        CS_HIP(hipMemsetAsync(cnt->p, 0, 8, s));
-        ScanStreamArgs sa{};
-        sa.in = view_of(col);
-        sa.flags = d_unicode_flags();
-        sa.L = tp.d;
-        sa.found = ptr<unsigned long long>(cnt);
-        sa.nsub = (rows + tc.R - 1) / tc.R;
-        sa.rows_per_tile = tc.R;
-        sa.cap_in = cap;
-        sa.tbl_bytes = (int)(tbl_x + gt_bytes);
-        sa.gt_off = (int)tbl_x;
-        if (chain_mem) sa.L.in_lds = 2;
-        sa.gt_words = gt_bytes ? (int)re->gtags.size() : 0;
-        sa.begins = ptr<int32_t>(begins);
-        sa.lens = ptr<int32_t>(lens);
-        sa.spans = ptr<uint32_t>(spans);
-        sa.tile_tot = ptr<int32_t>(tile_tot);
-        sa.ncols = groups;
-        sa.gtags = ptr<const int32_t>(re->d_gtags);
-        auto kern = tc.lng ? &k_tdfa_scan_stream<4, true, true> : &k_tdfa_scan_stream<4, true, false>;
-        if (chain_form) kern = chain_mem ? &k_tdfa_scan_stream<4, false, false, true, true> : &k_tdfa_scan_stream<4, true, false, true, true>;
-        ProfScope ps("k_extract_spans", s);
-        launch_resident(kern, lds, (sa.nsub + 3) / 4, s, sa);
-        streamed = true;
-      }
-    }
-    if (!streamed) {
-      begins = dev_alloc(sizeof(int32_t) * rows * groups, s);
-      lens = dev_alloc(sizeof(int32_t) * rows * groups, s);
-    }
-    if (streamed) {
-    } else if (dfa_groups) {
-      TPlan tp = tplan(re, rows, s);
-      ProfScope ps("k_extract_spans", s);
-      if (tp.d.in_lds)
-        hipLaunchKernelGGL(k_extract_spans_dfa<true>, dim3(tp.grid), dim3(256), tp.lds_bytes, s, src, tp.d, ptr<const int32_t>(re->d_gtags),
-                           groups, ptr<int32_t>(begins), ptr<int32_t>(lens));
-      else
-        hipLaunchKernelGGL(k_extract_spans_dfa<false>, dim3(tp.grid), dim3(256), 0, s, src, tp.d, ptr<const int32_t>(re->d_gtags), groups,
-                           ptr<int32_t>(begins), ptr<int32_t>(lens));
-    } else if (tdfa) {
-      TPlan tp = tplan(re, rows, s);
-      size_t fast_bytes = (size_t)256 * csvm::GroupVm<true>::kFastSlots * 4;
-      const int use_fast = tp.lds_bytes + fast_bytes <= kLdsBudget;
-      if (!use_fast) fast_bytes = 0;
-      L.image_in_lds = tp.lds_bytes + fast_bytes + img_bytes <= kLdsBudget;
-      const size_t lds = tp.lds_bytes + fast_bytes + (L.image_in_lds ? img_bytes : 0);
-      ProfScope ps("k_extract_spans", s);
-      if (tp.d.in_lds && ninst <= 64)
-        hipLaunchKernelGGL((k_extract_spans_tdfa<true, true>), dim3(grid), dim3(256), lds, s, src, tp.d, L, groups, use_fast,
-                           ptr<int32_t>(begins), ptr<int32_t>(lens));
-      else if (tp.d.in_lds)
-        hipLaunchKernelGGL((k_extract_spans_tdfa<true, false>), dim3(grid), dim3(256), lds, s, src, tp.d, L, groups, use_fast,
-                           ptr<int32_t>(begins), ptr<int32_t>(lens));
-      else if (ninst <= 64)
-        hipLaunchKernelGGL((k_extract_spans_tdfa<false, true>), dim3(grid), dim3(256), lds, s, src, tp.d, L, groups, use_fast,
-                           ptr<int32_t>(begins), ptr<int32_t>(lens));
-      else
-        hipLaunchKernelGGL((k_extract_spans_tdfa<false, false>), dim3(grid), dim3(256), lds, s, src, tp.d, L, groups, use_fast,
-                           ptr<int32_t>(begins), ptr<int32_t>(lens));
-    } else {
-      ProfScope ps("k_extract_spans", s);
-      if (ninst <= 64)
-        hipLaunchKernelGGL((k_extract_spans<true>), dim3(grid), dim3(256), L.image_in_lds ? img_bytes : 0, s, src, L, groups,
-                           ptr<int32_t>(begins), ptr<int32_t>(lens));
-      else
-        hipLaunchKernelGGL((k_extract_spans<false>), dim3(grid), dim3(256), L.image_in_lds ? img_bytes : 0, s, src, L, groups,
-                           ptr<int32_t>(begins), ptr<int32_t>(lens));
-    }
+    upload(r.re, r.s);
+    const bool dfa_groups = use_tdfa(r.re) && r.re->d_gtags && !cs::cfg("CS_EXTRACT_LISTS");
+    Buf arena;  // (extract_rowwise)
+    SpanBufs sp;
+    if (!(dfa_groups && !cs::cfg("CS_REGEX_ROWWISE") && extract_stream(r, groups, sp))) extract_rowwise(r, groups, dfa_groups, arena, sp);
     CS_HIP(hipGetLastError());
     std::vector<std::unique_ptr<cs_column>> cols;
-    if (packed) {
-      columns_from_packed_spans(col, groups, ptr<const uint32_t>(spans), ptr<const int32_t>(tile_tot), choose_tile(col, s).cap, s, cols);
-      release_columns(cols, out_cols, ncols_out);
-      return;
-    }
-    ExtractOut eo{};
-    for (int g = 0; g < groups; ++g) {
-      Built b(rows, Nulls::fused, s);
-      b.scan(ptr<int32_t>(lens) + (size_t)g * rows);
-      eo.off[g] = b.off;
-      eo.chars[g] = b.alloc_chars();
-      cols.push_back(std::move(b.col));
-    }
-    write_spans(col, groups, ptr<int32_t>(begins), ptr<int32_t>(lens), eo, s);
-    CS_HIP(hipGetLastError());
-    CS_HIP(hipStreamSynchronize(s));  // arena / span buffers
+    columns_from(col, groups, sp, r.s, cols);
     release_columns(cols, out_cols, ncols_out);
   });
 }
@@ -4293,150 +4644,26 @@ int cs_findall(const cs_column* col, const cs_regex* cre, cs_stream stream, cs_c
   return guard([&] {
     if (!col || !cre || !out_cols || !ncols_out) fail(CS_ERR_INVALID_ARG, "null argument");
     require_device();
-    hipStream_t s = S(stream);
-    cs_regex* re = const_cast<cs_regex*>(cre);
+    SpanRun r{col, const_cast<cs_regex*>(cre), S(stream)};
     *out_cols = nullptr;
     *ncols_out = 0;
-    const int64_t rows = col->rows;
-    if (rows == 0) return;
-    auto finish = [&](std::vector<std::unique_ptr<cs_column>>& cols) { release_columns(cols, out_cols, ncols_out); };
+    if (col->rows == 0) return;
     std::vector<std::unique_ptr<cs_column>> cols;
-    Buf dmax = dev_alloc(8, s);
-    int* hmax = (int*)pinned_scratch(8);
-    auto read_max = [&]() {
-      CS_HIP(hipMemcpyAsync(hmax, dmax->p, 4, hipMemcpyDeviceToHost, s));
-      CS_HIP(hipStreamSynchronize(s));
-      return hmax[0];
-    };
-    RowSrc src{view_of(col), d_unicode_flags(), col->nbytes + (col->chars && col->chars->capacity ? 64 : 0)};
-    Buf begins, lens, spans, tile_tot;
-    Plan pl{};
-    int ncols = -1;  // unknown
-    bool streamed = false, packed = false;
-    int packed_cap = 0;
-    // The scan stream kernel reports spans and the largest match count in ONE pass when the rows hold at most
-    // kProvisional matches (the span arrays are laid out [k * rows + row], so unused columns cost only memory);
-    // a column with busier rows is scanned a second time with the exact column count.
-    constexpr int kProvisional = 4;
-    if (use_tdfa(re) && !cs::cfg("CS_REGEX_ROWWISE")) {
-      TPlan tp = tplan(re, rows, s);
-      const TileChoice tc = choose_tile(col, s);
-      const int cap = tc.cap;
-      // the unit scan where the tagged DFA offers the decomposition (as count_re)
-      const bool units = ((re->tdfa[31] & 1) != 0 || ((re->tdfa[30] >> 16) & 15) != 0) && !tc.lng && tc.R == 64 && !cs::cfg("CS_NO_UNITS");
-      size_t lds = tp.lds_bytes + (size_t)(cap + 32 + (cap >> 3) + 32 + (units ? (cap >> 3) + 32 + kUnitQueue * 4 + 64 * 4 + 16 : 0)) * 4;
-      const bool chain_scan = units && ((re->tdfa[30] >> 16) & 15) != 0 && !sample_has_high_bytes(col, s) && !cs::cfg("CS_NO_CHAIN_FORM");
-      const bool chain_global = chain_scan && tp.d.in_lds && lds > 40 * 1024 && lds - tp.lds_bytes + cstd::kHeadTailWords * 4 <= 40 * 1024 && !cs::cfg("CS_CHAIN_TABLES_IN_LDS");  // (as in count_re)
-      const size_t scan_tbl = chain_global ? (size_t)cstd::kHeadTailWords * 4 : tp.lds_bytes;
-      if (chain_global) lds -= tp.lds_bytes - scan_tbl;
-      if (tp.d.in_lds && tc.R && lds <= 150 * 1024) {
-        Buf hits = dev_alloc(8, s);
-        CS_HIP(hipMemsetAsync(hits->p, 0, 8, s));
-        ScanStreamArgs sa{};
-        sa.in = view_of(col);
-        sa.flags = d_unicode_flags();
-        sa.L = tp.d;
-        sa.found = ptr<unsigned long long>(hits);  // (hit counter: not used here)
-        sa.nsub = (rows + tc.R - 1) / tc.R;
-        sa.rows_per_tile = tc.R;
-        sa.cap_in = cap;
-        sa.tbl_bytes = (int)scan_tbl;
-        if (chain_global) sa.L.in_lds = 2;
-        sa.maxp = ptr<int>(dmax);
-        auto kern = tc.lng ? &k_tdfa_scan_stream<3, true, true> : &k_tdfa_scan_stream<3, true, false>;
-        if (units) kern = &k_tdfa_scan_stream<3, true, false, true>;
-        if (chain_scan) kern = &k_tdfa_scan_stream<3, true, false, true, true>;  // (a chain pattern on a column whose sample is plain ASCII)
-        if (chain_global) kern = &k_tdfa_scan_stream<3, false, false, true, true>;
-        int width = kProvisional;
-        for (int pass = 0; pass < 2; ++pass) {
-          // (the provisional pass on 64-row tiles leaves packed spans and tile totals: k_spans_write_tile2 needs no pass
-          // over the lengths; a second pass -- rows with more than kProvisional matches -- writes begins / lens)
-          packed = tc.R == 64 && width <= kMaxGroups && (pass == 0 || !cs::cfg("CS_SPANS_EXACT_UNPACKED")) && !cs::cfg("CS_SPANS_UNPACKED");
-          if (packed) {
-            spans = dev_alloc(sizeof(uint32_t) * rows * width, s);
-            tile_tot = dev_alloc(sizeof(int32_t) * ((rows + 63) / 64) * width, s);
-          } else {
-            begins = dev_alloc(sizeof(int32_t) * rows * width, s);
-            lens = dev_alloc(sizeof(int32_t) * rows * width, s);
-          }
-          CS_HIP(hipMemsetAsync(dmax->p, 0, 8, s));
-          sa.begins = packed ? nullptr : ptr<int32_t>(begins);
-          sa.lens = packed ? nullptr : ptr<int32_t>(lens);
-          sa.spans = packed ? ptr<uint32_t>(spans) : nullptr;
-          sa.tile_tot = packed ? ptr<int32_t>(tile_tot) : nullptr;
-          sa.ncols = width;
-          {
-            ProfScope ps("k_findall_spans", s);
-            launch_resident(kern, lds, (sa.nsub + 3) / 4, s, sa);
-          }
-          ncols = read_max();
-          if (ncols <= width) break;
-          width = ncols;  // busier rows than provisioned for: once more, exactly
-        }
-        streamed = true;
-        packed_cap = cap;
-      }
-    }
-    if (!streamed) {
-      // matches per row (the count_re kernels), their maximum = number of columns
-      Buf counts = dev_alloc(sizeof(int32_t) * rows, s);
-      scan<2>(ScanCall{col, re, counts->p, sizeof(int32_t), 1, s, nullptr, "k_count_re"});
-      CS_HIP(hipMemsetAsync(dmax->p, 0, 8, s));
-      hipLaunchKernelGGL(k_max_i32, dim3((unsigned)std::min<int64_t>((rows + 255) / 256, 2048)), dim3(256), 0, s, ptr<int32_t>(counts), rows,
-                         ptr<int>(dmax));
-      ncols = read_max();
-    }
+    Buf dmax = dev_alloc(8, r.s);  // (read_max)
+    SpanBufs sp;
+    Plan pl{};  // (findall_rowwise)
+    int ncols = use_tdfa(r.re) && !cs::cfg("CS_REGEX_ROWWISE") ? findall_stream(r, dmax, sp) : -1;
+    const bool streamed = ncols >= 0;
+    if (!streamed) ncols = findall_count_rows(r, dmax);
     if (ncols == 0) {  // findall.cu:149-151
-      cols.emplace_back(make_all_null(rows, s));
-      finish(cols);
+      cols.emplace_back(make_all_null(col->rows, r.s));
+      release_columns(cols, out_cols, ncols_out);
       return;
     }
-    if (streamed && packed) {
-      columns_from_packed_spans(col, ncols, ptr<const uint32_t>(spans), ptr<const int32_t>(tile_tot), packed_cap, s, cols);
-      finish(cols);
-      return;
-    }
-    if (!streamed) {
-      begins = dev_alloc(sizeof(int32_t) * rows * ncols, s);
-      lens = dev_alloc(sizeof(int32_t) * rows * ncols, s);
-    }
-    if (!streamed) {
-      ProfScope ps("k_findall_spans", s);
-      if (use_tdfa(re)) {
-        TPlan tp = tplan(re, rows, s);
-        if (tp.d.in_lds)
-          hipLaunchKernelGGL(k_findall_spans_tdfa<true>, dim3(tp.grid), dim3(256), tp.lds_bytes, s, src, tp.d, ncols, ptr<int32_t>(begins),
-                             ptr<int32_t>(lens));
-        else
-          hipLaunchKernelGGL(k_findall_spans_tdfa<false>, dim3(tp.grid), dim3(256), 0, s, src, tp.d, ncols, ptr<int32_t>(begins),
-                             ptr<int32_t>(lens));
-      } else {
-        pl = plan(re, rows, s);
-        if (pl.small)
-          hipLaunchKernelGGL((k_findall_spans<true>), dim3(pl.grid), dim3(pl.threads), pl.lds_bytes, s, src, pl.d, ncols,
-                             ptr<int32_t>(begins), ptr<int32_t>(lens));
-        else
-          hipLaunchKernelGGL((k_findall_spans<false>), dim3(pl.grid), dim3(pl.threads), pl.lds_bytes, s, src, pl.d, ncols,
-                             ptr<int32_t>(begins), ptr<int32_t>(lens));
-      }
-    }
+    if (!streamed) pl = findall_rowwise(r, ncols, sp);
     CS_HIP(hipGetLastError());
-    // columns, kMaxGroups at a time through the shared write kernel
-    for (int k0 = 0; k0 < ncols; k0 += kMaxGroups) {
-      const int nk = std::min(kMaxGroups, ncols - k0);
-      ExtractOut eo{};
-      for (int k = 0; k < nk; ++k) {
-        Built b(rows, Nulls::fused, s);
-        b.scan(ptr<int32_t>(lens) + (size_t)(k0 + k) * rows);
-        eo.off[k] = b.off;
-        eo.chars[k] = b.alloc_chars();
-        cols.push_back(std::move(b.col));
-      }
-      write_spans(col, nk, ptr<int32_t>(begins) + (size_t)k0 * rows, ptr<int32_t>(lens) + (size_t)k0 * rows, eo, s);
-    }
-    CS_HIP(hipGetLastError());
-    CS_HIP(hipStreamSynchronize(s));
-    finish(cols);
+    columns_from(col, ncols, sp, r.s, cols);
+    release_columns(cols, out_cols, ncols_out);
   });
 }
 
@@ -4450,152 +4677,21 @@ int cs_replace_with_backrefs(const cs_column* col, const cs_regex* cre, const ch
     hipStream_t s = S(stream);
     cs_regex* re = const_cast<cs_regex*>(cre);
     if (re->empty_pattern) fail(CS_ERR_INVALID_ARG, "nvstrings::replace_with_backrefs parameter cannot be null or empty");
-    const int64_t rows = col->rows;
-    if (rows == 0 || !repl) {
-      *out = make_all_null(rows, s);
+    if (col->rows == 0 || !repl) {
+      *out = make_all_null(col->rows, s);
       return;
     }
-    // backref.h:31-57: a backslash followed by digits is a reference
-    std::string text;
-    csvm::BackrefTemplate t{};
-    for (const char* p = repl; *p;) {
-      if (*p == '\\' && p[1] >= '0' && p[1] <= '9') {
-        const char* q = p + 1;
-        while (*q >= '0' && *q <= '9') ++q;
-        if (t.nrefs == csvm::BackrefTemplate::kMaxRefs) fail(CS_ERR_RANGE, "replace_with_backrefs: more than 16 references in the template");
-        t.idx[t.nrefs] = atoi(p + 1);
-        t.pos[t.nrefs] = (int)text.size();
-        ++t.nrefs;
-        p = q;
-      } else {
-        text.push_back(*p++);
-      }
-    }
-    t.bytes = (int)text.size();
-    t.groups = re->prog.num_groups;
+    BackrefTemplateText tt = parse_backref_template(repl, re);
     upload(re, s);
     const bool dfa = use_tdfa(re) && (re->d_gtags || re->prog.num_groups == 0);
     if (csrx::min_match_chars(re->prog) == 0) fail(CS_ERR_INVALID_ARG, "replace_with_backrefs: the pattern matches the empty string");
-    Buf d_text = dev_alloc(text.size() + 1, s);
-    CS_HIP(hipMemcpyAsync(d_text->p, text.c_str(), text.size() + 1, hipMemcpyHostToDevice, s));
-    t.text = ptr<const uint8_t>(d_text);
-    // First choice: the single-pass replace kernel in its backrefs form (unit scan, one group run per match, coalesced
-    // output).  It declines patterns without the unit decomposition, more than four groups, long rows; a launch that
-    // runs out of output room or meets a row the unit route hands over reports it, and the two-pass form below runs.
-    bool packs = t.bytes <= 255;  // (the kernel keeps the references' group numbers and positions packed in registers)
-    for (int j = 0; j < t.nrefs; ++j) packs = packs && t.idx[j] <= 15 && t.pos[j] <= 255;
-    if (dfa && packs && re->prog.num_groups >= 1 && !cs::cfg("CS_BACKREFS_TWO_PASS")) {
-      Buf d_t = dev_alloc(sizeof(csvm::BackrefTemplate), s);
-      CS_HIP(hipMemcpyAsync(d_t->p, &t, sizeof(t), hipMemcpyHostToDevice, s));
-      CS_HIP(hipStreamSynchronize(s));  // (`t` lives on this stack frame)
-      cs::ReplaceCall call{col, re, "", 0, -1, s};
-      call.tmpl_host = &t;
-      call.tmpl_dev = d_t->p;
-      call.tmpl_text_bytes = t.bytes;
-      call.single_pass_only = true;
-      // (whatever fails in there -- declined, out of room, a HIP error --, the two-pass form below answers)
-      if (guard([&] { *out = cs::replace_re_column(call); }) == CS_OK) return;
-    }
-    BackrefArgs a{};
-    a.src = RowSrc{view_of(col), d_unicode_flags(), col->nbytes + (col->chars && col->chars->capacity ? 64 : 0)};
-    a.gtags = ptr<const int32_t>(re->d_gtags);
-    a.t = t;
-    const int ninst = (int)re->prog.insts.size();
-    unsigned grid = (unsigned)std::min<int64_t>((rows + 255) / 256, 256 * 8);
-    size_t lds = 0;
-    Buf arena;
-    if (dfa) {
-      TPlan tp = tplan(re, rows, s);
-      a.TL = tp.d;
-      lds = tp.lds_bytes;
-    } else {
-      a.L.image = ptr<const int32_t>(re->d_image);
-      a.L.image_words = (int)re->image.size();
-      a.L.slots = csvm::gvm_slots(ninst);
-      grid = std::min(grid, 1024u);
-      arena = dev_alloc((size_t)grid * 256 * a.L.slots * 4, s);
-      a.L.arena = ptr<uint32_t>(arena);
-    }
-    auto launch = [&](bool write, int32_t* lens, const int64_t* off, uint8_t* chars) {
-      const bool small = ninst <= 64;
-#define CS_BR(D_, I_, S_)                                                                                        \
-  do {                                                                                                           \
-    if (write) hipLaunchKernelGGL((k_backrefs<D_, I_, S_, true>), dim3(grid), dim3(256), lds, s, a, lens, off, chars);  \
-    else hipLaunchKernelGGL((k_backrefs<D_, I_, S_, false>), dim3(grid), dim3(256), lds, s, a, lens, off, chars);       \
-  } while (0)
-      if (dfa && a.TL.in_lds) CS_BR(true, true, true);
-      else if (dfa) CS_BR(true, false, true);
-      else if (small) CS_BR(false, false, true);
-      else CS_BR(false, false, false);
-#undef CS_BR
-      CS_HIP(hipGetLastError());
-    };
-    // rows staged through LDS tiles by the scan stream kernel when the DFA carries the groups and the tiles fit
-    ScanStreamArgs sa{};
-    Buf d_tmpl;
-    size_t slds = 0;
-    bool lng = false, stream = false;
-    if (dfa && a.TL.in_lds && !cs::cfg("CS_REGEX_ROWWISE")) {
-      const TileChoice tc = choose_tile(col, s);
-      const size_t gt_bytes = (!re->gtags.empty() && re->gtags.size() * 4 <= 16 * 1024) ? ((re->gtags.size() * 4 + 15) & ~size_t(15)) : 0;
-      slds = lds + gt_bytes + (size_t)(tc.cap + 32 + (tc.cap >> 3) + 32) * 4;
-      if (tc.R && slds <= 150 * 1024) {
-        sa.gt_off = (int)lds;
-        sa.gt_words = gt_bytes ? (int)re->gtags.size() : 0;
-        stream = true;
-        lng = tc.lng;
-        sa.in = view_of(col);
-        sa.flags = d_unicode_flags();
-        sa.L = a.TL;
-        sa.nsub = (rows + tc.R - 1) / tc.R;
-        sa.rows_per_tile = tc.R;
-        sa.cap_in = tc.cap;
-        sa.tbl_bytes = (int)(lds + gt_bytes);
-        sa.gtags = a.gtags;
-        d_tmpl = dev_alloc(sizeof(csvm::BackrefTemplate), s);
-        CS_HIP(hipMemcpyAsync(d_tmpl->p, &t, sizeof(t), hipMemcpyHostToDevice, s));
-        sa.tmpl = ptr<const csvm::BackrefTemplate>(d_tmpl);
-      }
-    }
-    Buf scnt;
-    auto launch_stream = [&](bool write) {
-      if (!scnt) {
-        scnt = dev_alloc(8, s);
-        CS_HIP(hipMemsetAsync(scnt->p, 0, 8, s));
-        sa.found = ptr<unsigned long long>(scnt);
-      }
-      auto kern = write ? (lng ? &k_tdfa_scan_stream<6, true, true> : &k_tdfa_scan_stream<6, true, false>)
-                        : (lng ? &k_tdfa_scan_stream<5, true, true> : &k_tdfa_scan_stream<5, true, false>);
-      launch_resident(kern, slds, (sa.nsub + 3) / 4, s, sa);
-    };
-    Built b(col, s);
-    Buf lens = dev_alloc(sizeof(int32_t) * rows, s);
-    {
-      ProfScope ps("k_backrefs_size", s);
-      if (stream) {
-        sa.out32 = ptr<int32_t>(lens);
-        launch_stream(false);
-      } else {
-        launch(false, ptr<int32_t>(lens), nullptr, nullptr);
-      }
-    }
-    b.scan(ptr<int32_t>(lens));
-    b.alloc_chars();
-    {
-      ProfScope ps("k_backrefs_write", s);
-      if (stream) {
-        sa.out_off = b.off;
-        sa.out_chars = b.chars;
-        launch_stream(true);
-      } else {
-        launch(true, nullptr, b.off, b.chars);
-      }
-    }
-    CS_HIP(hipStreamSynchronize(s));
-    *out = b.col.release();
+    Buf d_text = dev_alloc(tt.text.size() + 1, s);
+    CS_HIP(hipMemcpyAsync(d_text->p, tt.text.c_str(), tt.text.size() + 1, hipMemcpyHostToDevice, s));
+    tt.t.text = ptr<const uint8_t>(d_text);
+    if (backrefs_single_pass(col, re, tt.t, dfa, s, out)) return;
+    *out = backrefs_two_pass(col, re, tt.t, dfa, s);
   });
 }
-
 
 // NVStrings::replace_re(patterns, repls) (NVStrings.h:777; replace_multi.cu:110-189)
 int cs_replace_re_multi(const cs_column* col, const cs_regex* const* res, int npatterns, const cs_column* repls, cs_stream stream,

@@ -1,9 +1,10 @@
-"""The launches of the replace route, of the scan route or of the split route, case by case (dev tool): which kernels a
-call starts, on what grid and with how much dynamic LDS, for every case of tests/test_gpu_replace_forms.py (`run
-replace`: plus bench.py's pattern on a 1M-row generated column), of tests/test_gpu_scan_forms.py (`run scan`: plus
-contains_re and count_re of that pattern on the same column) or of tests/test_gpu_split_forms.py (`run split`: plus
-split(' ') on that column; the single pass's cases where the library has the experiments).  Two builds whose listings
-agree start the same kernels.
+"""The launches of the replace route, of the scan route, of the split route or of the span routes, case by case (dev
+tool): which kernels a call starts, on what grid and with how much dynamic LDS, for every case of
+tests/test_gpu_replace_forms.py (`run replace`: plus bench.py's pattern on a 1M-row generated column), of
+tests/test_gpu_scan_forms.py (`run scan`: plus contains_re and count_re of that pattern on the same column), of
+tests/test_gpu_split_forms.py (`run split`: plus split(' ') on that column; the single pass's cases where the library
+has the experiments) or of tests/test_gpu_span_forms.py (`run spans`: plus findall, extract and replace_with_backrefs
+with tools/bench_ops.py's patterns on that column).  Two builds whose listings agree start the same kernels.
 
     rocprofv3 --kernel-trace --output-format json -d DIR -- python tools/replace_launches.py run scan 2> DIR/stream_info.txt
     python tools/replace_launches.py list DIR > listing.txt
@@ -86,6 +87,17 @@ def run(table):
         bench = gpuutil.synth(3, 0, 1_000_000)
         for i in range(2):  # (the second call finds the column's metadata cached)
             call("bench-1M-%d" % i, (), lambda: bench.split(" "))
+    elif table == "spans":
+        import test_gpu_scan_forms as scans
+        import test_gpu_span_forms as spans
+
+        for name, op, pat, tmpl, kind, n, switches in spans.CASES:
+            call(name, switches, lambda: spans.run(scans._col(kind, n)[1], op, pat, tmpl))
+        bench = gpuutil.synth(3, 0, 1_000_000)
+        # (tools/bench_ops.py's patterns)
+        for op, pat, tmpl in ((spans.FINDALL, forms.IPV4, None), (spans.EXTRACT, r"(\d+)\.(\d+)\.\d+\.(\d+) ", None), (spans.BREFS, r"(\d+)\.(\d+)\.(\d+)\.(\d+)", r"\4.\3.\2.\1")):
+            for i in range(2):
+                call("bench-1M-%s-%d" % (op, i), (), lambda: spans.run(bench, op, pat, tmpl))
     else:
         import test_gpu_scan_forms as scans
 
@@ -156,7 +168,7 @@ def listing(d, force_csv=False):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) >= 2 and sys.argv[1] == "run" and sys.argv[2:] in ([], ["replace"], ["scan"], ["split"]):
+    if len(sys.argv) >= 2 and sys.argv[1] == "run" and sys.argv[2:] in ([], ["replace"], ["scan"], ["split"], ["spans"]):
         run(sys.argv[2] if sys.argv[2:] else "replace")
     elif len(sys.argv) >= 3 and sys.argv[1] == "list":
         listing(sys.argv[2], force_csv=sys.argv[3:] == ["csv"])
