@@ -170,6 +170,8 @@ _PROTOS = {
     "cs_islower": (i32, [vp, vp, i32, vp, P(i64)]),
     "cs_isupper": (i32, [vp, vp, i32, vp, P(i64)]),
     "cs_is_empty": (i32, [vp, vp, i32, vp, P(i64)]),
+    "cs_column_statistics": (i32, [vp, i32, vp, vp, i64, P(i64), i32, vp]),
+    "cs_stats_lds_bins": (i32, []),
     "cs_swapcase": (i32, [vp, vp, P(vp)]),
     "cs_capitalize": (i32, [vp, vp, P(vp)]),
     "cs_title": (i32, [vp, vp, P(vp)]),

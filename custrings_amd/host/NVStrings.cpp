@@ -2,6 +2,7 @@
 // over the C ABI of libcustrings_amd.so.  Host C++ only: every member is argument checking, one or two
 // C-ABI calls and the reference's exception / return-value conventions (cited per member).
 #include "nvstrings/NVStrings.h"
+#include "nvstrings/StringsStatistics.h"
 #include "nvstrings/ipc_transfer.h"
 
 #include <cstdlib>
@@ -168,6 +169,41 @@ size_t NVStrings::byte_count(int* lengths, bool devmem) {
   int64_t total = 0;
   check(cs_column_byte_count(m_col, lengths, devmem ? 1 : 0, nullptr, &total));
   return (size_t)total;
+}
+
+// every field is assigned (the struct holds a vector: no memset); the buffer has room for every code point 1 .. 0xFFFF,
+// the library copies only the pairs that occur
+void NVStrings::compute_statistics(StringsStatistics& stats) {
+  cs_statistics st;
+  const int64_t cap = 0xFFFF;
+  std::vector<uint32_t> pairs(2 * (size_t)cap);
+  int64_t npairs = 0;
+  check(cs_column_statistics(m_col, CS_STATS_ALL, &st, pairs.data(), cap, &npairs, 0, nullptr));
+  stats.total_bytes = st.total_bytes;
+  stats.total_chars = st.total_chars;
+  stats.bytes_avg = st.bytes_avg;
+  stats.bytes_max = st.bytes_max;
+  stats.bytes_min = st.bytes_min;
+  stats.bytes_95 = st.bytes_95;
+  stats.chars_avg = st.chars_avg;
+  stats.chars_max = st.chars_max;
+  stats.chars_min = st.chars_min;
+  stats.chars_95 = st.chars_95;
+  stats.total_memory = st.total_memory;
+  stats.mem_avg = st.mem_avg;
+  stats.mem_max = st.mem_max;
+  stats.mem_min = st.mem_min;
+  stats.mem_95 = st.mem_95;
+  stats.total_strings = st.total_strings;
+  stats.total_nulls = st.total_nulls;
+  stats.total_empty = st.total_empty;
+  stats.unique_strings = st.unique_strings;
+  stats.whitespace_count = st.whitespace_count;
+  stats.digits_count = st.digits_count;
+  stats.uppercase_count = st.uppercase_count;
+  stats.lowercase_count = st.lowercase_count;
+  stats.char_counts.clear();
+  for (int64_t i = 0; i < npairs; ++i) stats.char_counts.emplace_back(pairs[2 * (size_t)i], pairs[2 * (size_t)i + 1]);
 }
 
 // ---- re-arrangement ----------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 // pyniNVStrings -- CPython glue of the nvstrings Python class (python/cpp/pystrings.cpp in the reference,
 // method table :3860-3973) for the members SURVEY.md section 8 names, over libNVStrings.so.
 #include "pyni_common.h"
+#include "nvstrings/StringsStatistics.h"
 #include "nvstrings/ipc_transfer.h"
 #include <cstring>
 #include <memory>
@@ -532,6 +533,58 @@ static PyObject* n_join(PyObject*, PyObject* args) {
   return make_instance([&] { return s->join(sep ? sep : ""); });
 }
 static PyObject* n_device_memory(PyObject*, PyObject* args) { return PyLong_FromLong((long)SELF(args)->memsize()); }
+// pystrings.cpp:3780-3832: (self) -> the dict of NVStrings::compute_statistics; chars_histogram maps a one-character str to its
+// count (a pair whose bytes are no valid UTF-8 -- a lone surrogate -- has no str and is left out; the C++ vector keeps it)
+static PyObject* n_get_info(PyObject*, PyObject* args) {
+  NVStrings* s = SELF(args);
+  StringsStatistics st;
+  if (!guarded([&] { s->compute_statistics(st); })) return nullptr;
+  PyObject* d = PyDict_New();
+  auto put = [&](const char* key, size_t v) {
+    PyObject* o = PyLong_FromUnsignedLongLong((unsigned long long)v);
+    PyDict_SetItemString(d, key, o);
+    Py_DECREF(o);
+  };
+  put("total_strings", st.total_strings);
+  put("null_strings", st.total_nulls);
+  put("empty_strings", st.total_empty);
+  put("unique_strings", st.unique_strings);
+  put("total_bytes", st.total_bytes);
+  put("total_chars", st.total_chars);
+  put("device_memory", st.total_memory);
+  put("bytes_avg", st.bytes_avg);
+  put("bytes_min", st.bytes_min);
+  put("bytes_max", st.bytes_max);
+  put("chars_avg", st.chars_avg);
+  put("chars_min", st.chars_min);
+  put("chars_max", st.chars_max);
+  put("memory_avg", st.mem_avg);
+  put("memory_min", st.mem_min);
+  put("memory_max", st.mem_max);
+  put("whitespace", st.whitespace_count);
+  put("digits", st.digits_count);
+  put("uppercase", st.uppercase_count);
+  put("lowercase", st.lowercase_count);
+  PyObject* hist = PyDict_New();
+  for (const auto& pr : st.char_counts) {
+    char text[4];
+    int w = 0;
+    for (int shift = 24; shift >= 0; shift -= 8)
+      if (w || (pr.first >> shift) & 0xFF || shift == 0) text[w++] = (char)((pr.first >> shift) & 0xFF);
+    PyObject* key = PyUnicode_DecodeUTF8(text, w, "strict");
+    if (!key) {
+      PyErr_Clear();
+      continue;
+    }
+    PyObject* n = PyLong_FromUnsignedLong(pr.second);
+    PyDict_SetItem(hist, key, n);
+    Py_DECREF(key);
+    Py_DECREF(n);
+  }
+  PyDict_SetItemString(d, "chars_histogram", hist);
+  Py_DECREF(hist);
+  return d;
+}
 
 static PyObject* n_dropWrapper(PyObject*, PyObject* args) { return drop_wrapper<NVStrings>(args); }
 
@@ -977,7 +1030,7 @@ static PyMethodDef s_Methods[] = {
     M(n_rsplit_record), M(n_partition), M(n_rpartition), M(n_replace), M(n_replace_multi), M(n_replace_with_backrefs), M(n_lstrip), M(n_strip),
     M(n_rstrip), M(n_lower), M(n_upper), M(n_find), M(n_rfind), M(n_find_from), M(n_find_multiple), M(n_compare), M(n_match_strings), M(n_startswith), M(n_endswith), M(n_contains), M(n_match), M(n_count), M(n_findall), M(n_findall_record), M(n_extract),
     M(n_extract_record), M(n_sort), M(n_order), M(n_gather), M(n_sublist), M(n_scatter), M(n_scalar_scatter), M(n_remove_strings),
-    M(n_add_strings), M(n_cat), M(n_join), M(n_device_memory),
+    M(n_add_strings), M(n_cat), M(n_join), M(n_device_memory), M(n_get_info),
     M(n_hash), M(n_stoi), M(n_stol), M(n_stof), M(n_stod), M(n_htoi), M(n_ip2int), M(n_to_bools), M(n_createFromInt32s),
     M(n_createFromInt64s), M(n_createFromFloat32s), M(n_createFromFloat64s), M(n_createFromIPv4Integers), M(n_createFromBools),
     M(n_timestamp2int), M(n_createFromTimestamp),

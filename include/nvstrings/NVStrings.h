@@ -20,6 +20,7 @@
 
 struct cs_column;
 struct nvstrings_ipc_transfer; /* nvstrings/ipc_transfer.h */
+struct StringsStatistics;      /* nvstrings/StringsStatistics.h */
 
 class NVStrings {
   cs_column* m_col; /* (the reference holds an NVStringsImpl* here; one pointer either way) */
@@ -57,6 +58,9 @@ class NVStrings {
   int to_host(char** list, int start, int end);
   unsigned int len(int* lengths, bool devmem = true);
   size_t byte_count(int* lengths, bool devmem = true);
+  /* NVStrings.h:1203 -- every length, memory and class figure, the distinct count and the character histogram, from one
+   * read of the chars and one category build (cs_column_statistics, include/custrings_amd.h) */
+  void compute_statistics(StringsStatistics& stats);
 
   /* ---- re-arrangement (NVStrings.h:261-334; array.cu) ---- */
   NVStrings* sublist(unsigned int start, unsigned int end, int step = 0);

@@ -61,7 +61,7 @@ def report(config, op, rows, in_bytes, alg_bytes, dt):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scale", type=float, default=1.0, help="row-count multiplier (1.0 = BASELINE.json single-GPU sizes)")
-    ap.add_argument("--only", default="C2,C3,C4,C5", help="comma-separated configs to run (CONV: the conversion ops, TS: the timestamp ones, PAD: substring / padding / wrapping, CHR: character types and swapcase / capitalize / title, TXT: the NVText matches, edit distance, stemmer measure and scatter_count, URL: url_encode / url_decode / translate / fillna, NUM: the numeric categories -- from_numbers, to_numbers, merge_and_remap -- beside two yardsticks, CSV: from_csv -- the line-start kernels, the field locator and the whole call)")
+    ap.add_argument("--only", default="C2,C3,C4,C5", help="comma-separated configs to run (CONV: the conversion ops, TS: the timestamp ones, PAD: substring / padding / wrapping, CHR: character types and swapcase / capitalize / title, TXT: the NVText matches, edit distance, stemmer measure and scatter_count, URL: url_encode / url_decode / translate / fillna, NUM: the numeric categories -- from_numbers, to_numbers, merge_and_remap -- beside two yardsticks, CSV: from_csv -- the line-start kernels, the field locator and the whole call, STATS: compute_statistics / get_info -- the fused pass beside the separate ops, the histogram layouts, the whole call)")
     a = ap.parse_args()
     only = set(a.only.split(","))
     ov = 8.125  # native offset + validity bytes per row
@@ -90,6 +90,49 @@ def main():
         run_num(a)
     if "CSV" in only:
         run_csv(a)
+    if "STATS" in only:
+        run_stats(a)
+
+
+def run_stats(a):
+    """compute_statistics / get_info (cs_column_statistics) on the C2, C3 and C5 columns at 20M rows (x --scale): (a) the fused
+    pass for the length and class figures, (b) what gives the same figures without it -- len, byte_count and isspace /
+    isdigit / isupper / islower, summed -- (c) the pass with the histogram, in each layout of CS_STATS_HIST (1 per-workgroup
+    LDS bins, 2 per-wave bins, 3 per-workgroup bins behind the wave's leader-match step), and the whole call with the distinct
+    count.  Beside them the box's read-only stream rate (cs_box_rates) and each pass's share of it at one read of the column
+    (chars, offsets, validity)."""
+    rates = (C.c_double * 6)()
+    _lib.check(L.cs_box_rates(2048, 3, None, rates))
+    read_rate = rates[1] * 1e12
+    print(json.dumps({"config": "STATS box", "read_GBps": round(rates[1] * 1e3, 1)}), flush=True)
+    rows = int(20_000_000 * a.scale)
+    for kind, name in ((2, "C2"), (3, "C3"), (5, "C5")):
+        col = synth(kind, rows)
+        one_read = nbytes(col) + 8.125 * rows
+        res32 = torch.empty(rows, dtype=torch.int32, device="cuda")
+        res8 = torch.empty(rows, dtype=torch.uint8, device="cuda")
+
+        def line(op, fn, passes=1, reps=5):
+            dt = timed(fn, reps=reps)
+            print(json.dumps({"config": "STATS " + name, "op": op, "rows": rows, "ms": round(dt * 1e3, 3), "chars_reads": passes,
+                              "frac_of_box_read_rate_at_one_read": round(one_read / dt / read_rate, 4)}), flush=True)
+            return dt
+
+        fused = line("(a) fused pass: lengths + classes", lambda: nvstrings.column_statistics(col, 3))
+        route = L.cs_debug_last_route().decode()
+        today = [("len", lambda: col.len(res32.data_ptr())), ("byte_count", lambda: col.byte_count(res32.data_ptr(), True)),
+                 ("isspace", lambda: col.isspace(res8.data_ptr())), ("isdigit", lambda: col.isdigit(res8.data_ptr())),
+                 ("isupper", lambda: col.isupper(res8.data_ptr())), ("islower", lambda: col.islower(res8.data_ptr()))]
+        total = sum(line("(b) part: " + op, fn) for op, fn in today)
+        print(json.dumps({"config": "STATS " + name, "op": "(b) len + byte_count + isspace + isdigit + isupper + islower", "rows": rows,
+                          "ms": round(total * 1e3, 3), "fused_route": route, "fused_over_separate": round(fused / total, 3)}), flush=True)
+        for layout in (1, 2, 3):
+            L.cs_config_set(b"CS_STATS_HIST", str(layout).encode())
+            line("(c) fused pass + histogram, CS_STATS_HIST=%d" % layout, lambda: nvstrings.column_statistics(col, 7))
+            line("    histogram alone, CS_STATS_HIST=%d" % layout, lambda: nvstrings.column_statistics(col, 4))
+        L.cs_config_set(b"CS_STATS_HIST", None)
+        line("whole call: pass + histogram + distinct count (get_info)", lambda: col.get_info(), reps=2)
+        del col
 
 
 def run_c2(a, ov):
