@@ -228,6 +228,8 @@ _PROTOS = {
     "cs_tokenize": (i32, [vp, cp, vp, P(vp)]),
     "cs_tokenize_multi": (i32, [vp, vp, vp, P(vp)]),
     "cs_ngrams": (i32, [vp, C.c_uint, cp, vp, P(vp)]),
+    "cs_minhash": (i32, [vp, i32, C.c_uint32, vp, vp, i32, vp, i32, vp]),
+    "cs_minhash_bands": (i32, [vp, i64, i32, i32, vp, i32, vp]),
     "cs_synth_column": (i32, [i32, i64, i64, u64, i64, vp, P(vp)]),
     "cs_column_digest": (i32, [vp, vp, P(u64)]),
     "cs_prof_reset": (i32, []),

@@ -32,6 +32,8 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "minhash_ops.h"
+
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define CSCONV_HD __host__ __device__ __forceinline__
@@ -217,42 +219,8 @@ CSCONV_HD bool row_equals(const uint8_t* p, int n, const char* s, int m) {
   return true;
 }
 
-// ---- hash: MurmurHash3_x86_32, seed 31 (custring.inl:164-230) -------------------------------------------------------
-CSCONV_HD uint32_t rotl32(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
-CSCONV_HD uint32_t hash_row(const uint8_t* p, int n) {
-  const uint32_t c1 = 0xcc9e2d51u, c2 = 0x1b873593u;
-  uint32_t h = 31u;
-  const int nblocks = n / 4;
-  for (int i = 0; i < nblocks; ++i) {
-    const uint8_t* q = p + 4 * i;
-    uint32_t k = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24);
-    k *= c1;
-    k = rotl32(k, 15);
-    k *= c2;
-    h ^= k;
-    h = rotl32(h, 13);
-    h = h * 5u + 0xe6546b64u;
-  }
-  const uint8_t* t = p + 4 * nblocks;
-  uint32_t k = 0;
-  switch (n & 3) {
-    case 3: k ^= (uint32_t)t[2] << 16;  // fall through
-    case 2: k ^= (uint32_t)t[1] << 8;   // fall through
-    case 1:
-      k ^= t[0];
-      k *= c1;
-      k = rotl32(k, 15);
-      k *= c2;
-      h ^= k;
-  }
-  h ^= (uint32_t)n;
-  h ^= h >> 16;
-  h *= 0x85ebca6bu;
-  h ^= h >> 13;
-  h *= 0xc2b2ae35u;
-  h ^= h >> 16;
-  return h;
-}
+// ---- hash: MurmurHash3_x86_32, seed 31 (custring.inl:164-230); the function itself is minhash_ops.h's, seed as a parameter ----
+CSCONV_HD uint32_t hash_row(const uint8_t* p, int n) { return csmh::murmur3_32(p, n, 31u); }
 
 // ---- stol / stoi (custring.inl:25-52) ----------------------------------------------------------------------------------
 CSCONV_HD int64_t stol_row(const uint8_t* p, int n) {

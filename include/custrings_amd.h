@@ -724,6 +724,23 @@ int cs_porter_stemmer_measure(const cs_column* col, const char* vowels, const ch
  * a total of 2^31 or more: CS_ERR_RANGE. */
 int cs_scatter_count(const cs_column* col, const uint32_t* counts, int on_device, cs_stream stream, cs_column** out);
 
+/* ---- minhash: MinHash signatures of a column and LSH band keys (no reference member; the definition and the per-row logic
+ * are custrings_amd/csrc/minhash_ops.h; kernels cs_minhash.hip) ----------------------------------------------------
+ * results[r * nperm + i] = the minimum, over the n-grams of `width` characters of row r, of
+ * ((MurmurHash3_x86_32(n-gram bytes, seed) * a[i] + b[i]) mod (2^61 - 1)) & 0xFFFFFFFF.  A character starts at every byte
+ * that is no continuation byte; a row of fewer than `width` characters (and one at least) is one n-gram; a row of none
+ * -- null, empty, continuation bytes only -- gives 0xFFFFFFFF everywhere.  `a` and `b` are host arrays of nperm values;
+ * `results` is device memory when on_device.  A null `col` / `a` / `b`, width < 1 or nperm < 1: CS_ERR_INVALID_ARG;
+ * width > 255, nperm > 4096 or some a[i] == 0: CS_ERR_RANGE.  A column of no rows or a NULL `results` writes nothing. */
+int cs_minhash(const cs_column* col, int width, uint32_t seed, const uint32_t* a, const uint32_t* b, int nperm, uint32_t* results, int on_device,
+               cs_stream stream);
+/* keys[r * bands + j] = (int64)j << 32 | MurmurHash3_x86_32(the nperm / bands values of band j of signature r as
+ * little-endian bytes, seed j): equal keys mean two rows agree on a whole band, keys of different bands never collide.
+ * `signatures` (rows x nperm) and `keys` are both device memory when on_device, both host memory otherwise.  nperm < 1,
+ * bands < 1, nperm % bands != 0, rows < 0 or a NULL `signatures` with rows > 0: CS_ERR_INVALID_ARG; nperm > 4096:
+ * CS_ERR_RANGE.  rows == 0 or a NULL `keys` writes nothing. */
+int cs_minhash_bands(const uint32_t* signatures, int64_t rows, int nperm, int bands, int64_t* keys, int on_device, cs_stream stream);
+
 /* ---- the URL codec, translate and fillna (reference: cpp/src/strings/urlencode.cu, modify.cu:302-489; per-row logic in
  * custrings_amd/csrc/recode_ops.h; kernels cs_recode.hip) --------------------------------------------------------
  * url_encode, url_decode and translate keep null rows null (the output shares the input's validity); an output row of

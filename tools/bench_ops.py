@@ -61,7 +61,7 @@ def report(config, op, rows, in_bytes, alg_bytes, dt):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scale", type=float, default=1.0, help="row-count multiplier (1.0 = BASELINE.json single-GPU sizes)")
-    ap.add_argument("--only", default="C2,C3,C4,C5", help="comma-separated configs to run (CONV: the conversion ops, TS: the timestamp ones, PAD: substring / padding / wrapping, CHR: character types and swapcase / capitalize / title, TXT: the NVText matches, edit distance, stemmer measure and scatter_count, URL: url_encode / url_decode / translate / fillna, NUM: the numeric categories -- from_numbers, to_numbers, merge_and_remap -- beside two yardsticks, CSV: from_csv -- the line-start kernels, the field locator and the whole call, STATS: compute_statistics / get_info -- the fused pass beside the separate ops, the histogram layouts, the whole call)")
+    ap.add_argument("--only", default="C2,C3,C4,C5", help="comma-separated configs to run (CONV: the conversion ops, TS: the timestamp ones, PAD: substring / padding / wrapping, CHR: character types and swapcase / capitalize / title, TXT: the NVText matches, edit distance, stemmer measure and scatter_count, URL: url_encode / url_decode / translate / fillna, NUM: the numeric categories -- from_numbers, to_numbers, merge_and_remap -- beside two yardsticks, CSV: from_csv -- the line-start kernels, the field locator and the whole call, STATS: compute_statistics / get_info -- the fused pass beside the separate ops, the histogram layouts, the whole call, MINHASH: minhash on short and long rows at nperm 1 / 64 / 256 and the band keys)")
     a = ap.parse_args()
     only = set(a.only.split(","))
     ov = 8.125  # native offset + validity bytes per row
@@ -92,6 +92,53 @@ def main():
         run_csv(a)
     if "STATS" in only:
         run_stats(a)
+    if "MINHASH" in only:
+        run_minhash(a)
+
+
+def run_minhash(a):
+    """minhash (cs_minhash) at width 5: the C3 log-line column and the C5 column at 2M rows (x --scale) and a generated column
+    of 20 000 rows of ~4 KB, at nperm 64 and 256 -- ms, (n-grams x nperm) per second, the form that ran -- and at nperm 1,
+    where the input read rate is set beside the box's read-only stream rate (cs_box_rates); then the band keys of the
+    256-wide signatures.  The n-gram count comes from len(): max(chars - 4, 1) for a row with a character."""
+    import numpy as np
+
+    from custrings_amd import minhash
+
+    rates = (C.c_double * 6)()
+    _lib.check(L.cs_box_rates(2048, 3, None, rates))
+    print(json.dumps({"config": "MINHASH box", "read_GBps": round(rates[1] * 1e3, 1)}), flush=True)
+    rows = int(2_000_000 * a.scale)
+    long_rows = max(int(20_000 * a.scale), 64)
+    rng = np.random.default_rng(SEED)
+    lens = rng.integers(3600, 4600, size=long_rows)
+    offs = np.zeros(long_rows + 1, dtype=np.int64)
+    np.cumsum(lens, out=offs[1:])
+    text = rng.integers(97, 123, size=int(offs[-1]), dtype=np.uint8)
+    text[rng.integers(0, 6, size=text.size) == 0] = 32
+    cols = [("C3", lambda: synth(3, rows)), ("C5", lambda: synth(5, rows)), ("4KB", lambda: nvstrings.from_offsets64(text, offs, long_rows, None))]
+    for name, make in cols:
+        col = make()
+        n = col.size()
+        nch = torch.empty(n, dtype=torch.int32, device="cuda")
+        col.len(nch.data_ptr())
+        grams = int(torch.where(nch >= 5, nch - 4, nch.clamp(0, 1)).sum(dtype=torch.int64).item())
+        for nperm in (1, 64, 256):
+            pa, pb = minhash.permutations(nperm, 0)
+            out = torch.empty((n, nperm), dtype=torch.int32, device="cuda")
+            dt = timed(lambda: minhash.minhash(col, width=5, seed=0, a=pa, b=pb, devptr=out), reps=3)
+            line = {"config": "MINHASH " + name, "op": "minhash width 5 nperm %d" % nperm, "route": L.cs_debug_last_route().decode(), "rows": n,
+                    "bytes": nbytes(col), "ngrams": grams, "ms": round(dt * 1e3, 3), "gram_perms_per_s": round(grams * nperm / dt, 0)}
+            if nperm == 1:
+                line["input_GBps"] = round((nbytes(col) + 8.125 * n) / dt / 1e9, 1)
+                line["frac_of_box_read_rate"] = round((nbytes(col) + 8.125 * n) / dt / (rates[1] * 1e12), 4)
+            print(json.dumps(line), flush=True)
+            if nperm == 256:
+                keys = torch.empty((n, 32), dtype=torch.int64, device="cuda")
+                dt = timed(lambda: minhash.band_keys(out, 32, devptr=keys), reps=3)
+                print(json.dumps({"config": "MINHASH " + name, "op": "band_keys 256 -> 32", "rows": n, "ms": round(dt * 1e3, 3)}), flush=True)
+            del out
+        del col
 
 
 def run_stats(a):
