@@ -88,6 +88,7 @@ _PROTOS = {
     "cs_split_record": (i32, [vp, cp, i32, vp, i32, vp, P(vp)]),
     "cs_rsplit_record": (i32, [vp, cp, i32, vp, i32, vp, P(vp)]),
     "cs_partition": (i32, [vp, cp, i32, vp, P(vp)]),
+    "cs_category_indexes_for": (i32, [vp, i32, vp, i32, vp, P(i64)]),
     "cs_category_to_strings": (i32, [vp, vp, P(vp)]),
     "cs_category_gather_strings": (i32, [vp, vp, i64, i32, vp, P(vp)]),
     "cs_category_gather": (i32, [vp, vp, i64, i32, vp, P(vp)]),

@@ -756,6 +756,10 @@ int cs_category_merge(const cs_category* const* cats, int ncats, cs_stream strea
     // category of the concatenated key sets: its keys are the merged key set and
     // its codes are, per input category, the old-code -> new-code table
     std::unique_ptr<cs_category> merged(build(all_keys.get(), s));
+    if (all_keys->rows == 0) {  // NVCategory.cu:443-444: no key anywhere -> an empty category, whatever rows there were
+      *out = merged.release();
+      return;
+    }
     auto res = std::make_unique<cs_category>();
     res->rows = total_rows;
     res->values = dev_alloc(sizeof(int32_t) * total_rows, s);

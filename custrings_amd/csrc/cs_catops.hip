@@ -2,7 +2,8 @@
 // gather_strings, gather, gather_and_remap, add_strings, remove_strings, merge_category,
 // merge_and_remap, add / remove / set keys and remove_unused_keys (all "_and_remap").
 //
-// A category is (sorted unique keys column, int32 value per row).  Every member of the
+// A category is (unique keys column, int32 value per row; -1 = no key).  The keys are sorted, null first, but behind
+// merge_category, which appends, and in what gather / gather_and_remap / a copy make of such a category.  Every member of the
 // family is "compute a new key set, then send each value through an old-key -> new-key
 // table".  The table comes from ONE category build over the concatenation new keys ++ old
 // keys: equal strings get equal codes there, so a scatter of the new keys' codes followed
@@ -70,6 +71,46 @@ std::unique_ptr<cs_column> unique_sorted(const cs_column* strs, hipStream_t s) {
   return std::move(c->keys);
 }
 cs_category* copy_category(const cs_category* cat, hipStream_t s) { return remapped(cat, copy_handle(cat->keys.get()), nullptr, s); }
+cs_category* empty_category(hipStream_t s) {
+  auto out = std::make_unique<cs_category>();
+  out->rows = 0;
+  out->keys.reset(make_all_null(0, s));
+  out->values = dev_alloc(sizeof(int32_t), s);
+  return out.release();
+}
+
+// table[i] = flags[i] ? base + place[slot[i]] : keep[i] (-1 without `keep`)
+__global__ void k_table_from_places(const int32_t* __restrict__ flags, const int64_t* __restrict__ slot, int64_t n, int32_t base,
+                                    const int32_t* __restrict__ place, const int32_t* __restrict__ keep, int32_t* __restrict__ table) {
+  int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i < n) table[i] = flags[i] ? base + place[slot[i]] : (keep ? keep[i] : -1);
+}
+// The flagged rows of `keys` (distinct strings, any order; c = compact(flags, keys->rows)) as a SORTED column, and in
+// `table` where each key went: base + its place in that column, keep[i] (-1 without `keep`) for a key that is not flagged.
+// The reference picks the keys it keeps out of a stable sort of all of them (NVCategory.cu:1260, 1510, 1622), so they come
+// out sorted whatever order the category held them in (merge_category leaves them unsorted).
+std::unique_ptr<cs_column> sorted_subset(const cs_column* keys, const int32_t* flags, const Compacted& c, int32_t base, const int32_t* keep, Buf& table,
+                                         hipStream_t s) {
+  const int64_t nk = keys->rows;
+  table = dev_alloc(sizeof(int32_t) * std::max<int64_t>(nk, 1), s);
+  if (c.n == 0) {
+    if (nk) hipLaunchKernelGGL(k_table_from_slots, dim3(blocks_for(nk)), dim3(kBlock), 0, s, flags, ptr<const int64_t>(c.slot), nk, base, keep, ptr<int32_t>(table));
+    CS_HIP(hipStreamSynchronize(s));
+    return std::unique_ptr<cs_column>(make_all_null(0, s));
+  }
+  std::unique_ptr<cs_column> picked(gather_rows(keys, ptr<const int32_t>(c.pos), c.n, s));
+  std::unique_ptr<cs_category> u(category_build(picked.get(), s));  // distinct rows: its keys are `picked` sorted, its values their places
+  if (u->keys->rows != c.n) fail(CS_ERR_INTERNAL, "category keys are not distinct");
+  hipLaunchKernelGGL(k_table_from_places, dim3(blocks_for(nk)), dim3(kBlock), 0, s, flags, ptr<const int64_t>(c.slot), nk, base, ptr<const int32_t>(u->values), keep,
+                     ptr<int32_t>(table));
+  CS_HIP(hipStreamSynchronize(s));
+  return std::move(u->keys);
+}
+// rows[i] == v
+__global__ void k_flag_value(const int32_t* __restrict__ values, int64_t n, int32_t v, int32_t* __restrict__ out) {
+  int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i < n) out[i] = values[i] == v ? 1 : 0;
+}
 
 
 }  // namespace
@@ -184,7 +225,11 @@ int cs_category_merge_category(const cs_category* cat, const cs_category* cat2, 
     require_device();
     hipStream_t s = S(stream);
     const int64_t k1 = cat->keys->rows, k2 = cat2->keys->rows;
-    if (k1 == 0 || k2 == 0) {  // NVCategory.cu:1231-1239: a copy of the one that has keys (or an empty category)
+    if (k1 == 0 && k2 == 0) {  // NVCategory.cu:1230-1231: an empty category, the rows of both are gone
+      *out = empty_category(s);
+      return;
+    }
+    if (k1 == 0 || k2 == 0) {  // :1235-1239: a copy of the one that has keys
       *out = copy_category(k1 == 0 ? cat2 : cat, s);
       return;
     }
@@ -192,12 +237,10 @@ int cs_category_merge_category(const cs_category* cat, const cs_category* cat2, 
     Buf is_new = dev_alloc(sizeof(int32_t) * k2, s);
     hipLaunchKernelGGL(k_flag_negative, dim3(blocks_for(k2)), dim3(kBlock), 0, s, ptr<const int32_t>(in1), k2, ptr<int32_t>(is_new));
     Compacted c = compact(ptr<const int32_t>(is_new), k2, s);
-    Buf table2 = dev_alloc(sizeof(int32_t) * k2, s);
-    hipLaunchKernelGGL(k_table_from_slots, dim3(blocks_for(k2)), dim3(kBlock), 0, s, ptr<const int32_t>(is_new), ptr<const int64_t>(c.slot), k2, (int32_t)k1,
-                       ptr<const int32_t>(in1), ptr<int32_t>(table2));
+    Buf table2;
+    std::unique_ptr<cs_column> fresh = sorted_subset(cat2->keys.get(), ptr<const int32_t>(is_new), c, (int32_t)k1, ptr<const int32_t>(in1), table2, s);
     auto res = std::make_unique<cs_category>();
     if (c.n) {
-      std::unique_ptr<cs_column> fresh(gather_rows(cat2->keys.get(), ptr<const int32_t>(c.pos), c.n, s));
       std::vector<const cs_column*> both{cat->keys.get(), fresh.get()};
       res->keys.reset(concat_columns(both, s));
     } else {
@@ -219,8 +262,8 @@ int cs_category_add_keys(const cs_category* cat, const cs_column* strs, cs_strea
     if (!cat || !strs || !out) fail(CS_ERR_INVALID_ARG, "add_keys: bad arguments");
     require_device();
     hipStream_t s = S(stream);
-    if (strs->rows == 0) {
-      *out = copy_category(cat, s);
+    if (strs->rows == 0) {  // :1380-1383: a copy, or an empty category when there are no keys either
+      *out = cat->keys->rows == 0 ? empty_category(s) : copy_category(cat, s);
       return;
     }
     if (cat->keys->rows == 0) {  // :1391-1403: the new keys, the values as they are
@@ -252,10 +295,8 @@ int cs_category_remove_keys(const cs_category* cat, const cs_column* strs, cs_st
     Buf keep = dev_alloc(sizeof(int32_t) * nk, s);
     hipLaunchKernelGGL(k_flag_negative, dim3(blocks_for(nk)), dim3(kBlock), 0, s, ptr<const int32_t>(hit), nk, ptr<int32_t>(keep));
     Compacted c = compact(ptr<const int32_t>(keep), nk, s);
-    Buf table = dev_alloc(sizeof(int32_t) * nk, s);
-    hipLaunchKernelGGL(k_table_from_slots, dim3(blocks_for(nk)), dim3(kBlock), 0, s, ptr<const int32_t>(keep), ptr<const int64_t>(c.slot), nk, 0,
-                       (const int32_t*)nullptr, ptr<int32_t>(table));
-    std::unique_ptr<cs_column> keys(c.n ? gather_rows(cat->keys.get(), ptr<const int32_t>(c.pos), c.n, s) : make_all_null(0, s));
+    Buf table;
+    std::unique_ptr<cs_column> keys = sorted_subset(cat->keys.get(), ptr<const int32_t>(keep), c, 0, nullptr, table, s);
     *out = remapped(cat, std::move(keys), table, s);
   });
 }
@@ -266,24 +307,39 @@ int cs_category_remove_unused_keys(const cs_category* cat, cs_stream stream, cs_
     require_device();
     hipStream_t s = S(stream);
     const int64_t nk = cat->keys->rows;
-    if (nk == 0) {
+    if (nk == 0 || cat->rows == 0) {  // :1571-1572, and :1581-1594: without values nothing counts as unused
       *out = copy_category(cat, s);
       return;
     }
     Buf used = zeros32(nk, s), bad = zeros32(1, s);
-    if (cat->rows)
-      hipLaunchKernelGGL(k_mark_used, dim3(blocks_for(cat->rows)), dim3(kBlock), 0, s, ptr<const int32_t>(cat->values), cat->rows, nk, INT32_MIN, ptr<int32_t>(used),
-                         ptr<unsigned>(bad));
+    hipLaunchKernelGGL(k_mark_used, dim3(blocks_for(cat->rows)), dim3(kBlock), 0, s, ptr<const int32_t>(cat->values), cat->rows, nk, INT32_MIN, ptr<int32_t>(used),
+                       ptr<unsigned>(bad));
     Compacted c = compact(ptr<const int32_t>(used), nk, s);
     if (c.n == nk) {
       *out = copy_category(cat, s);
       return;
     }
-    Buf table = dev_alloc(sizeof(int32_t) * nk, s);
-    hipLaunchKernelGGL(k_table_from_slots, dim3(blocks_for(nk)), dim3(kBlock), 0, s, ptr<const int32_t>(used), ptr<const int64_t>(c.slot), nk, 0,
-                       (const int32_t*)nullptr, ptr<int32_t>(table));
-    std::unique_ptr<cs_column> keys(c.n ? gather_rows(cat->keys.get(), ptr<const int32_t>(c.pos), c.n, s) : make_all_null(0, s));
+    Buf table;
+    std::unique_ptr<cs_column> keys = sorted_subset(cat->keys.get(), ptr<const int32_t>(used), c, 0, nullptr, table, s);
     *out = remapped(cat, std::move(keys), table, s);
+  });
+}
+// NVCategory::get_indexes_for (NVCategory.cu:885-915): the rows whose value is `key`, ascending, into `results` (host or
+// device memory with room for *count items; NULL: the count alone)
+int cs_category_indexes_for(const cs_category* cat, int32_t key, int32_t* results, int on_device, cs_stream stream, int64_t* count) {
+  return guard([&] {
+    if (!cat || !count) fail(CS_ERR_INVALID_ARG, "indexes_for: bad arguments");
+    require_device();
+    hipStream_t s = S(stream);
+    *count = 0;
+    const int64_t n = cat->rows;
+    if (n == 0) return;
+    Buf hit = dev_alloc(sizeof(int32_t) * n, s);
+    hipLaunchKernelGGL(k_flag_value, dim3(blocks_for(n)), dim3(kBlock), 0, s, ptr<const int32_t>(cat->values), n, key, ptr<int32_t>(hit));
+    Compacted c = compact(ptr<const int32_t>(hit), n, s);
+    *count = c.n;
+    if (results && c.n) CS_HIP(hipMemcpyAsync(results, c.pos->p, sizeof(int32_t) * c.n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+    CS_HIP(hipStreamSynchronize(s));
   });
 }
 // NVCategory::set_keys_and_remap (NVCategory.cu:1708-1822): the keys become sorted-unique(strs); values of keys that are gone become -1

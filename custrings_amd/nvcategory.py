@@ -179,19 +179,35 @@ class nvcategory:
         return lib.cs_category_values_ptr(self.m_cptr)
 
     def value_for_index(self, idx):
-        """nvcategory.py:324-341."""
-        return self.values()[idx]
+        """nvcategory.py:324-341 -- the row's value; -1 for an index outside the rows, a negative one too
+        (NVCategory::get_value, NVCategory.cu:754-763, takes it as unsigned)."""
+        return self.values()[idx] if 0 <= idx < self.size() else -1
 
     def value(self, str):
-        """nvcategory.py:343-362 -- index of a key, -1 when absent."""
+        """nvcategory.py:343-362 -- index of a key (None: the null key), -1 when absent."""
         k = self.keys().to_host()
         return k.index(str) if str in k else -1
 
     def indexes_for_key(self, str, devptr=0):
-        """nvcategory.py:276-322 -- the rows whose value is the given key."""
+        """nvcategory.py:292-322 -- the rows whose value is the given key, as a list; with `devptr` (a numpy int32 array, a
+        device tensor or a device address) they are written there and their number is returned.  A string that is no
+        key raises ValueError (pycategory.cpp:371-372)."""
         k = self.value(str)
-        res = [i for i, v in enumerate(self.values()) if v == k] if k >= 0 else []
-        return res
+        if k < 0:
+            raise ValueError("nvcategory: string not found in keys")
+        count = C.c_int64()
+        if isinstance(devptr, int) and devptr == 0:
+            check(lib.cs_category_indexes_for(self.m_cptr, k, None, 0, None, C.byref(count)))
+            res = np.zeros(max(count.value, 1), dtype=np.int32)
+            if count.value:
+                check(lib.cs_category_indexes_for(self.m_cptr, k, res.ctypes.data, 0, None, C.byref(count)))
+            return res[: count.value].tolist()
+        rp, n, dev, keep = _typed(devptr, 1, "indexes_for_key")
+        if n is not None and n < self.size():  # an array that may be too short: count first
+            check(lib.cs_category_indexes_for(self.m_cptr, k, None, 0, None, C.byref(count)))
+            _room(n, count.value, "indexes_for_key")
+        check(lib.cs_category_indexes_for(self.m_cptr, k, rp, dev, None, C.byref(count)))
+        return int(count.value)
 
     def _cat_call(self, fn, *args):
         out = C.c_void_p()

@@ -458,6 +458,10 @@ const int32_t* cs_category_values_ptr(const cs_category* cat);
 /* NVCategory::get_values (NVCategory.h:225). */
 int cs_category_get_values(const cs_category* cat, int32_t* out, int on_device,
                            cs_stream stream);
+/* NVCategory::get_indexes_for: the rows whose value is `key`, ascending, into `results` (host or device memory with room
+ * for that many int32; NULL: the count alone); *count = how many. */
+int cs_category_indexes_for(const cs_category* cat, int32_t key, int32_t* results, int on_device, cs_stream stream,
+                            int64_t* count);
 /* The remap family (NVCategory.h:247-420; NVCategory.cu:926-1822).  Keys stay
  * sorted unique (merge_category alone appends the new keys behind the old ones);
  * values of keys that disappear become -1. */

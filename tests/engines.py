@@ -15,6 +15,7 @@ import os
 import numpy as np
 
 import cpulibs
+import strcat_model as M
 from cpulibs import Col
 
 ROOT = cpulibs.ROOT
@@ -273,74 +274,48 @@ class OracleEngine:
         k, _ = self.o.category(Col.from_list(s))
         return self.o.cat_gather_strings(k, pos, strict=True).to_list()
 
-    def cat_gather(self, s, pos):  # NVCategory.cu:1142-1170: same keys, the positions as values (-1 allowed)
-        k, _ = self.o.category(Col.from_list(s))
-        if any(p < -1 or p >= k.rows for p in pos):
-            raise IndexError("out of range")
-        return k.to_list(), list(pos)
+    # the rules of the family are stated once, in strcat_model.py; the C++ oracle builds the category they start from
+    def _model(self, s):
+        keys, values = self.category(s)
+        return M.enc(keys), values
+
+    @staticmethod
+    def _lists(cat):
+        return M.dec(cat[0]), list(cat[1])
+
+    def cat_gather(self, s, pos):
+        return self._lists(M.gather(self._model(s), list(pos)))
 
     def cat_gather_and_remap(self, s, pos):
         k, _ = self.o.category(Col.from_list(s))
         nk, v = self.o.cat_gather_and_remap(k, pos)
         return nk.to_list(), v.tolist()
 
-    def cat_add_strings(self, s, t):  # NVCategory.cu:926-940: category of (rows ++ strs)
-        return self.category(self.cat_to_strings(s) + list(t))
+    def cat_add_strings(self, s, t):
+        return self._lists(M.add_strings(self._model(s), t))
 
-    def cat_remove_strings(self, s, t):  # NVCategory.cu:942-975: rows equal to any of strs (null == null) go away
-        gone = set(t)
-        return self.category([x for x in self.cat_to_strings(s) if x not in gone])
+    def cat_remove_strings(self, s, t):
+        return self._lists(M.remove_strings(self._model(s), t))
 
     def cat_add_keys(self, s, t):
         k, v = self.o.category(Col.from_list(s))
         nk, nv = self.o.cat_add_keys_and_remap(k, v, Col.from_list(t))
         return nk.to_list(), nv.tolist()
 
-    @staticmethod
-    def _sorted_keys(keys):
-        """null first, then unsigned bytewise order (custring.inl:240-261)"""
-        return sorted(keys, key=lambda x: (x is not None, b"" if x is None else x.encode("utf8")))
+    def cat_remove_keys(self, s, t):
+        return self._lists(M.remove_keys(self._model(s), t))
 
-    def _remap(self, keys, values, new_keys):
-        where = {k: i for i, k in enumerate(new_keys)}
-        return new_keys, [v if v < 0 else where.get(keys[v], -1) for v in values]
+    def cat_remove_unused_keys(self, keys, values):  # (on a given category)
+        return self._lists(M.remove_unused_keys((M.enc(keys), list(values))))
 
-    def cat_remove_keys(self, s, t):  # NVCategory.cu:1482-1565
-        keys, values = self.category(s)
-        if not keys or not t:
-            return keys, values
-        gone = set(t)
-        return self._remap(keys, values, [k for k in keys if k not in gone])
+    def cat_set_keys(self, s, t):
+        return self._lists(M.set_keys(self._model(s), t))
 
-    def cat_remove_unused_keys(self, keys, values):  # NVCategory.cu:1567-1706 (on a given category)
-        used = {v for v in values if v >= 0}
-        return self._remap(keys, values, [k for i, k in enumerate(keys) if i in used])
+    def cat_merge_category(self, s, t):
+        return self._lists(M.merge_category(self._model(s), self._model(t)))
 
-    def cat_set_keys(self, s, t):  # NVCategory.cu:1708-1822
-        keys, values = self.category(s)
-        if not t:
-            return [], ([-1] * len(values) if keys else [])
-        new_keys = self._sorted_keys(set(t))
-        if not keys:
-            return new_keys, values
-        return self._remap(keys, values, new_keys)
-
-    def cat_merge_category(self, s, t):  # NVCategory.cu:1223-1337: the new keys of cat2 go behind the keys of cat1
-        k1, v1 = self.category(s)
-        k2, v2 = self.category(t)
-        if not k1 or not k2:
-            return (k2, v2) if not k1 else (k1, v1)
-        have = set(k1)
-        merged = k1 + [k for k in k2 if k not in have]
-        where = {k: i for i, k in enumerate(merged)}
-        return merged, v1 + [v if v < 0 else where[k2[v]] for v in v2]
-
-    def cat_merge_and_remap(self, s, t):  # NVCategory.cu:1339-1345 == create_from_categories
-        k1, v1 = self.category(s)
-        k2, v2 = self.category(t)
-        merged = self._sorted_keys(set(k1) | set(k2))
-        where = {k: i for i, k in enumerate(merged)}
-        return merged, [where[k1[v]] for v in v1] + [where[k2[v]] for v in v2]
+    def cat_merge_and_remap(self, s, t):
+        return self._lists(M.merge_and_remap(self._model(s), self._model(t)))
 
 
 class EmuEngine:
