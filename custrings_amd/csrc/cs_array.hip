@@ -78,21 +78,6 @@ void prefer_offsets32(cs_column* c, hipStream_t s) {
   c->offsets = nullptr;
 }
 
-template <class T>
-struct DevArray {  // caller array made device-visible (copied when it lives on the host)
-  Buf tmp;
-  const T* d = nullptr;
-  DevArray(const T* p, int64_t n, int on_device, hipStream_t s) {
-    if (on_device || !p || n == 0) {
-      d = p;
-      return;
-    }
-    tmp = dev_alloc(sizeof(T) * (size_t)n, s);
-    CS_HIP(hipMemcpyAsync(tmp->p, p, sizeof(T) * (size_t)n, hipMemcpyHostToDevice, s));
-    d = ptr<const T>(tmp);
-  }
-};
-
 // ---- create_from_index ------------------------------------------------------------------------
 struct IndexPair {
   const char* p;
@@ -508,17 +493,32 @@ __global__ void k_join_copy(ColView in, const uint8_t* __restrict__ delim, int d
   if (put && dn > 0) copy_bytes(d, delim, dn);
 }
 
-struct HostText {  // small host string on the device (nullptr stays nullptr)
-  Buf buf;
-  int n = -1;
-  HostText(const char* t, hipStream_t s) {
-    if (!t) return;
-    n = (int)strlen(t);
-    buf = dev_alloc((size_t)n + 1, s);
-    CS_HIP(hipMemcpyAsync(buf->p, t, (size_t)n + 1, hipMemcpyHostToDevice, s));
+cs_column* join_rows(const cs_column* col, const char* delimiter, const char* narep, hipStream_t s) {
+  const int64_t rows = col->rows;
+  auto o = std::make_unique<cs_column>();
+  o->rows = 1;
+  o->null_count = 0;
+  Buf two = dev_alloc(sizeof(int64_t) * 2, s);
+  int64_t total = 0;
+  HostText del(delimiter, s), nar(narep, s);
+  Buf off;
+  if (rows) {
+    Buf lens = dev_alloc(sizeof(int32_t) * rows, s);
+    hipLaunchKernelGGL(k_join_lengths, dim3(blocks_for(rows)), dim3(kBlock), 0, s, view_of(col), del.n, nar.n, ptr<int32_t>(lens));
+    off = dev_alloc(sizeof(int64_t) * (rows + 1), s);
+    total = offsets_from_lengths(ptr<int32_t>(lens), rows, ptr<int64_t>(off), s);
   }
-  const uint8_t* d() const { return ptr<const uint8_t>(buf); }
-};
+  o->nbytes = total;
+  o->chars = dev_alloc((size_t)total, s);
+  if (rows)
+    hipLaunchKernelGGL(k_join_copy, dim3(blocks_for(rows)), dim3(kBlock), 0, s, view_of(col), del.d(), del.n, nar.d(), nar.n, ptr<const int64_t>(off),
+                       ptr<uint8_t>(o->chars));
+  const int64_t h[2] = {0, total};
+  CS_HIP(hipMemcpyAsync(two->p, h, sizeof(h), hipMemcpyHostToDevice, s));
+  CS_HIP(hipStreamSynchronize(s));
+  o->offsets = two;
+  return o.release();
+}
 
 }  // namespace cs
 
@@ -598,31 +598,7 @@ int cs_join(const cs_column* col, const char* delimiter, const char* narep, cs_s
     if (!col || !out) fail(CS_ERR_INVALID_ARG, "join: bad arguments");
     if (!delimiter) fail(CS_ERR_INVALID_ARG, "nvstrings::join delimiter cannot be null");
     require_device();
-    hipStream_t s = S(stream);
-    const int64_t rows = col->rows;
-    auto o = std::make_unique<cs_column>();
-    o->rows = 1;
-    o->null_count = 0;
-    Buf two = dev_alloc(sizeof(int64_t) * 2, s);
-    int64_t total = 0;
-    HostText del(delimiter, s), nar(narep, s);
-    Buf off;
-    if (rows) {
-      Buf lens = dev_alloc(sizeof(int32_t) * rows, s);
-      hipLaunchKernelGGL(k_join_lengths, dim3(blocks_for(rows)), dim3(kBlock), 0, s, view_of(col), del.n, nar.n, ptr<int32_t>(lens));
-      off = dev_alloc(sizeof(int64_t) * (rows + 1), s);
-      total = offsets_from_lengths(ptr<int32_t>(lens), rows, ptr<int64_t>(off), s);
-    }
-    o->nbytes = total;
-    o->chars = dev_alloc((size_t)total, s);
-    if (rows)
-      hipLaunchKernelGGL(k_join_copy, dim3(blocks_for(rows)), dim3(kBlock), 0, s, view_of(col), del.d(), del.n, nar.d(), nar.n, ptr<const int64_t>(off),
-                         ptr<uint8_t>(o->chars));
-    const int64_t h[2] = {0, total};
-    CS_HIP(hipMemcpyAsync(two->p, h, sizeof(h), hipMemcpyHostToDevice, s));
-    CS_HIP(hipStreamSynchronize(s));
-    o->offsets = two;
-    *out = o.release();
+    *out = join_rows(col, delimiter, narep, S(stream));
   });
 }
 

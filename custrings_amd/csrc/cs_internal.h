@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include <array>
 #include <memory>
@@ -266,6 +267,32 @@ struct ResultsOut {
 // A 64-bit count the kernels add to: zeroed on the device; read_count brings it back (synchronises `s`).
 Buf zeroed_count(hipStream_t s);
 int64_t read_count(const Buf& acc, hipStream_t s);
+
+template <class T>
+struct DevArray {  // caller array made device-visible (copied when it lives on the host)
+  Buf tmp;
+  const T* d = nullptr;
+  DevArray(const T* p, int64_t n, int on_device, hipStream_t s) {
+    if (on_device || !p || n == 0) {
+      d = p;
+      return;
+    }
+    tmp = dev_alloc(sizeof(T) * (size_t)n, s);
+    CS_HIP(hipMemcpyAsync(tmp->p, p, sizeof(T) * (size_t)n, hipMemcpyHostToDevice, s));
+    d = ptr<const T>(tmp);
+  }
+};
+struct HostText {  // small host string on the device (nullptr stays nullptr)
+  Buf buf;
+  int n = -1;
+  HostText(const char* t, hipStream_t s) {
+    if (!t) return;
+    n = (int)strlen(t);
+    buf = dev_alloc((size_t)n + 1, s);
+    CS_HIP(hipMemcpyAsync(buf->p, t, (size_t)n + 1, hipMemcpyHostToDevice, s));
+  }
+  const uint8_t* d() const { return ptr<const uint8_t>(buf); }
+};
 }  // namespace cs
 namespace csrow {
 struct CharSet;
@@ -361,6 +388,9 @@ cs_column* gather_rows(const cs_column* col, const int32_t* d_pos, int64_t n, hi
 // cs_array.hip: the column of `count` (pointer, byte length) spans in device memory (std::pair<const char*, size_t>; null
 // pointer = null row), sorted when `sorttype` says so (NVStrings::sorttype bits): create_from_index and from_csv
 cs_column* column_from_spans(const void* spans, int64_t count, int sorttype, hipStream_t s);
+// cs_array.hip: every row of `col` in one row, `delimiter` between them; a null row is `narep`, or without one leaves
+// nothing, no delimiter either (cs_join, and create_ngrams of a column with no more tokens than an n-gram takes)
+cs_column* join_rows(const cs_column* col, const char* delimiter, const char* narep, hipStream_t s);
 // The output column of an op that sizes its rows first (int32 lengths, negative = null row): the one host tail from
 // lengths to a column.  The constructor makes the column with its row count and nulls; scan() allocates the offsets
 // and scans the lengths into them (the total is the column's nbytes, the scan's metadata goes to the column; no rows:

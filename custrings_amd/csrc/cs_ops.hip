@@ -1,8 +1,12 @@
-// Row-parallel string ops: lower/upper, strip, find, contains, replace, split,
-// tokenize, ngrams.  One thread per row (256 rows per workgroup), every op is
-//   size kernel (+ fused block sums) -> block-sum scan -> offsets -> write kernel
-// with the per-row logic in row_ops.h.  Reference call sites are cited at each
-// entry point.
+// The C entries of the case, strip, find, replace, split, tokenize and ngrams families and their row-wise kernels: one
+// thread a row, the per-row logic in row_ops.h.  The tile routes of these families live in cs_rows.hip (strip, find,
+// contains), cs_case.hip, cs_casemodes.hip, cs_split.hip, cs_tokenize.hip and cs_ngram.hip; an entry here tries its
+// tile route first and what is in this file answers when that declines: long rows, non-ASCII arguments, a row-wise switch.
+//  - ops that make a column (case, strip, replace): two_pass -- a size kernel with fused block sums, the scan to offsets,
+//    a write kernel; split, tokenize and ngrams have kernels of their own with the same three steps;
+//  - ops that make one value a row and a count of the hits (find, rfind, find_from, compare, startswith, endswith,
+//    contains, match_strings): the counted-rows route, k_counted_rows<Op> / run_counted, with an op struct each.
+// Reference call sites are cited at each entry point.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -33,21 +37,6 @@ bool find_tiles(const cs_column* in, const unsigned char* needle, int nb, int mo
 }
 using namespace csrow;
 
-namespace {
-
-struct Needle {  // small host string copied to the device
-  Buf buf;
-  int n = 0;
-  const uint8_t* d() const { return ptr<const uint8_t>(buf); }
-};
-Needle upload(const char* s, hipStream_t st) {
-  Needle nd;
-  nd.n = (int)strlen(s);
-  nd.buf = dev_alloc((size_t)nd.n + 1, st);
-  CS_HIP(hipMemcpyAsync(nd.buf->p, s, (size_t)nd.n + 1, hipMemcpyHostToDevice, st));
-  return nd;
-}
-}  // namespace
 namespace cs {
 // the character set of a UTF-8 string of any length; `more` keeps what does not fit the struct alive for the caller's kernels
 CharSet make_charset(const char* s, Buf& more, hipStream_t st) {
@@ -178,38 +167,113 @@ struct ReplaceWrite {
   __device__ void operator()(const uint8_t* p, int n, int64_t, uint8_t* o) const { row_replace_write(p, n, needle, nb, repl, rb, maxrepl, o); }
 };
 
-// ---- find / contains ------------------------------------------------------------------
-__global__ void k_find(ColView in, const uint8_t* __restrict__ needle, int nb, int start, int end,
-                       int32_t* __restrict__ out, unsigned long long* __restrict__ found) {
-  // (grid-stride: one same-address atomic per workgroup of a capped grid, not per 256 rows)
-  int hit = 0;
-  for (int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x; r < in.rows; r += (int64_t)gridDim.x * kBlock) {
-    int v = -2;  // null row (find.cu:108)
-    if (row_is_valid(in.validity, r)) {
-      int64_t b = in.offsets[r];
-      v = row_find(in.chars + b, (int)(in.offsets[r + 1] - b), needle, nb, start, end);
-    }
-    out[r] = v;
-    hit += v != -1;  // null rows are counted too (find.cu:112)
-  }
-  long long t = block_reduce_sum(hit);
-  if (threadIdx.x == 0 && t) atomicAdd(found, (unsigned long long)t);
-}
-__global__ void k_contains(ColView in, const uint8_t* __restrict__ needle, int nb,
-                           uint8_t* __restrict__ out, unsigned long long* __restrict__ found) {
+// ---- the counted-rows route: one value a row and the count of the hits (the find family, find.cu:36-387) --------------
+// An op is a struct passed by value with its state (the needle, the bounds, the other column):
+//   using T = int32_t or uint8_t;                                                    // the result type
+//   __device__ T operator()(int64_t r, const uint8_t* p, int n, bool valid) const;  // row r's bytes [p, p + n); a null row's value too
+//   static __device__ bool counts(T v);                                              // is this result a hit
+// A thread a row on a capped grid (rows a grid apart), so the count takes one same-address atomic per workgroup and not
+// one per 256 rows, and none from a workgroup without a hit.
+template <class Op>
+__global__ void __launch_bounds__(256) k_counted_rows(ColView in, Op op, typename Op::T* __restrict__ out,
+                                                      unsigned long long* __restrict__ count) {
   int hits = 0;
-  for (int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x; r < in.rows; r += (int64_t)gridDim.x * kBlock) {
-    int hit = 0;
-    if (nb > 0 && row_is_valid(in.validity, r)) {
-      int64_t b = in.offsets[r];
-      hit = find_bytes(in.chars + b, 0, (int)(in.offsets[r + 1] - b), needle, nb) >= 0;
-    }
-    out[r] = (uint8_t)hit;
-    hits += hit;
-  }
-  long long t = block_reduce_sum(hits);
-  if (threadIdx.x == 0 && t) atomicAdd(found, (unsigned long long)t);
+  for_each_row(in, [&](int64_t r, const uint8_t* p, int n, bool valid) {
+    const typename Op::T v = op(r, p, n, valid);
+    out[r] = v;
+    hits += Op::counts(v);
+  });
+  const long long t = block_reduce_sum(hits);
+  if (threadIdx.x == 0 && t) atomicAdd(count, (unsigned long long)t);
 }
+// The host tail of every counted op: the results to the caller's buffer (host or device), the count returned.  `tiles`
+// (find, contains): the tile route, tried first -- true when it wrote the results and the count.  Synchronises `s`, so
+// what the op points to may go when this returns.
+template <class Op, class Tiles>
+int64_t run_counted(const cs_column* col, const Op& op, void* results, int on_device, const char* prof_name, hipStream_t s,
+                    Tiles&& tiles) {
+  using T = typename Op::T;
+  const Buf cnt = zeroed_count(s);
+  const ResultsOut res(results, sizeof(T) * (size_t)col->rows, on_device, s);
+  T* out = static_cast<T*>(res.dev);
+  {
+    ProfScope ps(prof_name, s);
+    if (!tiles(out, ptr<unsigned long long>(cnt)))
+      hipLaunchKernelGGL(k_counted_rows<Op>, dim3(std::min(blocks_for(col->rows), 8192u)), dim3(kBlock), 0, s, view_of(col), op,
+                         out, ptr<unsigned long long>(cnt));
+  }
+  CS_HIP(hipGetLastError());
+  res.copy_back(s);
+  return read_count(cnt, s);
+}
+template <class Op>
+int64_t run_counted(const cs_column* col, const Op& op, void* results, int on_device, const char* prof_name, hipStream_t s) {
+  return run_counted(col, op, results, on_device, prof_name, s, [](typename Op::T*, unsigned long long*) { return false; });
+}
+
+// positions in characters, -1 no occurrence, -2 a null row -- which the reference counts like a hit (find.cu:108-112)
+struct FindOp {  // find(str, start, end)
+  using T = int32_t;
+  const uint8_t* needle;
+  int nb, start, end;
+  __device__ T operator()(int64_t, const uint8_t* p, int n, bool valid) const { return valid ? row_find(p, n, needle, nb, start, end) : -2; }
+  static __device__ bool counts(T v) { return v != -1; }
+};
+struct RfindOp {  // rfind(str, start, end), start >= 0
+  using T = int32_t;
+  const uint8_t* needle;
+  int nb, start, end;
+  __device__ T operator()(int64_t, const uint8_t* p, int n, bool valid) const {
+    return valid ? row_rfind_count(p, n, needle, nb, (unsigned)start, end - start) : -2;
+  }
+  static __device__ bool counts(T v) { return v != -1; }
+};
+struct FindFromOp {  // find_from(str, starts[], ends[]): a window a row; no starts: from 0, no ends: to the row's end
+  using T = int32_t;
+  const uint8_t* needle;
+  int nb;
+  const int32_t *starts, *ends;
+  __device__ T operator()(int64_t r, const uint8_t* p, int n, bool valid) const {
+    if (!valid) return -2;
+    const int pos = starts ? starts[r] : 0;
+    return row_find_count(p, n, needle, nb, (unsigned)pos, ends ? ends[r] - pos : -1);
+  }
+  static __device__ bool counts(T v) { return v != -1; }
+};
+struct CompareOp {  // compare(str): 0 equal, and those are counted; a null row -1
+  using T = int32_t;
+  const uint8_t* needle;
+  int nb;
+  __device__ T operator()(int64_t, const uint8_t* p, int n, bool valid) const { return valid ? row_compare(p, n, needle, nb) : -1; }
+  static __device__ bool counts(T v) { return v == 0; }
+};
+template <bool kEnd>
+struct AffixOp {  // startswith(str) / endswith(str); a null row is false
+  using T = uint8_t;
+  const uint8_t* needle;
+  int nb;
+  __device__ T operator()(int64_t, const uint8_t* p, int n, bool valid) const {
+    return valid && (kEnd ? row_ends_with(p, n, needle, nb) : row_starts_with(p, n, needle, nb));
+  }
+  static __device__ bool counts(T v) { return v; }
+};
+struct ContainsOp {  // contains(str) by bytes; an empty needle and a null row are false
+  using T = uint8_t;
+  const uint8_t* needle;
+  int nb;
+  __device__ T operator()(int64_t, const uint8_t* p, int n, bool valid) const { return nb > 0 && valid && find_bytes(p, 0, n, needle, nb) >= 0; }
+  static __device__ bool counts(T v) { return v; }
+};
+struct MatchStringsOp {  // match_strings(other): equal rows; two nulls are equal
+  using T = uint8_t;
+  ColView other;
+  __device__ T operator()(int64_t r, const uint8_t* p, int n, bool valid) const {
+    if (!row_is_valid(other.validity, r)) return !valid;
+    const int64_t o0 = other.offsets[r];
+    return valid && row_compare(p, n, other.chars + o0, (int)(other.offsets[r + 1] - o0)) == 0;
+  }
+  static __device__ bool counts(T v) { return v; }
+};
 
 // ---- split ---------------------------------------------------------------------------------
 struct SplitArgs {
@@ -374,26 +438,6 @@ __global__ void k_ngram_write(ColView in, const int32_t* __restrict__ kept, int6
       for (int i = 0; i < sepn; ++i) *o++ = sep[i];
   }
 }
-// join(sep, narep="") of every row into one string (combine.cu:291-420 as used by ngram.cu:51-52)
-__global__ void k_join_sizes(ColView in, int sepn, int32_t* __restrict__ lens) {
-  int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (r >= in.rows) return;
-  int len = row_is_valid(in.validity, r) ? (int)(in.offsets[r + 1] - in.offsets[r]) : 0;
-  lens[r] = len + (r + 1 < in.rows ? sepn : 0);
-}
-__global__ void k_join_write(ColView in, const uint8_t* __restrict__ sep, int sepn,
-                             const int64_t* __restrict__ pos, uint8_t* __restrict__ out) {
-  int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (r >= in.rows) return;
-  uint8_t* o = out + pos[r];
-  if (row_is_valid(in.validity, r)) {
-    const uint8_t* p = in.chars + in.offsets[r];
-    int len = (int)(in.offsets[r + 1] - in.offsets[r]);
-    for (int i = 0; i < len; ++i) *o++ = p[i];
-  }
-  if (r + 1 < in.rows)
-    for (int i = 0; i < sepn; ++i) *o++ = sep[i];
-}
 
 template <class T>
 T read_back(const Buf& b, hipStream_t s) {
@@ -492,75 +536,17 @@ int cs_find(const cs_column* col, const char* str, int start, int end, int32_t* 
     if (!col || !str || !results || col->rows == 0) return;  // reference returns 0 (find.cu:78-79)
     require_device();
     hipStream_t s = S(stream);
-    Needle nd = upload(str, s);
-    const Buf cnt = zeroed_count(s);
-    const ResultsOut res(results, sizeof(int32_t) * col->rows, on_device, s);
-    int32_t* d_out = static_cast<int32_t*>(res.dev);
-    {
-      ProfScope ps("k_find", s);
-      if (!find_tiles(col, reinterpret_cast<const unsigned char*>(str), nd.n, 0, start, end, d_out, nullptr,
-                      ptr<unsigned long long>(cnt), s))
-        hipLaunchKernelGGL(k_find, dim3(std::min(blocks_for(col->rows), 8192u)), dim3(kBlock), 0, s, view_of(col), nd.d(),
-                           nd.n, start, end, d_out, ptr<unsigned long long>(cnt));
-    }
-    res.copy_back(s);
-    const int64_t n = read_count(cnt, s);
+    const HostText nd(str, s);
+    const int64_t n = run_counted(col, FindOp{nd.d(), nd.n, start, end}, results, on_device, "k_find", s, [&](int32_t* out, unsigned long long* cnt) {
+      return find_tiles(col, reinterpret_cast<const unsigned char*>(str), nd.n, 0, start, end, out, nullptr, cnt, s);
+    });
     if (found) *found = n;
   });
 }
 
-// ---- rfind, find_from, find_multiple, compare, match_strings, startswith, endswith (find.cu:36-72, 123-236, 276-387) ----
-// One thread a row (these are not on the benchmarked path).  `op`: 0 rfind(start, end), 1 find_from(starts[], ends[]),
-// 2 compare, 3 startswith, 4 endswith; null rows: -2 for the positions, -1 for compare, false for the predicates.
-__global__ void k_find_family(ColView in, int op, const uint8_t* __restrict__ needle, int nb, int start, int end, const int32_t* __restrict__ starts,
-                              const int32_t* __restrict__ ends, int32_t* __restrict__ out32, uint8_t* __restrict__ out8, unsigned long long* __restrict__ count) {
-  int hit = 0;  // (a capped grid, rows a grid apart: one addition to `count` per workgroup -- see k_find)
-  for (int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x; r < in.rows; r += (int64_t)gridDim.x * kBlock) {
-    const bool valid = row_is_valid(in.validity, r);
-    const int64_t b = in.offsets[r];
-    const uint8_t* p = in.chars + b;
-    const int n = valid ? (int)(in.offsets[r + 1] - b) : 0;
-    if (op == 0) {
-      const int v = valid ? row_rfind_count(p, n, needle, nb, (unsigned)start, end - start) : -2;
-      out32[r] = v;
-      hit += v != -1;
-    } else if (op == 1) {
-      int v = -2;
-      if (valid) {
-        const int pos = starts ? starts[r] : 0;
-        v = row_find_count(p, n, needle, nb, (unsigned)pos, ends ? ends[r] - pos : -1);
-      }
-      out32[r] = v;
-      hit += v != -1;
-    } else if (op == 2) {
-      const int v = valid ? row_compare(p, n, needle, nb) : -1;
-      out32[r] = v;
-      hit += v == 0;
-    } else {
-      const bool v = valid && (op == 3 ? row_starts_with(p, n, needle, nb) : row_ends_with(p, n, needle, nb));
-      out8[r] = v ? 1 : 0;
-      hit += v;
-    }
-  }
-  const long long t = block_reduce_sum(hit);
-  if (threadIdx.x == 0 && t) atomicAdd(count, (unsigned long long)t);
-}
-// match_strings: equal rows (two nulls are equal); find_multiple: out[r * tcount + j] = position of target j in row r
-__global__ void k_match_strings(ColView a, ColView b, uint8_t* __restrict__ out, unsigned long long* __restrict__ count) {
-  int hit = 0;
-  for (int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x; r < a.rows; r += (int64_t)gridDim.x * kBlock) {
-    const bool va = row_is_valid(a.validity, r), vb = row_is_valid(b.validity, r);
-    bool same = va == vb;
-    if (va && vb) {
-      const int64_t oa = a.offsets[r], ob = b.offsets[r];
-      same = row_compare(a.chars + oa, (int)(a.offsets[r + 1] - oa), b.chars + ob, (int)(b.offsets[r + 1] - ob)) == 0;
-    }
-    out[r] = same ? 1 : 0;
-    hit += same;
-  }
-  const long long t = block_reduce_sum(hit);
-  if (threadIdx.x == 0 && t) atomicAdd(count, (unsigned long long)t);
-}
+// ---- rfind, find_from, compare, startswith, endswith, match_strings, find_multiple (find.cu:36-72, 123-236, 276-387):
+// no tile route, a thread a row (these are not on the benchmarked path) ----
+// find_multiple has rows x targets results, so kernels of its own: out[r * tcount + j] = position of target j in row r
 __global__ void k_find_multiple(ColView in, ColView targets, int32_t* __restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= in.rows * targets.rows) return;
@@ -578,44 +564,16 @@ __global__ void k_count_not_minus_one(const int32_t* __restrict__ v, int64_t n, 
   const long long t = block_reduce_sum(hit);
   if (threadIdx.x == 0 && t) atomicAdd(count, (unsigned long long)t);
 }
-// shared driver of the one-needle ops
-static void find_family(const cs_column* col, int op, const char* str, int start, int end, const int32_t* starts, const int32_t* ends, int bounds_on_device,
-                        void* results, int on_device, hipStream_t s, int64_t* found) {
-  const int64_t rows = col->rows;
-  const bool bools = op >= 3;
-  Needle nd = upload(str, s);
-  const Buf cnt = zeroed_count(s);
-  Buf sbuf, ebuf;
-  const ResultsOut res(results, (bools ? 1 : sizeof(int32_t)) * rows, on_device, s);
-  void* d_out = res.dev;
-  if (starts && !bounds_on_device) {
-    sbuf = dev_alloc(sizeof(int32_t) * rows, s);
-    CS_HIP(hipMemcpyAsync(sbuf->p, starts, sizeof(int32_t) * rows, hipMemcpyHostToDevice, s));
-    starts = ptr<const int32_t>(sbuf);
-  }
-  if (ends && !bounds_on_device) {
-    ebuf = dev_alloc(sizeof(int32_t) * rows, s);
-    CS_HIP(hipMemcpyAsync(ebuf->p, ends, sizeof(int32_t) * rows, hipMemcpyHostToDevice, s));
-    ends = ptr<const int32_t>(ebuf);
-  }
-  {
-    ProfScope ps("k_find_family", s);
-    hipLaunchKernelGGL(k_find_family, dim3(std::min(blocks_for(rows), 8192u)), dim3(kBlock), 0, s, view_of(col), op, nd.d(), nd.n, start, end, starts, ends,
-                       bools ? nullptr : static_cast<int32_t*>(d_out), bools ? static_cast<uint8_t*>(d_out) : nullptr, ptr<unsigned long long>(cnt));
-  }
-  CS_HIP(hipGetLastError());
-  res.copy_back(s);
-  const int64_t n = read_count(cnt, s);  // (synchronises: the staged bounds and the needle may go)
-  if (found) *found = n;
-}
-
 // NVStrings::rfind -- find.cu:163-200
 int cs_rfind(const cs_column* col, const char* str, int start, int end, int32_t* results, int on_device, cs_stream stream, int64_t* found) {
   return guard([&] {
     if (found) *found = 0;
     if (!col || !str || !results || col->rows == 0) return;  // the reference returns 0
     require_device();
-    find_family(col, 0, str, start < 0 ? 0 : start, end, nullptr, nullptr, 1, results, on_device, S(stream), found);
+    hipStream_t s = S(stream);
+    const HostText nd(str, s);
+    const int64_t n = run_counted(col, RfindOp{nd.d(), nd.n, start < 0 ? 0 : start, end}, results, on_device, "k_find_family", s);
+    if (found) *found = n;
   });
 }
 // NVStrings::find_from -- find.cu:123-160 (`starts` / `ends`: one int32 per row, either may be null)
@@ -625,10 +583,14 @@ int cs_find_from(const cs_column* col, const char* str, const int32_t* starts, c
     if (found) *found = 0;
     if (!col || !str || !results || col->rows == 0) return;
     require_device();
-    find_family(col, 1, str, 0, 0, starts, ends, bounds_on_device, results, on_device, S(stream), found);
+    hipStream_t s = S(stream);
+    const HostText nd(str, s);
+    const DevArray<int32_t> from(starts, col->rows, bounds_on_device, s), to(ends, col->rows, bounds_on_device, s);
+    const int64_t n = run_counted(col, FindFromOp{nd.d(), nd.n, from.d, to.d}, results, on_device, "k_find_family", s);
+    if (found) *found = n;
   });
 }
-// NVStrings::compare -- find.cu:36-72 (an empty `str` leaves the results alone and returns 0)
+// NVStrings::compare -- find.cu:36-72
 int cs_compare(const cs_column* col, const char* str, int32_t* results, int on_device, cs_stream stream, int64_t* matches) {
   return guard([&] {
     if (matches) *matches = 0;
@@ -636,7 +598,10 @@ int cs_compare(const cs_column* col, const char* str, int32_t* results, int on_d
     // the comparison with the empty string is computed like any other: 1 for a non-empty row, 0 for an empty one)
     if (!col || !str || !results || col->rows == 0) return;
     require_device();
-    find_family(col, 2, str, 0, 0, nullptr, nullptr, 1, results, on_device, S(stream), matches);
+    hipStream_t s = S(stream);
+    const HostText nd(str, s);
+    const int64_t n = run_counted(col, CompareOp{nd.d(), nd.n}, results, on_device, "k_find_family", s);
+    if (matches) *matches = n;
   });
 }
 // NVStrings::startswith / endswith -- find.cu:316-387
@@ -645,7 +610,10 @@ int cs_startswith(const cs_column* col, const char* str, uint8_t* results, int o
     if (matches) *matches = 0;
     if (!col || !str || !results || col->rows == 0) return;
     require_device();
-    find_family(col, 3, str, 0, 0, nullptr, nullptr, 1, results, on_device, S(stream), matches);
+    hipStream_t s = S(stream);
+    const HostText nd(str, s);
+    const int64_t n = run_counted(col, AffixOp<false>{nd.d(), nd.n}, results, on_device, "k_find_family", s);
+    if (matches) *matches = n;
   });
 }
 int cs_endswith(const cs_column* col, const char* str, uint8_t* results, int on_device, cs_stream stream, int64_t* matches) {
@@ -653,7 +621,10 @@ int cs_endswith(const cs_column* col, const char* str, uint8_t* results, int on_
     if (matches) *matches = 0;
     if (!col || !str || !results || col->rows == 0) return;
     require_device();
-    find_family(col, 4, str, 0, 0, nullptr, nullptr, 1, results, on_device, S(stream), matches);
+    hipStream_t s = S(stream);
+    const HostText nd(str, s);
+    const int64_t n = run_counted(col, AffixOp<true>{nd.d(), nd.n}, results, on_device, "k_find_family", s);
+    if (matches) *matches = n;
   });
 }
 // NVStrings::match_strings -- find.cu:276-314 (sizes must match: std::invalid_argument there)
@@ -665,14 +636,7 @@ int cs_match_strings(const cs_column* col, const cs_column* other, uint8_t* resu
     if (col->rows == 0) return;
     if (col->rows != other->rows) fail(CS_ERR_INVALID_ARG, "sizes must match");
     require_device();
-    hipStream_t s = S(stream);
-    const Buf cnt = zeroed_count(s);
-    const ResultsOut res(results, (size_t)col->rows, on_device, s);
-    hipLaunchKernelGGL(k_match_strings, dim3(std::min(blocks_for(col->rows), 8192u)), dim3(kBlock), 0, s, view_of(col), view_of(other), static_cast<uint8_t*>(res.dev),
-                       ptr<unsigned long long>(cnt));
-    CS_HIP(hipGetLastError());
-    res.copy_back(s);
-    const int64_t n = read_count(cnt, s);
+    const int64_t n = run_counted(col, MatchStringsOp{view_of(other)}, results, on_device, "k_match_strings", S(stream));
     if (matches) *matches = n;
   });
 }
@@ -707,19 +671,10 @@ int cs_contains(const cs_column* col, const char* str, uint8_t* results, int on_
     if (col->rows == 0) return;
     require_device();
     hipStream_t s = S(stream);
-    Needle nd = upload(str, s);
-    const Buf cnt = zeroed_count(s);
-    const ResultsOut res(results, (size_t)col->rows, on_device, s);
-    uint8_t* d_out = static_cast<uint8_t*>(res.dev);
-    {
-      ProfScope ps("k_contains", s);
-      if (!find_tiles(col, reinterpret_cast<const unsigned char*>(str), nd.n, 1, 0, 0, nullptr, d_out,
-                      ptr<unsigned long long>(cnt), s))
-        hipLaunchKernelGGL(k_contains, dim3(std::min(blocks_for(col->rows), 8192u)), dim3(kBlock), 0, s, view_of(col), nd.d(),
-                           nd.n, d_out, ptr<unsigned long long>(cnt));
-    }
-    res.copy_back(s);
-    const int64_t n = read_count(cnt, s);
+    const HostText nd(str, s);
+    const int64_t n = run_counted(col, ContainsOp{nd.d(), nd.n}, results, on_device, "k_contains", s, [&](uint8_t* out, unsigned long long* cnt) {
+      return find_tiles(col, reinterpret_cast<const unsigned char*>(str), nd.n, 1, 0, 0, nullptr, out, cnt, s);
+    });
     if (found) *found = n;
   });
 }
@@ -767,7 +722,7 @@ int cs_replace(const cs_column* col, const char* str, const char* repl, int maxr
         }
       }
     }
-    Needle nd = upload(str, s), rp = upload(repl, s);
+    const HostText nd(str, s), rp(repl, s);
     *out = two_pass(col, ReplaceSize{nd.d(), nd.n, rp.n, maxrepl},
                     ReplaceWrite{nd.d(), rp.d(), nd.n, rp.n, maxrepl}, s, "k_replace_size", "k_replace_write");
   });
@@ -868,9 +823,8 @@ static int split_impl(const cs_column* col, const char* delimiter, int maxsplit,
     hipStream_t s = S(stream);
     SplitArgs a{nullptr, 0, maxsplit > 0 ? maxsplit + 1 : 0, 0, 0};
     a.reverse = reverse && !rsplit_walks_like_split(delimiter, maxsplit) ? 1 : 0;
-    Needle nd;
+    const HostText nd(delimiter, s);
     if (delimiter) {
-      nd = upload(delimiter, s);
       a.delim = nd.d();
       a.nb = nd.n;
     }
@@ -963,7 +917,7 @@ int cs_ngrams(const cs_column* tokens, unsigned ngrams, const char* separator, c
     // tile kernel with closed-form offsets when no row is dropped (cs_ngram.hip)
     if (ngrams_fast(tokens, (int)ngrams, reinterpret_cast<const unsigned char*>(separator), (int)strlen(separator), s, out))
       return;
-    Needle sep = upload(separator, s);
+    const HostText sep(separator, s);
     // drop null and empty rows (ngram.cu:48-50)
     Buf flags = dev_alloc(sizeof(int32_t) * rows, s);
     hipLaunchKernelGGL(k_keep_flags, dim3(blocks_for(rows)), dim3(kBlock), 0, s, view_of(tokens),
@@ -972,24 +926,7 @@ int cs_ngrams(const cs_column* tokens, unsigned ngrams, const char* separator, c
     int64_t count = offsets_from_lengths(ptr<int32_t>(flags), rows, ptr<int64_t>(pos), s);
     if (count <= (int64_t)ngrams) {
       // join(separator, "") over ALL rows, nulls contributing "" (ngram.cu:51-52)
-      Buf lens = dev_alloc(sizeof(int32_t) * rows, s);
-      hipLaunchKernelGGL(k_join_sizes, dim3(blocks_for(rows)), dim3(kBlock), 0, s, view_of(tokens), sep.n,
-                         ptr<int32_t>(lens));
-      Buf jpos = dev_alloc(sizeof(int64_t) * (rows + 1), s);
-      int64_t total = offsets_from_lengths(ptr<int32_t>(lens), rows, ptr<int64_t>(jpos), s);
-      auto* c = new cs_column;
-      std::unique_ptr<cs_column> holder(c);
-      c->rows = 1;
-      c->nbytes = total;
-      c->null_count = 0;
-      c->chars = dev_alloc((size_t)total, s);
-      c->offsets = dev_alloc(sizeof(int64_t) * 2, s);
-      int64_t two[2] = {0, total};
-      CS_HIP(hipMemcpyAsync(c->offsets->p, two, sizeof(two), hipMemcpyHostToDevice, s));
-      hipLaunchKernelGGL(k_join_write, dim3(blocks_for(rows)), dim3(kBlock), 0, s, view_of(tokens), sep.d(),
-                         sep.n, ptr<const int64_t>(jpos), ptr<uint8_t>(c->chars));
-      CS_HIP(hipStreamSynchronize(s));
-      *out = holder.release();
+      *out = join_rows(tokens, separator, "", s);
       return;
     }
     if (ngrams == 1) {
