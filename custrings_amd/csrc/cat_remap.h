@@ -77,12 +77,6 @@ Compacted compact(const int32_t* d_flags, int64_t n, hipStream_t s) {
   if (c.n) hipLaunchKernelGGL(k_compact, dim3(blocks_for(n)), dim3(kBlock), 0, s, d_flags, ptr<const int64_t>(c.slot), n, ptr<int32_t>(c.pos));
   return c;
 }
-unsigned read_flag(const Buf& b, hipStream_t s) {
-  unsigned* h = (unsigned*)pinned_scratch(sizeof(unsigned));
-  CS_HIP(hipMemcpyAsync(h, b->p, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-  CS_HIP(hipStreamSynchronize(s));
-  return *h;
-}
 Buf zeros32(int64_t n, hipStream_t s) {
   Buf b = dev_alloc(sizeof(int32_t) * std::max<int64_t>(n, 1), s);
   CS_HIP(hipMemsetAsync(b->p, 0, sizeof(int32_t) * std::max<int64_t>(n, 1), s));

@@ -11,6 +11,8 @@
 // big-endian prefix with a full-compare tie break).
 #include <hip/hip_runtime.h>
 
+#include <optional>
+
 #include "cs_internal.h"
 #include "device_utils.h"
 
@@ -507,21 +509,317 @@ __global__ void k_remap(const int32_t* __restrict__ codes, int64_t n, const int3
   out[i] = v < 0 ? v : table[v];
 }
 
-template <class T>
-T read_back(const void* d, hipStream_t s) {
-  T* host = (T*)pinned_scratch(sizeof(T));
-  CS_HIP(hipMemcpyAsync(host, d, sizeof(T), hipMemcpyDeviceToHost, s));
+// ---- the host path: category_build (at the end) and its steps, in the order it takes them ----------------------------
+
+// The hash table of one build and what the insert pass leaves beside it.
+struct CatTable {
+  // int32 a row: the slot that holds the row's key, -1 for a null row.  Slot ids are int32 here and in rank_of_slot (a
+  // negative id means "null row"): a table for all-distinct rows beyond 2^30 rows would need ids from 2^31 on -- such a
+  // column is refused when (and only when) it needs that table (next_capacity).
+  Buf slot_of_row;
+  Buf flags;  // two ints the insert pass sets: [0] a row is null, [1] overflow: 1 a probe run beyond the limit, 2 a key the entry cannot name
+  Buf table;  // `cap` slots of `sw` words, all ones = empty; from distinct_slots on the dense copy, one word a slot
+  // Slots, a power of two.  Most columns have far fewer distinct keys than rows, and a table that stays in the caches
+  // makes every probe and every later pass over it cheap: the first table has 4M slots (first_capacity), and only when a
+  // probe run gets long is there a retry with a larger one -- at the most `full`, with room for all-distinct rows.
+  int64_t cap = 0;
+  int sw = 1;             // words per slot: 4 = the key's first bytes inside the slot (k_cat_insert; tables of up to 2^24 slots)
+  bool has_null = false;  // the host's copy of flags[0] after the last pass over all rows
+};
+// One launch of k_cat_insert: a thread each for `threads` rows, `stride` apart; `count` is the kernel's (-1: every row).
+struct InsertPass {
+  int64_t threads, stride, count;
+  int probe_limit;  // a longer probe run sets the overflow flag and ends the row
+  int dbg;          // CS_CAT_DEBUG (measurement only)
+  bool timed;       // under the `k_cat_insert` ProfScope
+};
+struct InsertFlags {
+  bool has_null;
+  int overflow;
+};
+constexpr int64_t kSampleRows = 1 << 21;  // (that many rows fit the small table whatever they hold)
+
+// The one place k_cat_insert is launched from: table and flags cleared, then the pass.
+void insert_rows(const ColView& in, const CatTable& t, const InsertPass& p, hipStream_t s) {
+  CS_HIP(hipMemsetAsync(t.table->p, 0xFF, sizeof(Entry) * t.cap * t.sw, s));
+  CS_HIP(hipMemsetAsync(t.flags->p, 0, 2 * sizeof(int), s));
+  std::optional<ProfScope> ps;
+  if (p.timed) ps.emplace("k_cat_insert", s);
+  hipLaunchKernelGGL(k_cat_insert, dim3(blocks_for(p.threads)), dim3(kBlock), 0, s, in, ptr<Entry>(t.table), (uint32_t)(t.cap - 1),
+                     ptr<int32_t>(t.slot_of_row), ptr<int>(t.flags), ptr<int>(t.flags) + 1, p.probe_limit, p.dbg, t.sw, p.stride, p.count);
+}
+// Both flags of the pass, once it has run (waits for `s`).  By value: the pinned scratch is the next reader's too.
+InsertFlags read_insert_flags(const CatTable& t, hipStream_t s) {
+  int* h = (int*)pinned_scratch(2 * sizeof(int));
+  CS_HIP(hipMemcpyAsync(h, t.flags->p, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
   CS_HIP(hipStreamSynchronize(s));
-  return *host;
+  return InsertFlags{h[0] != 0, h[1]};
+}
+
+// ---- the capacity rule: host functions of numbers ----
+// the table with room for all-distinct rows: no probe limit applies to it, nothing is retried after it
+int64_t full_capacity(int64_t rows) {
+  int64_t full = 256;
+  while (full < 2 * rows) full <<= 1;
+  return full;
+}
+// (slot ids are int32: a table of 2^31 slots or more cannot be addressed)
+bool out_of_range(int64_t full) { return full > ((int64_t)1 << 31); }
+int64_t first_capacity(int64_t full) {
+  int first_log2 = 22;
+  if (const char* e = cs::cfg("CS_CAT_FIRST_LOG2")) first_log2 = std::max(4, std::min(30, atoi(e)));  // tests: force retries
+  return std::min<int64_t>(full, cs::cfg("CS_CAT_FULL_TABLE") && !out_of_range(full) ? full : (int64_t)1 << first_log2);
+}
+int slot_words(int64_t cap) { return cap <= ((int64_t)1 << 24) && !cs::cfg("CS_CAT_PLAIN_SLOTS") ? 4 : 1; }
+// After a table of `cap` slots overflowed: 16 times as many, or what the sample asks for when that is more (`share`: the
+// sample's share of distinct keys, negative without a sample; 2.5 slots a distinct key expected), at the most `full`.
+int64_t next_capacity(int64_t cap, int64_t full, int64_t rows, double share) {
+  int64_t next = std::min<int64_t>(full, cap * 16);
+  if (share >= 0) {
+    int64_t want = 256;
+    while (want < (int64_t)(2.5 * share * (double)rows)) want <<= 1;
+    next = std::min<int64_t>(full, std::max<int64_t>(next, want));
+  }
+  if (next == full && out_of_range(full)) fail(CS_ERR_RANGE, "category: more than 2^30 rows with more distinct keys than a 2^31-slot table holds");
+  // slot ids travel as int32 (negative = null row): a table of 2^31 slots or more cannot be addressed
+  if (next > ((int64_t)1 << 30)) fail(CS_ERR_RANGE, "category: more than 2^29 rows with mostly distinct keys in one column");
+  return next;
+}
+// The small table overflowed.  How many distinct keys is this?  A sample of rows taken at a fixed stride across the
+// WHOLE column (the first rows alone say nothing about a column sorted or clustered by key) gives the share of
+// distinct keys among that many rows -- for a shuffled column an upper bound of the column's share (it only falls as
+// more rows come), in general a heuristic: the table is sized from it instead of growing 16-fold per lost pass over
+// all rows (K = 0.5 N: the 64M-slot attempt ran to 90 % before it gave up), and a table that still turns out too
+// small grows as before.  The sample goes into the table that overflowed (no probe limit: kSampleRows fit it); the slot
+// ids it writes are overwritten by the next pass over all rows.
+double sampled_share(const ColView& in, const CatTable& t, int64_t rows, hipStream_t s) {
+  // (a stride rounded UP, so that the sample spans the whole column -- rounded down it stopped short of the column's end,
+  // by almost half of it when the column has just under 2 x kSampleRows rows)
+  const int64_t sample_stride = (rows + kSampleRows - 1) / kSampleRows, sample_rows = (rows + sample_stride - 1) / sample_stride;
+  insert_rows(in, t, InsertPass{sample_rows, sample_stride, sample_rows, 0x7fffffff, 0, false}, s);
+  Buf occ = dev_alloc(sizeof(int32_t) * t.cap, s);
+  hipLaunchKernelGGL(k_cat_flags, dim3(blocks_for(t.cap)), dim3(kBlock), 0, s, ptr<const Entry>(t.table), t.cap, t.sw, ptr<int32_t>(occ), (Entry*)nullptr);
+  Buf occ_pos = dev_alloc(sizeof(int64_t) * (t.cap + 1), s);
+  const int64_t distinct = offsets_from_lengths(ptr<int32_t>(occ), t.cap, ptr<int64_t>(occ_pos), s);
+  return (double)distinct / (double)sample_rows;
+}
+// Every row in a table that holds the column's distinct keys: insert, and after an overflow again in a larger table.
+CatTable fill_table(const ColView& in, int64_t rows, hipStream_t s) {
+  const int64_t full = full_capacity(rows);
+  CatTable t;
+  t.slot_of_row = dev_alloc(sizeof(int32_t) * rows, s);
+  t.flags = dev_alloc(2 * sizeof(int), s);
+  t.cap = first_capacity(full);
+  bool sampled = cs::cfg("CS_CAT_NO_SAMPLE") != nullptr;
+  for (;;) {
+    t.sw = slot_words(t.cap);
+    t.table = dev_alloc(sizeof(Entry) * t.cap * t.sw, s);
+    insert_rows(in, t, InsertPass{rows, 1, -1, t.cap == full ? 0x7fffffff : kProbeLimit, cs::cfg_int("CS_CAT_DEBUG", 0), true}, s);
+    const InsertFlags f = read_insert_flags(t, s);
+    if (f.overflow & 2) fail(CS_ERR_RANGE, "category: a key of 16 MiB or more");
+    t.has_null = f.has_null;
+    if (t.cap == full || !f.overflow) return t;
+    double share = -1;
+    if (!sampled && rows > kSampleRows && t.cap >= 2 * kSampleRows) {
+      sampled = true;
+      share = sampled_share(in, t, rows, s);
+    }
+    t.cap = next_capacity(t.cap, full, rows, share);
+  }
+}
+
+// Which slots hold a key: flags, their scan and the count.  32-byte slots: the slot words move to a dense array in the same
+// pass, and `t.table` is that array from here on -- every later kernel reads it.
+struct Distinct {
+  Buf flags;  // int32 a slot: 1 when it holds a key
+  Buf pos;    // int64: exclusive scan of flags, a key's place among the records
+  int64_t uniq = 0;
+};
+Distinct distinct_slots(CatTable& t, hipStream_t s) {
+  Distinct d;
+  d.flags = dev_alloc(sizeof(int32_t) * t.cap, s);
+  {
+    Buf dense = t.sw == 1 ? t.table : dev_alloc(sizeof(Entry) * t.cap, s);
+    hipLaunchKernelGGL(k_cat_flags, dim3(blocks_for(t.cap)), dim3(kBlock), 0, s, ptr<const Entry>(t.table), t.cap, t.sw, ptr<int32_t>(d.flags),
+                       t.sw == 1 ? (Entry*)nullptr : ptr<Entry>(dense));
+    t.table = dense;
+  }
+  d.pos = dev_alloc(sizeof(int64_t) * (t.cap + 1), s);
+  d.uniq = offsets_from_lengths(ptr<int32_t>(d.flags), t.cap, ptr<int64_t>(d.pos), s);
+  return d;
+}
+
+// ---- distinct keys in order ----
+// The compare network over `padded` records (a power of two): stages that fit a chunk run in LDS in one launch; a later
+// stage takes its long-distance steps one launch each and finishes in LDS.
+void sort_network(const ColView& in, const Entry* table, uint64_t* pfx, int32_t* itm, int64_t padded, hipStream_t s) {
+  const int64_t chunk = std::min<int64_t>(padded, kSortChunk);
+  const unsigned nchunks = (unsigned)(padded / chunk);
+  if (padded >= 2) hipLaunchKernelGGL(k_bitonic_local, dim3(nchunks), dim3(256), 0, s, in, table, pfx, itm, padded, (int64_t)2, chunk);
+  for (int64_t k = 2 * chunk; k <= padded; k <<= 1) {
+    for (int64_t j = k >> 1; j >= chunk; j >>= 1)
+      hipLaunchKernelGGL(k_bitonic_step, dim3(blocks_for(padded)), dim3(kBlock), 0, s, in, table, pfx, itm, padded, j, k);
+    hipLaunchKernelGGL(k_bitonic_local, dim3(nchunks), dim3(256), 0, s, in, table, pfx, itm, padded, k, k);
+  }
+}
+// The records that share their prefix with a neighbour of the prefix-sorted sequence, in sequence order.
+struct Tied {
+  int64_t n = 0, padded = 1;  // their number; the next power of two (the network's padding)
+  Buf prefix, item;           // `padded` each: the tied records, then padding that sorts last
+  Buf where;                  // int32 each: the record's position in the full sequence
+};
+// (a handful of ties: one launch of the compare network in LDS)
+void ties_by_network(const ColView& in, const Entry* table, const Tied& t, int32_t* item, hipStream_t s) {
+  sort_network(in, table, ptr<uint64_t>(t.prefix), ptr<int32_t>(t.item), t.padded, s);
+  hipLaunchKernelGGL(k_tie_scatter, dim3(blocks_for(t.n)), dim3(kBlock), 0, s, ptr<const int32_t>(t.item), ptr<const int32_t>(t.where), t.n, item);
+}
+// What the rounds on the next seven key bytes work in (see above k_tie_groups0); every array has a place for each tied record.
+struct TieRounds {
+  Buf gid;     // int32: the record's group -- the records equal so far -- numbered along the sequence
+  Buf head;    // int32: 1 when the record begins a group
+  Buf hpos;    // int64: exclusive scan of head
+  Buf key1;    // uint64: the record's chunk key (next seven key bytes, their count); sorted with perm
+  Buf key2;    // uint64: the chunk keys in the round's new order
+  Buf gk;      // uint64: the group of perm's record, the key of the second (stable) sort
+  Buf perm;    // int32: the records by chunk
+  Buf perm2;   // int32: places in perm by (group, chunk)
+  Buf titem2;  // int32: the tied items in the round's new order
+  Buf gid2;    // int32: their groups in that order
+  Buf where2;  // int32: the positions array that is not being read (the compaction writes it)
+  Buf flags2;  // int32: 1 when the record still ties with a neighbour
+  Buf fpos;    // int64: exclusive scan of flags2
+  Buf more;    // one int: a record that still ties has key bytes left
+};
+void ties_by_rounds(const ColView& in, const Entry* table, const Tied& t, int32_t* item, hipStream_t s) {
+  int64_t nt = t.n;
+  TieRounds r;
+  r.gid = dev_alloc(sizeof(int32_t) * nt, s);
+  r.head = dev_alloc(sizeof(int32_t) * nt, s);
+  r.hpos = dev_alloc(sizeof(int64_t) * (nt + 1), s);
+  hipLaunchKernelGGL(k_tie_groups0, dim3(blocks_for(nt)), dim3(kBlock), 0, s, ptr<const uint64_t>(t.prefix), nt, ptr<int32_t>(r.head));
+  offsets_from_lengths(ptr<int32_t>(r.head), nt, ptr<int64_t>(r.hpos), s);
+  hipLaunchKernelGGL(k_tie_gid, dim3(blocks_for(nt)), dim3(kBlock), 0, s, ptr<const int32_t>(r.head), ptr<const int64_t>(r.hpos), nt, ptr<int32_t>(r.gid));
+  r.key1 = dev_alloc(sizeof(uint64_t) * nt, s);
+  r.key2 = dev_alloc(sizeof(uint64_t) * nt, s);
+  r.gk = dev_alloc(sizeof(uint64_t) * nt, s);
+  r.perm = dev_alloc(sizeof(int32_t) * nt, s);
+  r.perm2 = dev_alloc(sizeof(int32_t) * nt, s);
+  r.titem2 = dev_alloc(sizeof(int32_t) * nt, s);
+  r.gid2 = dev_alloc(sizeof(int32_t) * nt, s);
+  r.where2 = dev_alloc(sizeof(int32_t) * nt, s);
+  r.flags2 = dev_alloc(sizeof(int32_t) * nt, s);
+  r.fpos = dev_alloc(sizeof(int64_t) * (nt + 1), s);
+  r.more = dev_alloc(sizeof(int), s);
+  // a round reads the records' positions from one array; the compaction writes the survivors' into the other
+  int32_t* where_now = ptr<int32_t>(t.where);
+  int32_t* where_next = ptr<int32_t>(r.where2);
+  for (int depth = 8; nt > 0; depth += 7) {
+    const unsigned g = blocks_for(nt);
+    hipLaunchKernelGGL(k_tie_keys, dim3(g), dim3(kBlock), 0, s, in, table, ptr<const int32_t>(t.item), nt, depth, ptr<uint64_t>(r.key1), ptr<int32_t>(r.perm));
+    radix_sort_pairs64(ptr<uint64_t>(r.key1), ptr<int32_t>(r.perm), nt, s);
+    hipLaunchKernelGGL(k_tie_group_keys, dim3(g), dim3(kBlock), 0, s, ptr<const int32_t>(r.gid), ptr<const int32_t>(r.perm), nt, ptr<uint64_t>(r.gk),
+                       ptr<int32_t>(r.perm2));
+    radix_sort_pairs64(ptr<uint64_t>(r.gk), ptr<int32_t>(r.perm2), nt, s);
+    hipLaunchKernelGGL(k_tie_apply, dim3(g), dim3(kBlock), 0, s, ptr<const int32_t>(t.item), ptr<const int32_t>(r.gid), ptr<const uint64_t>(r.key1),
+                       ptr<const int32_t>(r.perm), ptr<const int32_t>(r.perm2), where_now, nt, ptr<int32_t>(r.titem2), ptr<int32_t>(r.gid2),
+                       ptr<uint64_t>(r.key2), item);
+    CS_HIP(hipMemsetAsync(r.more->p, 0, sizeof(int), s));
+    hipLaunchKernelGGL(k_tie_flags2, dim3(g), dim3(kBlock), 0, s, ptr<const int32_t>(r.gid2), ptr<const uint64_t>(r.key2), nt, ptr<int32_t>(r.flags2),
+                       ptr<int32_t>(r.head), ptr<int>(r.more));
+    const int64_t left = offsets_from_lengths(ptr<int32_t>(r.flags2), nt, ptr<int64_t>(r.fpos), s);
+    if (left == 0 || !read_back<int>(r.more->p, s)) break;  // (what still ties has no bytes left: equal keys, in input order)
+    offsets_from_lengths(ptr<int32_t>(r.head), nt, ptr<int64_t>(r.hpos), s);
+    hipLaunchKernelGGL(k_tie_compact, dim3(g), dim3(kBlock), 0, s, ptr<const int32_t>(r.flags2), ptr<const int64_t>(r.fpos), ptr<const int32_t>(r.titem2),
+                       where_now, ptr<const int32_t>(r.head), ptr<const int64_t>(r.hpos), nt, ptr<int32_t>(t.item), where_next, ptr<int32_t>(r.gid));
+    std::swap(where_now, where_next);  // the survivors' positions are the next round's
+    nt = left;
+  }
+}
+// After the radix sort on the prefix: records that share a prefix with a neighbour keep their SET of positions; the order
+// among them comes from full compares -- those records alone go through the compare network (a handful for ordinary
+// columns) or, when there are many, through the rounds.
+void break_ties(const ColView& in, const Entry* table, const uint64_t* prefix, int32_t* item, int64_t uniq, hipStream_t s) {
+  Buf tflags = dev_alloc(sizeof(int32_t) * uniq, s);
+  hipLaunchKernelGGL(k_tie_flags, dim3(blocks_for(uniq)), dim3(kBlock), 0, s, prefix, uniq, ptr<int32_t>(tflags));
+  Buf tpos = dev_alloc(sizeof(int64_t) * (uniq + 1), s);
+  Tied t;
+  t.n = offsets_from_lengths(ptr<int32_t>(tflags), uniq, ptr<int64_t>(tpos), s);
+  if (t.n == 0) return;
+  while (t.padded < t.n) t.padded <<= 1;
+  t.prefix = dev_alloc(sizeof(uint64_t) * t.padded, s);
+  t.item = dev_alloc(sizeof(int32_t) * t.padded, s);
+  t.where = dev_alloc(sizeof(int32_t) * t.n, s);
+  hipLaunchKernelGGL(k_tie_gather, dim3(blocks_for(std::max(uniq, t.padded))), dim3(kBlock), 0, s, prefix, (const int32_t*)item, ptr<const int32_t>(tflags),
+                     ptr<const int64_t>(tpos), uniq, t.n, t.padded, ptr<uint64_t>(t.prefix), ptr<int32_t>(t.item), ptr<int32_t>(t.where));
+  if (t.n <= kSortChunk || cs::cfg("CS_CAT_TIE_NETWORK"))
+    ties_by_network(in, table, t, item, s);
+  else
+    ties_by_rounds(in, table, t, item, s);
+  CS_HIP(hipStreamSynchronize(s));  // (the tie buffers' lifetime)
+}
+// The sort records of the distinct keys -- prefix[i] = the key's first 8 bytes big-endian, item[i] = its slot -- in key order.
+struct Records {
+  Buf prefix, item;
+};
+// The records are radix-sorted on the prefix -- linear in the key count, where the compare network this replaces took
+// log^2 K steps over the padded records and compared whole keys through the table on every tie (K = 100M: hundreds of
+// global steps) -- and break_ties orders the records with equal prefixes.  (A key set that one LDS chunk holds sorts in a
+// single launch of the compare network: the radix sort's histogram and scan round trips would cost more than they save
+// there.)
+Records sort_records(const ColView& in, const CatTable& t, const Distinct& d, hipStream_t s) {
+  const int64_t uniq = d.uniq;
+  const bool use_radix = !cs::cfg("CS_CAT_BITONIC") && (uniq > kSortChunk || cs::cfg("CS_CAT_RADIX"));
+  int64_t padded = 1;
+  while (padded < uniq) padded <<= 1;
+  if (use_radix) padded = std::max<int64_t>(uniq, 1);
+  Records r;
+  r.prefix = dev_alloc(sizeof(uint64_t) * padded, s);
+  r.item = dev_alloc(sizeof(int32_t) * padded, s);
+  hipLaunchKernelGGL(k_cat_records, dim3(blocks_for(std::max(t.cap, padded))), dim3(kBlock), 0, s, in, ptr<const Entry>(t.table),
+                     ptr<const int32_t>(d.flags), ptr<const int64_t>(d.pos), t.cap, padded, uniq, ptr<uint64_t>(r.prefix), ptr<int32_t>(r.item));
+  ProfScope ps("k_cat_sort", s);
+  if (!use_radix) {
+    sort_network(in, ptr<const Entry>(t.table), ptr<uint64_t>(r.prefix), ptr<int32_t>(r.item), padded, s);
+  } else if (uniq > 1) {
+    radix_sort_pairs64(ptr<uint64_t>(r.prefix), ptr<int32_t>(r.item), uniq, s);
+    break_ties(in, ptr<const Entry>(t.table), ptr<const uint64_t>(r.prefix), ptr<int32_t>(r.item), uniq, s);
+  }
+  return r;
+}
+
+// ---- values and keys ----
+// rank_of_slot[slot] = the index of the slot's key among the keys (`shift`: 1 when key 0 is the null key)
+Buf slot_ranks(const CatTable& t, const Records& r, int64_t uniq, int shift, hipStream_t s) {
+  Buf rank_of_slot = dev_alloc(sizeof(int32_t) * t.cap, s);
+  if (uniq)
+    hipLaunchKernelGGL(k_cat_ranks, dim3(blocks_for(uniq)), dim3(kBlock), 0, s, ptr<const int32_t>(r.item), uniq, shift, ptr<int32_t>(rank_of_slot));
+  return rank_of_slot;
+}
+Buf row_values(const CatTable& t, const Buf& rank_of_slot, int64_t rows, hipStream_t s) {
+  Buf values = dev_alloc(sizeof(int32_t) * rows, s);
+  ProfScope ps("k_cat_values", s);
+  hipLaunchKernelGGL(k_cat_values, dim3(blocks_for((rows + 3) / 4)), dim3(kBlock), 0, s, ptr<const int32_t>(t.slot_of_row),
+                     ptr<const int32_t>(rank_of_slot), rows, ptr<int32_t>(values));
+  return values;
+}
+// the keys in order as a column (waits for `s`: everything the build launched has run when it returns)
+std::unique_ptr<cs_column> keys_column(const ColView& in, const CatTable& t, const Records& r, int64_t uniq, int shift, hipStream_t s) {
+  const int64_t nkeys = uniq + shift;
+  Built b(nkeys, shift ? Nulls::separate : Nulls::none, s);  // (the null key, when there is one, is key 0)
+  b.col->null_count = shift;
+  Buf lens = dev_alloc(sizeof(int32_t) * nkeys, s);
+  hipLaunchKernelGGL(k_key_sizes, dim3(blocks_for(nkeys)), dim3(kBlock), 0, s, in, ptr<const Entry>(t.table), ptr<const int32_t>(r.item), nkeys, shift,
+                     ptr<int32_t>(lens));
+  b.scan(ptr<int32_t>(lens));
+  b.alloc_chars();
+  hipLaunchKernelGGL(k_key_copy, dim3(blocks_for(nkeys)), dim3(kBlock), 0, s, in, ptr<const Entry>(t.table), ptr<const int32_t>(r.item), nkeys, shift, b.off,
+                     b.chars);
+  CS_HIP(hipStreamSynchronize(s));
+  return std::move(b.col);
 }
 
 }  // namespace
-namespace cs {
-cs_category* category_build(const cs_column* col, hipStream_t s);
-}
-namespace {
-cs_category* build(const cs_column* col, hipStream_t s) { return cs::category_build(col, s); }
-}  // namespace
+
 cs_category* cs::category_build(const cs_column* col, hipStream_t s) {
   auto cat = std::make_unique<cs_category>();
   const int64_t rows = col->rows;
@@ -532,199 +830,14 @@ cs_category* cs::category_build(const cs_column* col, hipStream_t s) {
     return cat.release();
   }
   if (rows >= (1LL << 31) - 1) fail(CS_ERR_RANGE, "category: more than 2^31 rows in one column");
-  // Table capacity: most columns have far fewer distinct keys than rows, and a table that stays
-  // in the caches makes every probe and every later pass over it cheap -- start with 4M slots
-  // and retry with room for all-distinct rows only if a probe run gets long.
-  int64_t full = 256;
-  while (full < 2 * rows) full <<= 1;
-  // slot ids are int32 (slot_of_row, rank_of_slot; a negative id means "null row"): a table for all-distinct rows
-  // beyond 2^30 rows would need ids from 2^31 on -- such a column is refused when (and only when) it needs that table
-  const bool full_out_of_range = full > ((int64_t)1 << 31);
-  ColView in = view_of(col);
-  Buf slot_of_row = dev_alloc(sizeof(int32_t) * rows, s);
-  Buf flags_d = dev_alloc(2 * sizeof(int), s);  // [0] has_null, [1] overflow
-  Buf table;
-  int first_log2 = 22;
-  if (const char* e = cs::cfg("CS_CAT_FIRST_LOG2")) first_log2 = std::max(4, std::min(30, atoi(e)));  // tests: force retries
-  int64_t cap = std::min<int64_t>(full, cs::cfg("CS_CAT_FULL_TABLE") && !full_out_of_range ? full : (int64_t)1 << first_log2);
-  constexpr int64_t kSampleRows = 1 << 21;  // (that many rows fit the small table whatever they hold)
-  bool sampled = cs::cfg("CS_CAT_NO_SAMPLE") != nullptr;
-  int sw = 1;  // words per slot: 4 = the key's first bytes inside the slot (k_cat_insert)
-  for (;;) {
-    sw = cap <= ((int64_t)1 << 24) && !cs::cfg("CS_CAT_PLAIN_SLOTS") ? 4 : 1;
-    table = dev_alloc(sizeof(Entry) * cap * sw, s);
-    CS_HIP(hipMemsetAsync(table->p, 0xFF, sizeof(Entry) * cap * sw, s));
-    CS_HIP(hipMemsetAsync(flags_d->p, 0, 2 * sizeof(int), s));
-    {
-      ProfScope ps("k_cat_insert", s);
-      const int limit = cap == full ? 0x7fffffff : kProbeLimit;
-      const int dbg = cs::cfg_int("CS_CAT_DEBUG", 0);
-      hipLaunchKernelGGL(k_cat_insert, dim3(blocks_for(rows)), dim3(kBlock), 0, s, in, ptr<Entry>(table),
-                         (uint32_t)(cap - 1), ptr<int32_t>(slot_of_row), ptr<int>(flags_d), ptr<int>(flags_d) + 1, limit,
-                         dbg, sw);
-    }
-    int* h = (int*)pinned_scratch(2 * sizeof(int));
-    CS_HIP(hipMemcpyAsync(h, flags_d->p, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
-    CS_HIP(hipStreamSynchronize(s));
-    if (h[1] & 2) fail(CS_ERR_RANGE, "category: a key of 16 MiB or more");
-    if (cap == full || !h[1]) break;  // (room for all-distinct rows: no limit applied, nothing to retry)
-    int64_t next_cap = std::min<int64_t>(full, cap * 16);
-    if (!sampled && rows > kSampleRows && cap >= 2 * kSampleRows) {
-      // The small table overflowed.  How many distinct keys is this?  A sample of rows taken at a fixed stride across the
-      // WHOLE column (the first rows alone say nothing about a column sorted or clustered by key) gives the share of
-      // distinct keys among that many rows -- for a shuffled column an upper bound of the column's share (it only falls as
-      // more rows come), in general a heuristic: the table is sized from it instead of growing 16-fold per lost pass over
-      // all rows (K = 0.5 N: the 64M-slot attempt ran to 90 % before it gave up), and a table that still turns out too
-      // small grows as before.
-      sampled = true;
-      CS_HIP(hipMemsetAsync(table->p, 0xFF, sizeof(Entry) * cap * sw, s));
-      CS_HIP(hipMemsetAsync(flags_d->p, 0, 2 * sizeof(int), s));
-      // (a stride rounded UP, so that the sample spans the whole column -- rounded down it stopped short of the column's end,
-      // by almost half of it when the column has just under 2 x kSampleRows rows)
-      const int64_t sample_stride = (rows + kSampleRows - 1) / kSampleRows, sample_rows = (rows + sample_stride - 1) / sample_stride;
-      hipLaunchKernelGGL(k_cat_insert, dim3(blocks_for(sample_rows)), dim3(kBlock), 0, s, in, ptr<Entry>(table), (uint32_t)(cap - 1),
-                         ptr<int32_t>(slot_of_row), ptr<int>(flags_d), ptr<int>(flags_d) + 1, 0x7fffffff, 0, sw, sample_stride, sample_rows);
-      Buf occ = dev_alloc(sizeof(int32_t) * cap, s);
-      hipLaunchKernelGGL(k_cat_flags, dim3(blocks_for(cap)), dim3(kBlock), 0, s, ptr<const Entry>(table), cap, sw, ptr<int32_t>(occ), (Entry*)nullptr);
-      Buf occ_pos = dev_alloc(sizeof(int64_t) * (cap + 1), s);
-      const int64_t distinct = offsets_from_lengths(ptr<int32_t>(occ), cap, ptr<int64_t>(occ_pos), s);
-      const double share = (double)distinct / (double)sample_rows;
-      int64_t want = 256;
-      while (want < (int64_t)(2.5 * share * (double)rows)) want <<= 1;
-      next_cap = std::min<int64_t>(full, std::max<int64_t>(next_cap, want));
-    }
-    cap = next_cap;
-    if (cap == full && full_out_of_range) fail(CS_ERR_RANGE, "category: more than 2^30 rows with more distinct keys than a 2^31-slot table holds");
-    // slot ids travel as int32 (negative = null row): a table of 2^31 slots or more cannot be addressed
-    if (cap > ((int64_t)1 << 30)) fail(CS_ERR_RANGE, "category: more than 2^29 rows with mostly distinct keys in one column");
-  }
-  Buf has_null_d = flags_d;
-  // compact the occupied slots
-  Buf flags = dev_alloc(sizeof(int32_t) * cap, s);
-  {
-    // (32-byte slots: the slot words move to a dense array in the same pass -- every later kernel reads that)
-    Buf dense = sw == 1 ? table : dev_alloc(sizeof(Entry) * cap, s);
-    hipLaunchKernelGGL(k_cat_flags, dim3(blocks_for(cap)), dim3(kBlock), 0, s, ptr<const Entry>(table), cap, sw, ptr<int32_t>(flags),
-                       sw == 1 ? (Entry*)nullptr : ptr<Entry>(dense));
-    table = dense;
-  }
-  Buf pos = dev_alloc(sizeof(int64_t) * (cap + 1), s);
-  const int64_t uniq = offsets_from_lengths(ptr<int32_t>(flags), cap, ptr<int64_t>(pos), s);
-  const int shift = read_back<int>(has_null_d->p, s) ? 1 : 0;
-  // Distinct keys in order.  The records (8-byte big-endian prefix, slot) are radix-sorted on the prefix -- linear in the
-  // key count, where the bitonic network this replaces took log^2 K steps over the padded records and compared whole
-  // keys through the table on every tie (K = 100M: hundreds of global steps).  Keys that share a prefix with a
-  // neighbour keep their set of positions; the order among them comes from full compares: those records alone go
-  // through the compare network (a handful for ordinary columns; every one only when all keys share 8 bytes).
-  auto bitonic = [&](uint64_t* pfx, int32_t* itm, int64_t padded) {
-    // stages that fit a chunk run in LDS in one launch; a later stage takes its long-distance
-    // steps one launch each and finishes in LDS
-    const int64_t chunk = std::min<int64_t>(padded, kSortChunk);
-    const unsigned nchunks = (unsigned)(padded / chunk);
-    if (padded >= 2)
-      hipLaunchKernelGGL(k_bitonic_local, dim3(nchunks), dim3(256), 0, s, in, ptr<const Entry>(table), pfx, itm, padded, (int64_t)2, chunk);
-    for (int64_t k = 2 * chunk; k <= padded; k <<= 1) {
-      for (int64_t j = k >> 1; j >= chunk; j >>= 1)
-        hipLaunchKernelGGL(k_bitonic_step, dim3(blocks_for(padded)), dim3(kBlock), 0, s, in, ptr<const Entry>(table), pfx, itm, padded, j, k);
-      hipLaunchKernelGGL(k_bitonic_local, dim3(nchunks), dim3(256), 0, s, in, ptr<const Entry>(table), pfx, itm, padded, k, k);
-    }
-  };
-  // (a key set that one LDS chunk holds sorts in a single launch of the compare network: the radix sort's histogram and
-  // scan round trips would cost more than they save there)
-  const bool use_radix = !cs::cfg("CS_CAT_BITONIC") && (uniq > kSortChunk || cs::cfg("CS_CAT_RADIX"));
-  int64_t padded = 1;
-  while (padded < uniq) padded <<= 1;
-  if (use_radix) padded = std::max<int64_t>(uniq, 1);
-  Buf prefix = dev_alloc(sizeof(uint64_t) * padded, s);
-  Buf item = dev_alloc(sizeof(int32_t) * padded, s);
-  hipLaunchKernelGGL(k_cat_records, dim3(blocks_for(std::max(cap, padded))), dim3(kBlock), 0, s, in,
-                     ptr<const Entry>(table), ptr<const int32_t>(flags), ptr<const int64_t>(pos), cap, padded,
-                     uniq, ptr<uint64_t>(prefix), ptr<int32_t>(item));
-  {
-    ProfScope ps("k_cat_sort", s);
-    if (!use_radix) {
-      bitonic(ptr<uint64_t>(prefix), ptr<int32_t>(item), padded);
-    } else if (uniq > 1) {
-      radix_sort_pairs64(ptr<uint64_t>(prefix), ptr<int32_t>(item), uniq, s);
-      Buf tflags = dev_alloc(sizeof(int32_t) * uniq, s);
-      hipLaunchKernelGGL(k_tie_flags, dim3(blocks_for(uniq)), dim3(kBlock), 0, s, ptr<const uint64_t>(prefix), uniq, ptr<int32_t>(tflags));
-      Buf tpos = dev_alloc(sizeof(int64_t) * (uniq + 1), s);
-      const int64_t tied = offsets_from_lengths(ptr<int32_t>(tflags), uniq, ptr<int64_t>(tpos), s);
-      if (tied > 0) {
-        int64_t tpad = 1;
-        while (tpad < tied) tpad <<= 1;
-        Buf tprefix = dev_alloc(sizeof(uint64_t) * tpad, s), titem = dev_alloc(sizeof(int32_t) * tpad, s), where = dev_alloc(sizeof(int32_t) * tied, s);
-        hipLaunchKernelGGL(k_tie_gather, dim3(blocks_for(std::max(uniq, tpad))), dim3(kBlock), 0, s, ptr<const uint64_t>(prefix), ptr<const int32_t>(item),
-                           ptr<const int32_t>(tflags), ptr<const int64_t>(tpos), uniq, tied, tpad, ptr<uint64_t>(tprefix), ptr<int32_t>(titem),
-                           ptr<int32_t>(where));
-        if (tied <= kSortChunk || cs::cfg("CS_CAT_TIE_NETWORK")) {
-          // (a handful of ties: one launch of the compare network in LDS)
-          bitonic(ptr<uint64_t>(tprefix), ptr<int32_t>(titem), tpad);
-          hipLaunchKernelGGL(k_tie_scatter, dim3(blocks_for(tied)), dim3(kBlock), 0, s, ptr<const int32_t>(titem), ptr<const int32_t>(where), tied,
-                             ptr<int32_t>(item));
-        } else {
-          // rounds on the next seven key bytes (see above)
-          int64_t nt = tied;
-          Buf gid = dev_alloc(sizeof(int32_t) * nt, s), head = dev_alloc(sizeof(int32_t) * nt, s), hpos = dev_alloc(sizeof(int64_t) * (nt + 1), s);
-          hipLaunchKernelGGL(k_tie_groups0, dim3(blocks_for(nt)), dim3(kBlock), 0, s, ptr<const uint64_t>(tprefix), nt, ptr<int32_t>(head));
-          offsets_from_lengths(ptr<int32_t>(head), nt, ptr<int64_t>(hpos), s);
-          hipLaunchKernelGGL(k_tie_gid, dim3(blocks_for(nt)), dim3(kBlock), 0, s, ptr<const int32_t>(head), ptr<const int64_t>(hpos), nt, ptr<int32_t>(gid));
-          Buf key1 = dev_alloc(sizeof(uint64_t) * nt, s), key2 = dev_alloc(sizeof(uint64_t) * nt, s), gk = dev_alloc(sizeof(uint64_t) * nt, s);
-          Buf perm = dev_alloc(sizeof(int32_t) * nt, s), perm2 = dev_alloc(sizeof(int32_t) * nt, s);
-          Buf titem2 = dev_alloc(sizeof(int32_t) * nt, s), gid2 = dev_alloc(sizeof(int32_t) * nt, s), where2 = dev_alloc(sizeof(int32_t) * nt, s);
-          Buf flags2 = dev_alloc(sizeof(int32_t) * nt, s), fpos = dev_alloc(sizeof(int64_t) * (nt + 1), s), more_d = dev_alloc(sizeof(int), s);
-          int32_t* cur_where = ptr<int32_t>(where);
-          int32_t* alt_where = ptr<int32_t>(where2);
-          for (int depth = 8; nt > 0; depth += 7) {
-            const unsigned g = blocks_for(nt);
-            hipLaunchKernelGGL(k_tie_keys, dim3(g), dim3(kBlock), 0, s, in, ptr<const Entry>(table), ptr<const int32_t>(titem), nt, depth, ptr<uint64_t>(key1),
-                               ptr<int32_t>(perm));
-            radix_sort_pairs64(ptr<uint64_t>(key1), ptr<int32_t>(perm), nt, s);
-            hipLaunchKernelGGL(k_tie_group_keys, dim3(g), dim3(kBlock), 0, s, ptr<const int32_t>(gid), ptr<const int32_t>(perm), nt, ptr<uint64_t>(gk),
-                               ptr<int32_t>(perm2));
-            radix_sort_pairs64(ptr<uint64_t>(gk), ptr<int32_t>(perm2), nt, s);
-            hipLaunchKernelGGL(k_tie_apply, dim3(g), dim3(kBlock), 0, s, ptr<const int32_t>(titem), ptr<const int32_t>(gid), ptr<const uint64_t>(key1),
-                               ptr<const int32_t>(perm), ptr<const int32_t>(perm2), cur_where, nt, ptr<int32_t>(titem2), ptr<int32_t>(gid2), ptr<uint64_t>(key2),
-                               ptr<int32_t>(item));
-            CS_HIP(hipMemsetAsync(more_d->p, 0, sizeof(int), s));
-            hipLaunchKernelGGL(k_tie_flags2, dim3(g), dim3(kBlock), 0, s, ptr<const int32_t>(gid2), ptr<const uint64_t>(key2), nt, ptr<int32_t>(flags2),
-                               ptr<int32_t>(head), ptr<int>(more_d));
-            const int64_t left = offsets_from_lengths(ptr<int32_t>(flags2), nt, ptr<int64_t>(fpos), s);
-            if (left == 0 || !read_back<int>(more_d->p, s)) break;  // (what still ties has no bytes left: equal keys, in input order)
-            offsets_from_lengths(ptr<int32_t>(head), nt, ptr<int64_t>(hpos), s);
-            hipLaunchKernelGGL(k_tie_compact, dim3(g), dim3(kBlock), 0, s, ptr<const int32_t>(flags2), ptr<const int64_t>(fpos), ptr<const int32_t>(titem2),
-                               cur_where, ptr<const int32_t>(head), ptr<const int64_t>(hpos), nt, ptr<int32_t>(titem), alt_where, ptr<int32_t>(gid));
-            std::swap(cur_where, alt_where);
-            nt = left;
-          }
-        }
-        CS_HIP(hipStreamSynchronize(s));  // (the tie buffers' lifetime)
-      }
-    }
-  }
-  Buf rank_of_slot = dev_alloc(sizeof(int32_t) * cap, s);
-  if (uniq)
-    hipLaunchKernelGGL(k_cat_ranks, dim3(blocks_for(uniq)), dim3(kBlock), 0, s, ptr<const int32_t>(item), uniq,
-                       shift, ptr<int32_t>(rank_of_slot));
-  cat->values = dev_alloc(sizeof(int32_t) * rows, s);
-  {
-    ProfScope ps("k_cat_values", s);
-    hipLaunchKernelGGL(k_cat_values, dim3(blocks_for((rows + 3) / 4)), dim3(kBlock), 0, s, ptr<const int32_t>(slot_of_row),
-                       ptr<const int32_t>(rank_of_slot), rows, ptr<int32_t>(cat->values));
-  }
-  // keys column
-  const int64_t nkeys = uniq + shift;
-  Built b(nkeys, shift ? Nulls::separate : Nulls::none, s);  // (the null key, when there is one, is key 0)
-  b.col->null_count = shift;
-  Buf lens = dev_alloc(sizeof(int32_t) * nkeys, s);
-  hipLaunchKernelGGL(k_key_sizes, dim3(blocks_for(nkeys)), dim3(kBlock), 0, s, in, ptr<const Entry>(table),
-                     ptr<const int32_t>(item), nkeys, shift, ptr<int32_t>(lens));
-  b.scan(ptr<int32_t>(lens));
-  b.alloc_chars();
-  hipLaunchKernelGGL(k_key_copy, dim3(blocks_for(nkeys)), dim3(kBlock), 0, s, in, ptr<const Entry>(table),
-                     ptr<const int32_t>(item), nkeys, shift, b.off, b.chars);
-  CS_HIP(hipStreamSynchronize(s));
-  cat->keys = std::move(b.col);
+  const ColView in = view_of(col);
+  CatTable t = fill_table(in, rows, s);
+  const Distinct d = distinct_slots(t, s);
+  const int shift = t.has_null ? 1 : 0;  // (the null key, when there is one, is key 0)
+  const Records r = sort_records(in, t, d, s);
+  const Buf rank_of_slot = slot_ranks(t, r, d.uniq, shift, s);
+  cat->values = row_values(t, rank_of_slot, rows, s);
+  cat->keys = keys_column(in, t, r, d.uniq, shift, s);
   return cat.release();
 }
 
@@ -735,7 +848,7 @@ int cs_category_build(const cs_column* col, cs_stream stream, cs_category** out)
   return guard([&] {
     if (!col || !out) fail(CS_ERR_INVALID_ARG, "null argument");
     require_device();
-    *out = build(col, S(stream));
+    *out = category_build(col, S(stream));
   });
 }
 
@@ -755,7 +868,7 @@ int cs_category_merge(const cs_category* const* cats, int ncats, cs_stream strea
     std::unique_ptr<cs_column> all_keys(concat_columns(keysets, s));
     // category of the concatenated key sets: its keys are the merged key set and
     // its codes are, per input category, the old-code -> new-code table
-    std::unique_ptr<cs_category> merged(build(all_keys.get(), s));
+    std::unique_ptr<cs_category> merged(category_build(all_keys.get(), s));
     if (all_keys->rows == 0) {  // NVCategory.cu:443-444: no key anywhere -> an empty category, whatever rows there were
       *out = merged.release();
       return;
@@ -804,7 +917,7 @@ int cs_category_merge_gathered(const cs_category* local, const cs_column* const*
     // the category of the concatenated key sets: its keys are the merged key set, its codes the old-code -> new-code
     // tables of the ranks, back to back
     std::unique_ptr<cs_column> all_keys(concat_columns(sets, s));
-    std::unique_ptr<cs_category> merged(build(all_keys.get(), s));
+    std::unique_ptr<cs_category> merged(category_build(all_keys.get(), s));
     if (local->rows)
       hipLaunchKernelGGL(k_remap, dim3(blocks_for(local->rows)), dim3(kBlock), 0, s, ptr<const int32_t>(local->values), local->rows,
                          ptr<const int32_t>(merged->values) + before, values);

@@ -149,7 +149,7 @@ int cs_category_gather(const cs_category* cat, const int32_t* pos, int64_t n, in
     if (n) {
       Buf used = zeros32(nk, s), bad = zeros32(1, s);
       hipLaunchKernelGGL(k_mark_used, dim3(blocks_for(n)), dim3(kBlock), 0, s, p.d, n, nk, -1, ptr<int32_t>(used), ptr<unsigned>(bad));
-      if (read_flag(bad, s)) fail(CS_ERR_RANGE, "gather: position out of range");
+      if (read_back<unsigned>(bad->p, s)) fail(CS_ERR_RANGE, "gather: position out of range");
     }
     auto res = std::make_unique<cs_category>();
     res->rows = n;
@@ -170,7 +170,7 @@ int cs_category_gather_and_remap(const cs_category* cat, const int32_t* pos, int
     const int64_t nk = cat->keys->rows;
     Buf used = zeros32(nk, s), bad = zeros32(1, s);
     if (n) hipLaunchKernelGGL(k_mark_used, dim3(blocks_for(n)), dim3(kBlock), 0, s, p.d, n, nk, 0, ptr<int32_t>(used), ptr<unsigned>(bad));
-    if (n && read_flag(bad, s)) fail(CS_ERR_RANGE, "gather_and_remap: position out of range");
+    if (n && read_back<unsigned>(bad->p, s)) fail(CS_ERR_RANGE, "gather_and_remap: position out of range");
     Compacted c = compact(ptr<const int32_t>(used), nk, s);
     Buf table = dev_alloc(sizeof(int32_t) * std::max<int64_t>(nk, 1), s);
     if (nk) hipLaunchKernelGGL(k_table_from_slots, dim3(blocks_for(nk)), dim3(kBlock), 0, s, ptr<const int32_t>(used), ptr<const int64_t>(c.slot), nk, 0,

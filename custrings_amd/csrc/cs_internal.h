@@ -267,6 +267,14 @@ struct ResultsOut {
 // A 64-bit count the kernels add to: zeroed on the device; read_count brings it back (synchronises `s`).
 Buf zeroed_count(hipStream_t s);
 int64_t read_count(const Buf& acc, hipStream_t s);
+// One word of device memory -- a flag, a maximum, a position -- brought back through the pinned scratch (synchronises `s`).
+template <class T>
+T read_back(const void* d, hipStream_t s) {
+  T* host = (T*)pinned_scratch(sizeof(T));
+  CS_HIP(hipMemcpyAsync(host, d, sizeof(T), hipMemcpyDeviceToHost, s));
+  CS_HIP(hipStreamSynchronize(s));
+  return *host;
+}
 
 template <class T>
 struct DevArray {  // caller array made device-visible (copied when it lives on the host)

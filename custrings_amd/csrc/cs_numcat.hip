@@ -256,12 +256,6 @@ void dispatch(int type, F&& f) {
   fail(CS_ERR_INVALID_ARG, "numeric category: unknown type");
 }
 size_t at_least(size_t bytes) { return bytes ? bytes : 1; }
-int32_t read_i32(const int32_t* d, hipStream_t s) {
-  int32_t* h = (int32_t*)pinned_scratch(sizeof(int32_t));
-  CS_HIP(hipMemcpyAsync(h, d, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  CS_HIP(hipStreamSynchronize(s));
-  return *h;
-}
 
 // the bitmask and the null-row count from the values (the invariant), then the stream is waited for
 cs_numcat* finish(std::unique_ptr<cs_numcat> c, hipStream_t s) {
@@ -352,7 +346,7 @@ cs_numcat* key_set_op(const cs_numcat* cat, int op, const T* items, int64_t n, c
   Buf valid = dev_alloc(at_least(sizeof(int32_t) * n), s);
   if (n) hipLaunchKernelGGL(k_flag_valid, dim3(blocks_for(n)), dim3(kBlock), 0, s, nulls, n, ptr<int32_t>(valid), ptr<int32_t>(first_null));
   Compacted live = compact(ptr<const int32_t>(valid), n, s);
-  const int32_t fnull = read_i32(ptr<const int32_t>(first_null), s);
+  const int32_t fnull = read_back<int32_t>(first_null->p, s);
   const bool new_null = cat2 ? cat2->keys_have_null : fnull != INT32_MAX;
   const int64_t m = live.n, all = ko + m;
   Buf img = dev_alloc(at_least(sizeof(uint64_t) * all), s), idx = dev_alloc(at_least(sizeof(int32_t) * all), s);
@@ -400,9 +394,9 @@ cs_numcat* keep_used(const cs_numcat* cat, const int32_t* vals, int64_t n, int32
   const int64_t nk = cat->nkeys;
   Buf used = zeros32(nk, s), bad = zeros32(1, s);
   if (n) hipLaunchKernelGGL(k_mark_used, dim3(blocks_for(n)), dim3(kBlock), 0, s, vals, n, nk, lo_ok, ptr<int32_t>(used), ptr<unsigned>(bad));
-  if (n && read_flag(bad, s)) fail(CS_ERR_RANGE, std::string(what) + ": invalid index value");
+  if (n && read_back<unsigned>(bad->p, s)) fail(CS_ERR_RANGE, std::string(what) + ": invalid index value");
   Compacted c = compact(ptr<const int32_t>(used), nk, s);
-  const bool have_null = cat->keys_have_null && nk && read_i32(ptr<const int32_t>(used), s) != 0;
+  const bool have_null = cat->keys_have_null && nk && read_back<int32_t>(used->p, s) != 0;
   auto res = blank(cat->type, n, c.n, have_null, s);
   Buf table = dev_alloc(at_least(sizeof(int32_t) * nk), s);
   if (nk) hipLaunchKernelGGL(k_table_from_slots, dim3(blocks_for(nk)), dim3(kBlock), 0, s, ptr<const int32_t>(used), ptr<const int64_t>(c.slot), nk, 0,
@@ -429,14 +423,14 @@ int32_t index_for(const cs_numcat* cat, const void* key, hipStream_t s) {
     memcpy(&v, key, sizeof(T));
     hipLaunchKernelGGL(k_find<T>, dim3(blocks_for(ko)), dim3(kBlock), 0, s, ptr<const T>(cat->keys) + hn, ko, hn, Image<T>::of(v), ptr<int32_t>(out));
   });
-  return read_i32(ptr<const int32_t>(out), s);
+  return read_back<int32_t>(out->p, s);
 }
 
 void check_positions(const int32_t* pos, int64_t n, int64_t limit, const char* what, hipStream_t s) {
   if (!n) return;
   Buf bad = zeros32(1, s);
   hipLaunchKernelGGL(k_check_range, dim3(blocks_for(n)), dim3(kBlock), 0, s, pos, n, limit, ptr<unsigned>(bad));
-  if (read_flag(bad, s)) fail(CS_ERR_RANGE, std::string(what) + ": invalid index value");
+  if (read_back<unsigned>(bad->p, s)) fail(CS_ERR_RANGE, std::string(what) + ": invalid index value");
 }
 void write_mask(const int32_t* values, int64_t n, bool have_null, uint8_t* d_mask, hipStream_t s) {
   const int64_t nb = (n + 7) / 8;
@@ -654,7 +648,7 @@ int cs_numcat_gather_values(const cs_numcat* cat, const int32_t* indexes, int64_
       Buf bad = zeros32(1, s);
       hipLaunchKernelGGL(k_gather_values, dim3(blocks_for(n)), dim3(kBlock), 0, s, ptr<const int32_t>(cat->values), cat->rows, p.d, n, ptr<int32_t>(c->values),
                          ptr<unsigned>(bad));
-      if (read_flag(bad, s)) fail(CS_ERR_RANGE, "gather_values: invalid index value");
+      if (read_back<unsigned>(bad->p, s)) fail(CS_ERR_RANGE, "gather_values: invalid index value");
     }
     *out = finish(std::move(c), s);
   });

@@ -439,14 +439,6 @@ __global__ void k_ngram_write(ColView in, const int32_t* __restrict__ kept, int6
   }
 }
 
-template <class T>
-T read_back(const Buf& b, hipStream_t s) {
-  T* host = (T*)pinned_scratch(sizeof(T));
-  CS_HIP(hipMemcpyAsync(host, b->p, sizeof(T), hipMemcpyDeviceToHost, s));
-  CS_HIP(hipStreamSynchronize(s));
-  return *host;
-}
-
 }  // namespace
 
 extern "C" {
@@ -769,7 +761,7 @@ static void split_rowwise(const cs_column* col, SplitArgs a, hipStream_t s, cs_c
       hipLaunchKernelGGL(k_split_count, dim3(nb), dim3(kBlock), 0, s, view_of(col), a,
                          ptr<int32_t>(counts), ptr<int>(mx));
     }
-    ncols = read_back<int>(mx, s);
+    ncols = read_back<int>(mx->p, s);
     a.ncols = ncols;
   }
   std::vector<std::unique_ptr<cs_column>> cols;

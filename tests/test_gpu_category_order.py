@@ -14,7 +14,7 @@ Routes (switches, forwarded to the library by conftest.py):
     CS_CAT_BITONIC=1     the compare network over all records
     CS_CAT_TIE_NETWORK=1 the radix sort on the prefix, then the network over all tied records
 
-No route string reports which kernels ran; by the loop `bitonic` in category_build (kSortChunk = 2048): the network pads U
+No route string reports which kernels ran; by `sort_network`, which category_build's ordering calls (kSortChunk = 2048): the network pads U
 records to the next power of two P; for P > 2048 it runs k_bitonic_local on P / 2048 chunks for the stages k = 2 .. 2048,
 then for every stage k = 4096 .. P one k_bitonic_step launch for each j = k / 2 .. 2048 and one k_bitonic_local tail
 (j = 1024 .. 1).  So with CS_CAT_BITONIC the counts 2049 .. 4096 (P = 4096) launch k_bitonic_step once (k 4096, j 2048) and
@@ -175,3 +175,75 @@ def test_gpu_category_key_order_on_every_ordering_route(kind, count, monkeypatch
             if switch:
                 monkeypatch.setenv(switch, "1")
             check_category(rows, "%s, %d keys, %s, route %s" % (kind, count, "5 % nulls" if nulls else "no nulls", route))
+
+
+# ---- the sampled sizing of the table --------------------------------------------------------------------------------------
+# category_build's first table has 2^22 slots; after an overflow of a table of at least 2^22 slots, a column of more than
+# 2^21 rows is sampled at a stride and the next table sized from the sample's share of distinct keys.  2^22 + 1 distinct keys
+# cannot fit the first table whatever the hash does, and such a column has more than 2^21 rows: the smallest shape that must
+# take the branch.  With these rows the table for all-distinct rows has 2^24 slots, and so have the sample's size and the
+# 16-fold one: the second attempt is the unlimited one, in 32-byte slots.
+BIG_ROWS = 4_300_000
+BIG_NULLS = 3000
+assert BIG_ROWS - BIG_NULLS > (1 << 22)
+
+_big = {}
+
+
+def big_distinct_rows(nulls):
+    """-> (values, valid): BIG_ROWS distinct uint64 values in random order (a row's key is the value's eight big-endian bytes,
+    so the key bytes vary in every position and the key order is the numeric order) and which rows are not null."""
+    if "values" not in _big:
+        rng = np.random.default_rng(20260422)
+        values = rng.integers(0, 1 << 64, size=BIG_ROWS, dtype=np.uint64, endpoint=False)
+        assert np.unique(values).size == BIG_ROWS
+        valid = np.ones(BIG_ROWS, dtype=bool)
+        valid[rng.choice(BIG_ROWS, size=BIG_NULLS, replace=False)] = False
+        values.setflags(write=False)
+        valid.setflags(write=False)
+        _big["values"], _big["valid"] = values, valid
+    return _big["values"], (_big["valid"] if nulls else np.ones(BIG_ROWS, dtype=bool))
+
+
+def big_distinct_column(nulls):
+    """The device column of big_distinct_rows from raw chars, int64 offsets and a validity mask (null rows hold no bytes)."""
+    from custrings_amd import nvstrings
+
+    values, valid = big_distinct_rows(nulls)
+    chars = np.append(values[valid].astype(">u8").view(np.uint8), np.uint8(0))  # (never an empty buffer)
+    offsets = np.zeros(BIG_ROWS + 1, dtype=np.int64)
+    np.cumsum(8 * valid.astype(np.int64), out=offsets[1:])
+    validity = None if valid.all() else np.packbits(valid.astype(np.uint8), bitorder="little")
+    return nvstrings.from_offsets64(chars, offsets, BIG_ROWS, validity)
+
+
+def big_distinct_expected(nulls):
+    """-> (key bytes, key offsets, values) by numpy alone: the sorted values, the null key first when a row is null, and every
+    row's rank."""
+    values, valid = big_distinct_rows(nulls)
+    shift = 0 if valid.all() else 1
+    keys = np.sort(values[valid])
+    offs = np.concatenate([np.zeros(1 + shift, dtype=np.int64), 8 * np.arange(1, keys.size + 1, dtype=np.int64)])
+    ranks = np.where(valid, np.searchsorted(keys, values) + shift, 0).astype(np.int32)
+    return keys.astype(">u8").view(np.uint8), offs, ranks
+
+
+@pytest.mark.parametrize("nulls", [False, True], ids=["no_nulls", "nulls"])
+def test_gpu_category_sampled_table_size(nulls):
+    """4.3M rows, every one a distinct 8-byte key (and 3000 null rows mixed in): the first table overflows, the sample sizes the
+    second.  Key bytes, key offsets, the null key and every value exactly, against numpy."""
+    from custrings_amd import nvcategory
+
+    want_chars, want_offs, want_values = big_distinct_expected(nulls)
+    nkeys = want_offs.size - 1
+    cat = nvcategory.from_strings(big_distinct_column(nulls))
+    assert cat.keys_size() == nkeys
+    chars, offs, valid = cat.keys()._export64()
+    bits = np.unpackbits(valid, bitorder="little")[:nkeys].astype(bool)
+    assert bits[0] == (not nulls) and bits[1:].all(), "the null key"
+    assert np.array_equal(offs, want_offs), "key offsets"
+    assert np.array_equal(chars, want_chars), "key bytes"
+    values = np.full(BIG_ROWS, -1, dtype=np.int32)
+    cat.values(values)
+    wrong = np.flatnonzero(values != want_values)
+    assert wrong.size == 0, "%d values differ, the first at row %d: %d, expected %d" % (wrong.size, wrong[0], values[wrong[0]], want_values[wrong[0]])

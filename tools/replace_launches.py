@@ -4,7 +4,10 @@ tests/test_gpu_replace_forms.py (`run replace`: plus bench.py's pattern on a 1M-
 tests/test_gpu_scan_forms.py (`run scan`: plus contains_re and count_re of that pattern on the same column), of
 tests/test_gpu_split_forms.py (`run split`: plus split(' ') on that column; the single pass's cases where the library
 has the experiments) or of tests/test_gpu_span_forms.py (`run spans`: plus findall, extract and replace_with_backrefs
-with tools/bench_ops.py's patterns on that column).  Two builds whose listings agree start the same kernels.
+with tools/bench_ops.py's patterns on that column) or of the category build (`run category`: the key sets of
+tests/test_gpu_category_order.py on its three routes, test_gpu_category_table_growth's column from three first table
+sizes, the plain slots, the radix sort at a small count, the 4.3M-row column that takes the sampled sizing, and the
+generated C4 column of 1M rows at K = 1000 and 2^20).  Two builds whose listings agree start the same kernels.
 
     rocprofv3 --kernel-trace --output-format json -d DIR -- python tools/replace_launches.py run scan 2> DIR/stream_info.txt
     python tools/replace_launches.py list DIR > listing.txt
@@ -98,6 +101,42 @@ def run(table):
         for op, pat, tmpl in ((spans.FINDALL, forms.IPV4, None), (spans.EXTRACT, r"(\d+)\.(\d+)\.\d+\.(\d+) ", None), (spans.BREFS, r"(\d+)\.(\d+)\.(\d+)\.(\d+)", r"\4.\3.\2.\1")):
             for i in range(2):
                 call("bench-1M-%s-%d" % (op, i), (), lambda: spans.run(bench, op, pat, tmpl))
+    elif table == "category":
+        import random
+
+        import test_gpu_category_order as order
+        from custrings_amd import nvcategory
+
+        def build(g, switches):  # (NAME=VALUE, or NAME for 1)
+            pairs = [(v.split("=") + ["1"])[:2] for v in switches]
+            for k, v in pairs:
+                L.check(L.lib.cs_config_set(k.encode(), v.encode()))
+            try:
+                nvcategory.from_strings(g)
+            finally:
+                for k, _ in pairs:
+                    L.check(L.lib.cs_config_set(k.encode(), None))
+
+        # the order test's key sets (9000 rows, 5 % of them null) on its three routes
+        for kind in order.KEY_SETS:
+            for count in (2048, 2049, 6000):
+                rnd = random.Random("%s %d" % (kind, count))
+                g = order.column(order.make_rows(order.KEY_SETS[kind](count, rnd), True, rnd))
+                for route, switch in order.ROUTES:
+                    call("%s-%d-%s" % (kind, count, route), (), lambda: build(g, [switch] if switch else []))
+        # test_gpu_category_table_growth's column: retries from a tiny first table, and none
+        growth = gpuutil.synth(4, 0, 200_000, 1 << 20)
+        for first in (6, 12, 30):
+            call("growth-first-2^%d" % first, (), lambda: build(growth, ["CS_CAT_FIRST_LOG2=%d" % first]))
+        call("growth-plain-slots", (), lambda: build(growth, ["CS_CAT_PLAIN_SLOTS"]))
+        rnd = random.Random("radix 300")
+        small = order.column(order.make_rows(order.random_12_bytes(300, rnd), True, rnd))
+        call("radix-300-keys", (), lambda: build(small, ["CS_CAT_RADIX"]))
+        # the sampled sizing: the strided k_cat_insert between two over all rows
+        call("sampled-4.3M-distinct", (), lambda: build(order.big_distinct_column(False), []))
+        for k in (1000, 1 << 20):
+            bench = gpuutil.synth(4, 0, 1_000_000, k)
+            call("bench-1M-K%d" % k, (), lambda: build(bench, []))
     else:
         import test_gpu_scan_forms as scans
 
@@ -168,7 +207,7 @@ def listing(d, force_csv=False):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) >= 2 and sys.argv[1] == "run" and sys.argv[2:] in ([], ["replace"], ["scan"], ["split"], ["spans"]):
+    if len(sys.argv) >= 2 and sys.argv[1] == "run" and sys.argv[2:] in ([], ["replace"], ["scan"], ["split"], ["spans"], ["category"]):
         run(sys.argv[2] if sys.argv[2:] else "replace")
     elif len(sys.argv) >= 3 and sys.argv[1] == "list":
         listing(sys.argv[2], force_csv=sys.argv[3:] == ["csv"])
