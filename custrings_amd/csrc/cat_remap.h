@@ -83,19 +83,4 @@ Buf zeros32(int64_t n, hipStream_t s) {
   return b;
 }
 
-template <class T>
-struct DevIn {
-  Buf tmp;
-  const T* d = nullptr;
-  DevIn(const T* p, int64_t n, int on_device, hipStream_t s) {
-    if (on_device || !p || n == 0) {
-      d = p;
-      return;
-    }
-    tmp = dev_alloc(sizeof(T) * (size_t)n, s);
-    CS_HIP(hipMemcpyAsync(tmp->p, p, sizeof(T) * (size_t)n, hipMemcpyHostToDevice, s));
-    d = ptr<const T>(tmp);
-  }
-};
-
 }  // namespace

@@ -21,63 +21,6 @@ using namespace csdev;
 
 namespace cs {
 
-// The builder of output columns from per-row lengths (cs_internal.h: Built): offsets, nulls, the chars
-// buffer; the copy kernel uses the int64 offsets (always produced: the scan writes int64) -- the narrow
-// form (int32 when the chars stay below 2 GiB) is derived.
-__global__ void k_narrow(const int64_t* __restrict__ in, int64_t n, int32_t* __restrict__ out) {
-  int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (i < n) out[i] = (int32_t)in[i];
-}
-Built::Built(int64_t rows, Nulls nulls, hipStream_t s) : col(std::make_unique<cs_column>()), nulls_(nulls), s_(s) {
-  col->rows = rows;
-  if (nulls == Nulls::none) col->null_count = 0;
-}
-Built::Built(const cs_column* like, hipStream_t s) : Built(like->rows, Nulls::shared, s) {
-  col->validity = like->validity;
-  col->null_count = like->null_count;
-}
-int64_t Built::scan(const int32_t* lens, Buf block_sums) {
-  cs_column* c = col.get();
-  lens_ = lens;
-  // (an op that allocates its lengths after the offsets has set them already: the pool sees the order it always saw)
-  if (!c->offsets) c->offsets = dev_alloc(sizeof(int64_t) * (size_t)(c->rows + 1), s_);
-  int64_t* o = ptr<int64_t>(c->offsets);
-  LenMeta meta;  // (the longest row and the largest 64-row span come out of the same pass: no op on the new column pays for them)
-  c->nbytes = nulls_ == Nulls::fused ? offsets_and_validity_from_lengths(lens, c->rows, o, &c->validity, s_, &meta)
-                                     : offsets_from_lengths(lens, c->rows, o, s_, block_sums, &meta);
-  meta.give(c);
-  off = o;
-  return c->nbytes;
-}
-uint8_t* Built::alloc_chars() {
-  col->chars = dev_alloc((size_t)col->nbytes, s_);
-  if (nulls_ == Nulls::separate) col->validity = validity_from_lengths(lens_, col->rows, s_);
-  return chars = ptr<uint8_t>(col->chars);
-}
-Built column_from_lengths(const int32_t* lens, int64_t rows, bool any_null_possible, hipStream_t s) {
-  Built b(rows, any_null_possible ? Nulls::separate : Nulls::none, s);
-  b.scan(lens);
-  b.alloc_chars();
-  return b;
-}
-void release_columns(std::vector<std::unique_ptr<cs_column>>& cols, cs_column*** out_cols, int* ncols_out) {
-  cs_column** arr = (cs_column**)malloc(sizeof(cs_column*) * cols.size());
-  if (!arr) fail(CS_ERR_ALLOC, "host allocation failed");
-  for (size_t k = 0; k < cols.size(); ++k) arr[k] = cols[k].release();
-  *out_cols = arr;
-  *ncols_out = (int)cols.size();
-}
-// (after the copy kernel ran) keep the narrow offsets only, when they suffice
-void prefer_offsets32(cs_column* c, hipStream_t s) {
-  if (c->nbytes >= ((int64_t)1 << 31) || c->rows == 0) return;
-  Buf o32 = dev_alloc(sizeof(int32_t) * (c->rows + 1), s);
-  hipLaunchKernelGGL(k_narrow, dim3(blocks_for(c->rows + 1)), dim3(kBlock), 0, s, ptr<const int64_t>(c->offsets), c->rows + 1,
-                     ptr<int32_t>(o32));
-  CS_HIP(hipStreamSynchronize(s));
-  c->offsets32 = o32;
-  c->offsets = nullptr;
-}
-
 // ---- create_from_index ------------------------------------------------------------------------
 struct IndexPair {
   const char* p;

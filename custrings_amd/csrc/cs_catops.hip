@@ -133,7 +133,7 @@ int cs_category_gather_strings(const cs_category* cat, const int32_t* pos, int64
     if (!cat || !out || n < 0 || (n > 0 && !pos)) fail(CS_ERR_INVALID_ARG, "gather_strings: bad arguments");
     require_device();
     hipStream_t s = S(stream);
-    DevIn<int32_t> p(pos, n, on_device, s);
+    DevArray<int32_t> p(pos, n, on_device, s);
     if (n && cat->keys->rows == 0) fail(CS_ERR_RANGE, "gather_strings: position out of range");
     *out = gather_rows(cat->keys.get(), p.d, n, s, false);
   });
@@ -144,7 +144,7 @@ int cs_category_gather(const cs_category* cat, const int32_t* pos, int64_t n, in
     if (!cat || !out || n < 0 || (n > 0 && !pos)) fail(CS_ERR_INVALID_ARG, "gather: bad arguments");
     require_device();
     hipStream_t s = S(stream);
-    DevIn<int32_t> p(pos, n, on_device, s);
+    DevArray<int32_t> p(pos, n, on_device, s);
     const int64_t nk = cat->keys->rows;
     if (n) {
       Buf used = zeros32(nk, s), bad = zeros32(1, s);
@@ -166,7 +166,7 @@ int cs_category_gather_and_remap(const cs_category* cat, const int32_t* pos, int
     if (!cat || !out || n < 0 || (n > 0 && !pos)) fail(CS_ERR_INVALID_ARG, "gather_and_remap: bad arguments");
     require_device();
     hipStream_t s = S(stream);
-    DevIn<int32_t> p(pos, n, on_device, s);
+    DevArray<int32_t> p(pos, n, on_device, s);
     const int64_t nk = cat->keys->rows;
     Buf used = zeros32(nk, s), bad = zeros32(1, s);
     if (n) hipLaunchKernelGGL(k_mark_used, dim3(blocks_for(n)), dim3(kBlock), 0, s, p.d, n, nk, 0, ptr<int32_t>(used), ptr<unsigned>(bad));

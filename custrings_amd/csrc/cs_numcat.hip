@@ -457,8 +457,8 @@ int key_set_entry(const char* what, int op, const cs_numcat* cat, const void* it
     }
     dispatch(cat->type, [&](auto t) {
       using T = decltype(t);
-      DevIn<T> in((const T*)items, n, on_device, s);
-      DevIn<uint8_t> nl(n ? nulls : nullptr, (n + 7) / 8, on_device, s);
+      DevArray<T> in((const T*)items, n, on_device, s);
+      DevArray<uint8_t> nl(n ? nulls : nullptr, (n + 7) / 8, on_device, s);
       *out = key_set_op<T>(cat, op, in.d, n, nl.d, nullptr, s);
     });
   });
@@ -477,8 +477,8 @@ int cs_numcat_build(const void* items, int64_t n, const uint8_t* nulls, cs_numty
     hipStream_t s = S(stream);
     dispatch(type, [&](auto t) {
       using T = decltype(t);
-      DevIn<T> in((const T*)items, n, on_device, s);
-      DevIn<uint8_t> nl(items ? nulls : nullptr, (n + 7) / 8, on_device, s);
+      DevArray<T> in((const T*)items, n, on_device, s);
+      DevArray<uint8_t> nl(items ? nulls : nullptr, (n + 7) / 8, on_device, s);
       *out = build<T>(in.d, n, nl.d, s);
     });
   });
@@ -539,7 +539,7 @@ int cs_numcat_gather_type(const cs_numcat* cat, const int32_t* indexes, int64_t 
     check_rows(n);
     hipStream_t s = S(stream);
     if (!n) return;
-    DevIn<int32_t> p(indexes, n, on_device, s);
+    DevArray<int32_t> p(indexes, n, on_device, s);
     check_positions(p.d, n, cat->nkeys, "gather_type", s);
     ResultsOut res(results, (size_t)n * csnum::type_bytes(cat->type), on_device, s), mask(nulls, (size_t)((n + 7) / 8), on_device || !nulls, s);
     dispatch(cat->type, [&](auto t) {
@@ -619,7 +619,7 @@ int cs_numcat_gather(const cs_numcat* cat, const int32_t* indexes, int64_t n, in
     require_device();
     check_rows(n);
     hipStream_t s = S(stream);
-    DevIn<int32_t> p(indexes, n, on_device, s);
+    DevArray<int32_t> p(indexes, n, on_device, s);
     check_positions(p.d, n, cat->nkeys, "gather", s);
     auto c = same_keys(cat, n, s);
     if (n) CS_HIP(hipMemcpyAsync(c->values->p, p.d, sizeof(int32_t) * n, hipMemcpyDeviceToDevice, s));
@@ -632,7 +632,7 @@ int cs_numcat_gather_and_remap(const cs_numcat* cat, const int32_t* indexes, int
     require_device();
     check_rows(n);
     hipStream_t s = S(stream);
-    DevIn<int32_t> p(indexes, n, on_device, s);
+    DevArray<int32_t> p(indexes, n, on_device, s);
     *out = keep_used(cat, p.d, n, 0, "gather_and_remap", s);
   });
 }
@@ -642,7 +642,7 @@ int cs_numcat_gather_values(const cs_numcat* cat, const int32_t* indexes, int64_
     require_device();
     check_rows(n);
     hipStream_t s = S(stream);
-    DevIn<int32_t> p(indexes, n, on_device, s);
+    DevArray<int32_t> p(indexes, n, on_device, s);
     auto c = same_keys(cat, n, s);
     if (n) {
       Buf bad = zeros32(1, s);
@@ -662,7 +662,7 @@ int cs_debug_numcat_sort_rows(const void* items, int64_t n, cs_numtype type, int
     hipStream_t s = S(stream);
     dispatch(type, [&](auto t) {
       using T = decltype(t);
-      DevIn<T> in((const T*)items, n, on_device, s);
+      DevArray<T> in((const T*)items, n, on_device, s);
       Buf img = dev_alloc(sizeof(uint64_t) * n, s), idx = dev_alloc(sizeof(int32_t) * n, s);
       hipLaunchKernelGGL(k_images<T>, dim3(blocks_for(n)), dim3(kBlock), 0, s, in.d, (const int32_t*)nullptr, n, (int64_t)0, 0, ptr<uint64_t>(img), ptr<int32_t>(idx));
       radix_sort_pairs64(ptr<uint64_t>(img), ptr<int32_t>(idx), n, s);  // (waits for `s`: the buffers are idle when dropped)

@@ -1,4 +1,4 @@
-// Row-major ("record") forms of split and the partition pair:
+// Row-major ("record") forms of split, of any column-major result, and the partition pair:
 // NVStrings::split_record / rsplit_record (split.cu:125-700), partition / rpartition
 // (split.cu:1165-1361).  The reference returns one NVStrings instance -- and makes one
 // device allocation -- per row.  Natively a record result is ONE column holding every
@@ -8,6 +8,7 @@
 // The per-row token rules are the reference's, restated on byte offsets (row_ops.h).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstring>
 
 #include "cs_internal.h"
@@ -163,24 +164,78 @@ __global__ void k_part_copy(PartArgs a, const int64_t* __restrict__ off, uint8_t
     if (hi[k] > lo[k]) copy_bytes(out + off[3 * r + k], p + lo[k], hi[k] - lo[k]);
 }
 
-struct HostBytes {
-  Buf buf;
-  int n = 0;
-  HostBytes(const char* t, hipStream_t s) {
-    if (!t) return;
-    n = (int)strlen(t);
-    buf = dev_alloc((size_t)n + 1, s);
-    CS_HIP(hipMemcpyAsync(buf->p, t, (size_t)n + 1, hipMemcpyHostToDevice, s));
-  }
-  const uint8_t* d() const { return ptr<const uint8_t>(buf); }
-};
+}  // namespace
 
+// ---- records from columns: a column-major result (cs_split / cs_rsplit / cs_extract / cs_findall) turned row-major ----
+// The reference's *_record methods return one NVStrings instance per row (extract_record.cu:146-152,
+// findall_record.cu:144-151: a device allocation per row); here it is the same flat column and list offsets as above.
+namespace cs {
+struct RecordCols {
+  static constexpr int kMax = 64;
+  cs::ColView col[kMax];
+};
+// (the columns go through the kernels kMax at a time: c.col[j] is column k0 + j)
+// entries per record: all columns (fixed) or the row's leading non-null columns (ragged)
+__global__ void k_record_counts(RecordCols c, int k0, int nb, int ncols, int ragged, int64_t rows, int32_t* __restrict__ counts) {
+  int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (r >= rows) return;
+  if (!ragged) {
+    counts[r] = ncols;
+    return;
+  }
+  int n = k0 ? counts[r] : 0;
+  if (n == k0) {  // every earlier column was non-null for this row
+    int j = 0;
+    while (j < nb && row_is_valid(c.col[j].validity, r)) ++j;
+    n += j;
+  }
+  counts[r] = n;
+}
+__global__ void k_record_lengths(RecordCols c, int k0, int nb, int64_t rows, const int64_t* __restrict__ list,
+                                 int32_t* __restrict__ lens) {
+  int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (r >= rows) return;
+  const int64_t e0 = list[r];
+  const int n = (int)(list[r + 1] - e0);
+  for (int j = 0; j < nb && k0 + j < n; ++j) {
+    const cs::ColView& v = c.col[j];
+    lens[e0 + k0 + j] = row_is_valid(v.validity, r) ? (int32_t)(v.offsets[r + 1] - v.offsets[r]) : -1;
+  }
+}
+__global__ void k_record_copy(RecordCols c, int k0, int nb, int64_t rows, const int64_t* __restrict__ list,
+                              const int64_t* __restrict__ out_off, uint8_t* __restrict__ out_chars) {
+  int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (r >= rows) return;
+  const int64_t e0 = list[r];
+  const int n = (int)(list[r + 1] - e0);
+  for (int j = 0; j < nb && k0 + j < n; ++j) {
+    const cs::ColView& v = c.col[j];
+    if (!row_is_valid(v.validity, r)) continue;
+    const uint8_t* src = v.chars + v.offsets[r];
+    uint8_t* dst = out_chars + out_off[e0 + k0 + j];
+    const int len = (int)(v.offsets[r + 1] - v.offsets[r]);
+    for (int i = 0; i < len; ++i) dst[i] = src[i];
+  }
+}
+}  // namespace cs
+
+namespace {
+
+// Both record makers are the same five steps -- counts per row, scan to the list offsets, lengths per entry, column from
+// lengths, copy -- and end by handing the list offsets to the caller (waits for `s`: the column is finished too).
+void list_to_caller(const Buf& list, int64_t rows, int64_t* list_offsets, int on_device, hipStream_t s) {
+  CS_HIP(hipMemcpyAsync(list_offsets, list->p, sizeof(int64_t) * (rows + 1), on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+  CS_HIP(hipStreamSynchronize(s));
+}
+
+// split_record / rsplit_record: the records are a row's tokens
 void records(const cs_column* col, const char* delimiter, int maxsplit, int from_right, int64_t* list_offsets, int on_device, hipStream_t s,
              cs_column** out) {
   const int64_t rows = col->rows;
   if (delimiter && !*delimiter) delimiter = nullptr;  // (an empty delimiter string splits on whitespace, as a null one)
-  HostBytes d(delimiter, s);
-  RecArgs a{view_of(col), delimiter ? d.d() : nullptr, d.n, maxsplit > 0 ? maxsplit + 1 : 0, from_right};
+  HostText d(delimiter, s);
+  RecArgs a{view_of(col), d.d(), delimiter ? d.n : 0, maxsplit > 0 ? maxsplit + 1 : 0, from_right};
+  // counts per row, scan to the list offsets
   Buf list = dev_alloc(sizeof(int64_t) * (rows + 1), s);
   int64_t total = 0;
   if (rows) {
@@ -194,6 +249,7 @@ void records(const cs_column* col, const char* delimiter, int maxsplit, int from
   if (total == 0) {
     *out = make_all_null(0, s);
   } else {
+    // lengths per entry, column from lengths, copy
     Buf lens = dev_alloc(sizeof(int32_t) * total, s);
     hipLaunchKernelGGL(k_rec_lengths, dim3(blocks_for(rows)), dim3(kBlock), 0, s, a, ptr<const int64_t>(list), ptr<int32_t>(lens));
     Built b = column_from_lengths(ptr<int32_t>(lens), total, false, s);
@@ -202,8 +258,58 @@ void records(const cs_column* col, const char* delimiter, int maxsplit, int from
     prefer_offsets32(b.col.get(), s);
     *out = b.col.release();
   }
-  CS_HIP(hipMemcpyAsync(list_offsets, list->p, sizeof(int64_t) * (rows + 1), on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
-  CS_HIP(hipStreamSynchronize(s));
+  list_to_caller(list, rows, list_offsets, on_device, s);
+}
+
+// f(rc, k0, nb) for the columns in batches of RecordCols::kMax: rc.col[0 .. nb) are columns k0 .. k0 + nb - 1
+template <class F>
+void for_each_batch(const cs_column* const* cols, int ncols, F&& f) {
+  for (int k0 = 0; k0 < ncols; k0 += RecordCols::kMax) {
+    RecordCols rc{};
+    const int nb = std::min(RecordCols::kMax, ncols - k0);
+    for (int j = 0; j < nb; ++j) rc.col[j] = view_of(cols[k0 + j]);
+    f(rc, k0, nb);
+  }
+}
+// records from columns: the records are a row's entries across `ncols` columns of `rows` rows each.  The same steps as
+// records(), its own tail: its entries may be null, the column keeps its int64 offsets, and the offsets are allocated
+// before the lengths.
+void records_from_columns(const cs_column* const* cols, int ncols, int ragged, int64_t rows, int64_t* list_offsets, int on_device, hipStream_t s,
+                          cs_column** out) {
+  const dim3 grid(blocks_for(rows)), block(kBlock);
+  // counts per row, scan to the list offsets
+  Buf list = dev_alloc(sizeof(int64_t) * (rows + 1), s);
+  int64_t total = 0;
+  if (rows && ncols) {
+    Buf counts = dev_alloc(sizeof(int32_t) * rows, s);
+    for_each_batch(cols, ncols, [&](const RecordCols& rc, int k0, int nb) {
+      hipLaunchKernelGGL(k_record_counts, grid, block, 0, s, rc, k0, nb, ncols, ragged, rows, ptr<int32_t>(counts));
+    });
+    total = offsets_from_lengths(ptr<int32_t>(counts), rows, ptr<int64_t>(list), s);
+  } else {
+    CS_HIP(hipMemsetAsync(list->p, 0, sizeof(int64_t) * (rows + 1), s));
+  }
+  if (total >= (int64_t)1 << 31) fail(CS_ERR_RANGE, "records: more than 2^31 strings");
+  // lengths per entry
+  Built b(total, total ? Nulls::separate : Nulls::none, s);
+  b.col->offsets = dev_alloc(sizeof(int64_t) * (total + 1), s);  // (before the lengths, as the pool has always seen them)
+  Buf lens;
+  if (total) {
+    lens = dev_alloc(sizeof(int32_t) * total, s);
+    for_each_batch(cols, ncols, [&](const RecordCols& rc, int k0, int nb) {
+      hipLaunchKernelGGL(k_record_lengths, grid, block, 0, s, rc, k0, nb, rows, ptr<int64_t>(list), ptr<int32_t>(lens));
+    });
+  }
+  // column from lengths, copy
+  b.scan(ptr<int32_t>(lens));
+  b.alloc_chars();
+  if (total)
+    for_each_batch(cols, ncols, [&](const RecordCols& rc, int k0, int nb) {
+      hipLaunchKernelGGL(k_record_copy, grid, block, 0, s, rc, k0, nb, rows, ptr<int64_t>(list), b.off, b.chars);
+    });
+  CS_HIP(hipGetLastError());
+  list_to_caller(list, rows, list_offsets, on_device, s);
+  *out = b.col.release();
 }
 
 }  // namespace
@@ -226,6 +332,18 @@ int cs_rsplit_record(const cs_column* col, const char* delimiter, int maxsplit, 
     records(col, delimiter, maxsplit, 1, list_offsets, on_device, S(stream), out);
   });
 }
+// Row-major ("record") view of a column-major result (cs_split / cs_rsplit / cs_extract / cs_findall).
+int cs_records_from_columns(const cs_column* const* cols, int ncols, int ragged, int64_t* list_offsets, int on_device,
+                            cs_stream stream, cs_column** out) {
+  return guard([&] {
+    if (!out || !list_offsets || ncols < 0 || (ncols > 0 && !cols)) fail(CS_ERR_INVALID_ARG, "records: bad arguments");
+    require_device();
+    const int64_t rows = ncols ? cols[0]->rows : 0;
+    for (int k = 0; k < ncols; ++k)
+      if (!cols[k] || cols[k]->rows != rows) fail(CS_ERR_INVALID_ARG, "records: columns of different row counts");
+    records_from_columns(cols, ncols, ragged, rows, list_offsets, on_device, S(stream), out);
+  });
+}
 int cs_partition(const cs_column* col, const char* delimiter, int from_right, cs_stream stream, cs_column** out) {
   return guard([&] {
     if (!col || !out) fail(CS_ERR_INVALID_ARG, "partition: bad arguments");
@@ -239,7 +357,7 @@ int cs_partition(const cs_column* col, const char* delimiter, int from_right, cs
       return;
     }
     if (3 * rows >= ((int64_t)1 << 31)) fail(CS_ERR_RANGE, "partition: more than 2^31 strings");
-    HostBytes d(delimiter, s);
+    HostText d(delimiter, s);
     PartArgs a{view_of(col), d.d(), d.n, from_right};
     Buf lens = dev_alloc(sizeof(int32_t) * 3 * rows, s);
     hipLaunchKernelGGL(k_part_lengths, dim3(blocks_for(rows)), dim3(kBlock), 0, s, a, ptr<int32_t>(lens));

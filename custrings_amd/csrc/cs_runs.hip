@@ -17,7 +17,7 @@
 //   pass 0  every row's output length (the row lanes read the positions of their row's first and one-past-last byte out of
 //           the pieces' prefix table), the largest tile output (sizes pass 1's LDS)
 //   pass 1  compaction into an LDS tile, the replacement text at every run start, one coalesced flush at offsets[first row]
-// with the generic scan over the lengths in between (which also leaves the output's metadata: cs_core.hip, LenMeta).
+// with the generic scan over the lengths in between (which also leaves the output's metadata: cs_scan.hip, LenMeta).
 #include <hip/hip_runtime.h>
 
 #include "cs_internal.h"

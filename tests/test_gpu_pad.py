@@ -256,7 +256,7 @@ def test_against_harness(generated, harness, monkeypatch, k, rowwise):
 
 
 # ---- a staged tile whose output exceeds the out-tile ----------------------------------------------------------------------------
-# the host's tile plan, restated (cs_core.hip plan_row_tiles / plan_staged_tiles, sized_route.h write_sized)
+# the host's tile plan, restated (cs_plan.hip plan_row_tiles / plan_staged_tiles, sized_route.h write_sized)
 PF_BYTES, STAGE_SLACK, OUT_TILE, WAVE_ROW = 6144, 48, 16 * 1024, 256
 
 

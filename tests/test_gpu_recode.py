@@ -98,7 +98,7 @@ def check_sized(op, rows, g, route, pairs=None, want=None):
     return out
 
 
-# ---- the host's tile plan, restated (cs_core.hip plan_row_tiles / plan_staged_tiles, cs_recode.hip run_recode) ---------------------
+# ---- the host's tile plan, restated (cs_plan.hip plan_row_tiles / plan_staged_tiles, cs_recode.hip run_recode) ---------------------
 PF_BYTES, STAGE_SLACK, OUT_TILE = 6144, 48, 16 * 1024
 
 

@@ -543,7 +543,7 @@ def test_gpu_span_bytes_written_by_sub_tiles(gpu_engine, oracle_engine, shape, m
 
 
 def test_gpu_offsets_from_lengths_beyond_32_bits(gpu_engine):
-    """The chunked lengths -> offsets scan (cs_core.hip) runs a chunk's inner sums in 32 bits only when the chunk's total
+    """The chunked lengths -> offsets scan (cs_scan.hip) runs a chunk's inner sums in 32 bits only when the chunk's total
     fits; 200 copies of a 16 MiB row put 3.1 GiB into one 2048-row chunk.  Rows gathered from both ends of the result
     must come back whole, and the scan must also be right at sizes around a chunk (2047 .. 2049 rows) and a workgroup."""
     from custrings_amd import nvstrings
