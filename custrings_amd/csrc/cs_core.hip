@@ -76,7 +76,7 @@ void note_route_pieces() {
   snprintf(g_route_text, sizeof g_route_text, "pieces:%s", inner);
   g_last_route = g_route_text;
 }
-// the scan put the rows with bytes >= 0x80 off to a second launch (cs_regex.hip: ScanStreamArgs::deferred)
+// the scan put the rows with bytes >= 0x80 off to a second launch (regex_stream.h: ScanStreamArgs::deferred)
 void note_route_put_off() {
   char inner[48];
   snprintf(inner, sizeof inner, "%s", g_last_route);

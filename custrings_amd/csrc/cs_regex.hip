@@ -1,13 +1,9 @@
-// Regex ops: contains_re / match / count_re / replace_re.
-//
-// One thread per row.  The compiled program image (instructions, classes,
-// ASCII bitmaps, first-character prefilter) is staged into LDS once per
-// workgroup; each thread's two ordered thread lists + closure stack also live
-// in LDS, interleaved across lanes (slot-major) so accesses are bank-conflict
-// free.  Programs whose lists do not fit in LDS run with the same code against
-// a global scratch arena (the reference switches to a global `relists_mem`
-// above 1000 instructions, regexec.cpp:81-95; count.cu:74-85).
-// Workgroups walk the rows grid-stride so the arena is bounded by the grid.
+// The regex ops that build columns.  replace_re: the two-pass row-wise kernels, the kernel for the rows a single pass
+// leaves as holes, the persistent single-pass kernel k_tdfa_replace_stream, the host route cs::replace_re_column
+// (cs_internal.h: ReplaceCall) and cs_replace_re; replace_re with several patterns.  extract / findall /
+// replace_with_backrefs: the row-wise span and backrefs kernels, the writers of the spans' bytes, the host routes on
+// SpanRun and the C entries; regex_stream.h's kernel is instantiated here for MODE 3 (findall), 4 (extract), 5 and 6
+// (replace_with_backrefs).  The compiled pattern is cs_regex_pattern.hip's, the scans are cs_regex_scan.hip's.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -24,108 +20,19 @@
 #include <mutex>
 
 #include "tile_utils.h"
+#include "regex_exec.h"
+#include "regex_stream.h"
 
 using namespace cs;
 using namespace csdev;
-
-struct cs_regex {
-  csrx::Program prog;
-  std::vector<int32_t> blob;   // program only (ABI: cs_regex_blob)
-  std::vector<int32_t> image;  // blob + executor extras
-  std::vector<int32_t> tdfa;   // tagged DFA image (empty = not convertible)
-  std::vector<int32_t> gtags;  // capture-group tag image of the tagged DFA (empty = no groups / not convertible)
-  std::vector<int32_t> bits;   // bit-parallel form (regex_bits.h; empty = the program does not convert)
-  Buf d_image;                 // uploaded lazily
-  Buf d_tdfa;
-  Buf d_gtags;
-  Buf d_bits;
-  bool empty_pattern = false;
-  std::atomic<int> refs{1};    // handles given out by cs_regex_compile + one for the list of kept patterns
-};
+using namespace cs::rx;
 
 namespace cs {
 bool replace_class_runs(const cs_column* col, const int32_t* d_bits, const std::vector<int32_t>& bits, const char* repl, int rb, hipStream_t s, cs_column** out);
-bool count_class_runs(const cs_column* col, const int32_t* d_bits, const std::vector<int32_t>& bits, hipStream_t s, int32_t* results, int64_t* hits);
 }
 
 namespace {
 
-constexpr size_t kLdsBudget = 64 * 1024;
-
-struct Launch {  // kernel-visible part of the launch plan (POD)
-  const int32_t* image;
-  int image_words;
-  int slots;        // 32-bit scratch slots per thread
-  uint32_t* arena;  // global scratch (nullptr = lists in LDS)
-  int image_in_lds;
-};
-struct Plan {
-  Launch d;
-  int threads;       // workgroup size
-  size_t lds_bytes;  // dynamic LDS
-  unsigned grid;
-  bool small;
-  Buf arena_buf;
-};
-
-struct RowSrc {
-  ColView in;
-  const uint8_t* flags;
-  int64_t safe_end;  // chars bytes that may be read (logical size + allocation slack)
-};
-
-// common prologue: stage the image, carve per-thread scratch
-struct Ctx {
-  csvm::ProgView P;
-  uint32_t* mem;
-  int stride;
-};
-__device__ __forceinline__ Ctx setup(const Launch& L, const uint8_t* flags, uint32_t* smem) {
-  Ctx c;
-  const int32_t* img = L.image;
-  int used = 0;
-  if (L.image_in_lds) {
-    for (int i = threadIdx.x; i < L.image_words; i += blockDim.x) smem[i] = (uint32_t)L.image[i];
-    __syncthreads();
-    img = (const int32_t*)smem;
-    used = (L.image_words + 3) & ~3;
-  }
-  c.P = csvm::make_view(img, flags);
-  if (L.arena) {
-    c.mem = L.arena + (size_t)blockIdx.x * blockDim.x * L.slots + threadIdx.x;
-  } else {
-    c.mem = smem + used + threadIdx.x;
-  }
-  c.stride = blockDim.x;
-  return c;
-}
-
-// MODE 0 contains_re, 1 match, 2 count_re
-template <bool SMALL, int MODE>
-__global__ void k_regex_scan(RowSrc src, Launch L, uint8_t* __restrict__ out8, int32_t* __restrict__ out32,
-                             unsigned long long* __restrict__ found) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-  Ctx c = setup(L, src.flags, smem);
-  const ColView& in = src.in;
-  const int64_t nblk = (in.rows + blockDim.x - 1) / blockDim.x;
-  int hits = 0;
-  for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
-    int64_t r = blk * blockDim.x + threadIdx.x;
-    if (r >= in.rows) continue;
-    int v = 0;
-    if (row_is_valid(in.validity, r)) {
-      int64_t b = in.offsets[r];
-      csvm::Vm<SMALL> vm(c.P, c.mem, c.stride, in.chars + b, (int)(in.offsets[r + 1] - b));
-      if (MODE == 2) v = csvm::row_count_re(vm);
-      else v = csvm::row_contains_re(vm, MODE == 1);
-    }
-    if (MODE == 2) out32[r] = v;
-    else out8[r] = (uint8_t)v;
-    hits += v > 0;
-  }
-  long long t = block_reduce_sum(hits);
-  if (threadIdx.x == 0 && t) atomicAdd(found, (unsigned long long)t);
-}
 
 // replace_re size pass: output bytes per row (-1 for null rows) + block sums
 template <bool SMALL>
@@ -181,7 +88,6 @@ __global__ void k_replace_re_write(RowSrc src, Launch L, const uint8_t* __restri
 // begins / lens [group * rows + row] (len -1 = null row); a second kernel copies the bytes.
 // The thread lists live in a global arena (12 slots per instruction per thread), interleaved
 // across the lanes of a workgroup so the list walks coalesce.
-constexpr int kMaxGroups = 32;
 template <bool SMALL>
 __global__ void __launch_bounds__(256) k_extract_spans(RowSrc src, Launch L, int groups, int32_t* __restrict__ begins,
                                                        int32_t* __restrict__ lens) {
@@ -389,104 +295,6 @@ __global__ void __launch_bounds__(256) k_spans_write_tile2(SpanWrite2Args a) {
   }
 }
 
-// ---- tagged-DFA kernels (regex_tdfa.h): tables staged in LDS, no per-thread lists ----
-struct TLaunch {
-  const int32_t* tdfa;   // device image
-  int tdfa_words;
-  int in_lds;
-  const int32_t* image;  // list-simulator image (global; consulted for non-ASCII chars only)
-};
-struct TCtx {
-  cstd::View D;
-  csvm::ProgView P;
-};
-template <bool IN_LDS>
-__device__ __forceinline__ TCtx tsetup(const TLaunch& L, const uint8_t* flags, uint32_t* smem) {
-  TCtx c;
-  if (IN_LDS) {
-    for (int i = threadIdx.x; i < L.tdfa_words; i += blockDim.x) smem[i] = (uint32_t)L.tdfa[i];
-    __syncthreads();
-    c.D = cstd::make_view((const int32_t*)smem);
-  } else if (L.in_lds == 2) {
-    // the tables stay in memory, the header and the image's last words (suffix, repetition counts, group map) come into LDS:
-    // what the hot loops read of the image -- as scalar loads from memory each read also waited for every LDS access in flight
-    // (replace_re of the dotted quad on this form: 5.1 against 4.7 ms)
-    if (threadIdx.x < cstd::kHeadTailWords)
-      smem[threadIdx.x] = threadIdx.x == 15 ? (uint32_t)cstd::kHeadTailWords
-                                            : (uint32_t)L.tdfa[threadIdx.x < 32 ? (int)threadIdx.x : L.tdfa_words - cstd::kHeadTailWords + (int)threadIdx.x];
-    __syncthreads();
-    c.D = cstd::make_view((const int32_t*)smem, L.tdfa);
-  } else {
-    c.D = cstd::make_view(L.tdfa);
-  }
-  c.P = csvm::make_view(L.image, flags);
-  return c;
-}
-template <int MODE, bool IN_LDS, bool WIDE = false>
-__global__ void __launch_bounds__(256) k_tdfa_scan(RowSrc src, TLaunch L, uint8_t* __restrict__ out8,
-                                                   int32_t* __restrict__ out32,
-                                                   unsigned long long* __restrict__ found) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-  TCtx c = tsetup<IN_LDS>(L, src.flags, smem);
-  const ColView& in = src.in;
-  const int64_t nblk = (in.rows + blockDim.x - 1) / blockDim.x;
-  int hits = 0;
-  for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
-    int64_t r = blk * blockDim.x + threadIdx.x;
-    if (r >= in.rows) continue;
-    int v = 0;
-    if (row_is_valid(in.validity, r)) {
-      int64_t b = in.offsets[r];
-      typename std::conditional<WIDE, cstd::TdfaWide, cstd::Tdfa>::type vm(c.D, c.P, in.chars + b, (int)(in.offsets[r + 1] - b));
-      vm.wide_ok = (b & ~(int64_t)3) + cstd::Tdfa::kMaskBytes <= src.safe_end;
-      if (MODE == 2) v = csvm::row_count_re(vm);
-      else v = csvm::row_contains_re(vm, MODE == 1);
-    }
-    if (MODE == 2) out32[r] = v;
-    else out8[r] = (uint8_t)v;
-    hits += v > 0;
-  }
-  long long t = block_reduce_sum(hits);
-  if (threadIdx.x == 0 && t) atomicAdd(found, (unsigned long long)t);
-}
-// A row of the list kernels in LDS: the aligned 16-byte pieces that cover it (rows within the masks: seven at most), copied by
-// the row's own thread -- the generic executor then walks LDS bytes instead of a chain of dependent loads from memory
-// (k_tdfa_replace_list on the C5 pieces: 0.38 ms a launch from memory).  Returns the row's first byte; a longer row stays in memory.
-constexpr int kListRowBytes = 112;
-// (the pieces must lie inside the chars buffer -- [lo, hi): a caller's memory wrapped at an odd address has no slack around it)
-__device__ __forceinline__ const uint8_t* list_row_to_lds(const uint8_t* src, int n, uint8_t* buf, const uint8_t* lo, const uint8_t* hi) {
-  const int sh = (int)((uintptr_t)src & 15);
-  if (sh + n > kListRowBytes || src - sh < lo || src - sh + ((sh + n + 15) & ~15) > hi) return src;
-  const uint4* a = reinterpret_cast<const uint4*>(src - sh);
-  for (int k = 0; k * 16 < sh + n; ++k) *reinterpret_cast<uint4*>(buf + 16 * k) = a[k];
-  return buf + sh;
-}
-// the rows a stream launch put off (ScanStreamArgs::deferred): a thread a row, the generic executor on the row's bytes (staged in LDS)
-template <int MODE>
-__global__ void __launch_bounds__(256) k_tdfa_scan_list(RowSrc src, TLaunch L, const int32_t* __restrict__ list, const unsigned* __restrict__ nlist, unsigned cap,
-                                                        uint8_t* __restrict__ out8, int32_t* __restrict__ out32, unsigned long long* __restrict__ found) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-  const unsigned total = min(*nlist, cap);
-  if ((unsigned)blockIdx.x * 256u >= total) return;  // (nothing for this workgroup: not even the tables)
-  TCtx c = tsetup<true>(L, src.flags, smem);
-  const ColView& in = src.in;
-  int hits = 0;
-  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
-    const int64_t r = list[i];
-    const int64_t b = in.offsets[r];
-    const int n = (int)(in.offsets[r + 1] - b);
-    uint8_t* buf = reinterpret_cast<uint8_t*>(smem) + (((size_t)L.tdfa_words * 4 + 15) & ~(size_t)15) + (size_t)threadIdx.x * kListRowBytes;
-    const uint8_t* p = list_row_to_lds(in.chars + b, n, buf, in.chars, in.chars + src.safe_end);
-    cstd::Tdfa vm(c.D, c.P, p, n);
-    vm.wide_ok = p != in.chars + b || (b & ~(int64_t)3) + cstd::Tdfa::kMaskBytes <= src.safe_end;
-    const int v = MODE == 2 ? csvm::row_count_re(vm) : csvm::row_contains_re(vm, false);
-    if (MODE == 2) out32[r] = v;
-    else out8[r] = (uint8_t)v;
-    hits += v > 0;
-  }
-  const long long t = block_reduce_sum(hits);
-  if (threadIdx.x == 0 && t) atomicAdd(found, (unsigned long long)t);
-}
 template <bool IN_LDS, bool WIDE = false>
 __global__ void __launch_bounds__(256) k_tdfa_replace_size(RowSrc src, TLaunch L, int rb, int maxrepl,
                                                            int32_t* __restrict__ lens) {
@@ -976,124 +784,6 @@ __device__ __forceinline__ void lds_put_short(uint8_t* at, uint32_t r0, uint32_t
   if (rb & 1) *at = (uint8_t)r0;
 }
 
-// ---- unit scan (regex_tdfa.cpp, header word 31): helpers shared by the stream kernels ------------------
-constexpr int kUnitQueue = 128;  // units one round of the queue holds (a busier sub-tile scans its rows whole)
-// Row lanes: the row's candidate bits (returned in m0..m2) and x bits give its units; all units of the sub-tile are
-// queued as (row | first byte << 8 | end << 16).  `between` runs once every lane holds its masks (the bitmaps may
-// be re-used from there on).  Returns the number of units, or -1 when the queue cannot hold them (nothing is
-// written then and `between` has not run).
-template <class Between>
-__device__ __forceinline__ int unit_discover(const cstd::View& D, const uint32_t* bitmap, const uint32_t* xbitmap, int p0, int n, int lane,
-                                             uint32_t* uqueue, uint32_t& m0, uint32_t& m1, uint32_t& m2, Between&& between) {
-  using namespace cstd;
-  uint32_t x0 = 0, x1 = 0, x2 = 0;
-  cstile::row_bits96(bitmap, p0, n, m0, m1, m2);
-  if ((D.units >> 8) & 127u) cstile::row_bits96(xbitmap, p0, n, x0, x1, x2);
-  const U128 C = u128(m0 | ((unsigned long long)m1 << 32), m2), X = u128(x0 | ((unsigned long long)x1 << 32), x2);
-  U128 N;
-  U128 W = unit_ends(C, X, ((D.units >> 16) & 1u) != 0, N);
-  const int cnt = u128_popc(W);
-  const int uincl = csdev::wave_inclusive_scan(cnt);
-  const int total = __builtin_amdgcn_readlane(uincl, 63);
-  if (total > kUnitQueue) return -1;
-  cstile::wave_lds_fence();
-  between();
-  int slot = uincl - cnt;
-  while (__any(u128_any(W))) {
-    if (u128_any(W)) {
-      const int q = u128_ctz(W);
-      W = u128_clear_lowest(W);
-      uqueue[slot++] = (uint32_t)lane | ((uint32_t)unit_start(N, q) << 8) | ((uint32_t)q << 16);
-    }
-  }
-  cstile::wave_lds_fence();
-  return total;
-}
-// Unit lanes: queue entry -> the unit's row (its position and length come from the row's lane) and the row's
-// candidate bits cut to the unit.  Every lane of the wave must call this (shuffles).
-// `clip`: the row handed to the unit's scan ends where the unit ends (see reclassify_high: the byte behind it may be >= 0x80).
-__device__ __forceinline__ void unit_take(uint32_t ent, int rbeg, int n, uint32_t m0, uint32_t m1, uint32_t m2, int& r, int& rbeg_r, int& n_r,
-                                          uint32_t& c0, uint32_t& c1, uint32_t& c2, bool clip = false) {
-  using namespace cstd;
-  r = (int)(ent & 63u);
-  const int us = (int)((ent >> 8) & 255u), uq = (int)((ent >> 16) & 255u);
-  rbeg_r = __shfl(rbeg, r, 64);
-  n_r = __shfl(n, r, 64);
-  if (clip && uq < n_r) n_r = uq;
-  const U128 keep = u128_andn(u128_below(uq), u128_below(us));
-  c0 = (uint32_t)__shfl((int)m0, r, 64) & (uint32_t)keep.lo;
-  c1 = (uint32_t)__shfl((int)m1, r, 64) & (uint32_t)(keep.lo >> 32);
-  c2 = (uint32_t)__shfl((int)m2, r, 64) & (uint32_t)keep.hi;
-}
-// "byte == x" bits of one 16-byte piece (staging, from the prefetch registers)
-__device__ __forceinline__ uint32_t unit_xbits16(const uint4& q, uint32_t xpat) {
-  auto eq = [&](uint32_t w) {  // bit 7 of every byte lane that equals x (exact: no borrow between lanes)
-    const uint32_t t = w ^ xpat;
-    return ~(((t & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | t) & 0x80808080u;
-  };
-  return cstile::gather16_bit7(eq(q.x), eq(q.y), eq(q.z), eq(q.w));
-}
-
-// Sub-tiles that hold bytes >= 0x80 (non-ASCII text).  The lean scan indexes its table with ASCII bytes only, so such a
-// sub-tile used to take the generic per-character scan, three to four times slower.  For a pattern none of whose atoms can
-// match a non-ASCII character and that has no anchors and no \b (header word 31, bit 17) such a character kills every
-// thread, as the end of the row does: the UNIT route can take the sub-tile -- units are runs of candidate / x bytes, ASCII
-// all of them -- provided a unit's scan ends at the unit's end (unit_take: clip) instead of reading the killer behind it.
-// This pass re-derives the candidate bits from the staged bytes with the bytes >= 0x80 taken out (the classification out
-// of the prefetch registers looks at their low seven bits) and says whether the sub-tile holds a NUL byte (then: generic).
-// Header word 31 bit 18 (mask in bits 19-23): the pattern's builtin classes (\w, \s, \d) do match some non-ASCII characters
-// -- those whose unicode flags meet the mask; the row lanes then walk their rows' non-ASCII characters: the sub-tile
-// qualifies when its UTF-8 is well formed inside every row and no character's flags meet the mask.
-__device__ __forceinline__ bool reclassify_high(const cstd::View& D, bool has_r2, const uint8_t* lds_in, int want, int lane, uint32_t* bitmap,
-                                                const uint8_t* flags, const uint8_t* row, int n) {
-  const unsigned fmask = (D.units >> 19) & 31u;
-  bool row_bad = false;
-  {
-    // aligned words of the row, only the bytes >= 0x80 looked at one by one (a lead byte checks its continuation bytes and
-    // covers them; a byte >= 0x80 that no lead covers is a stray one).  Also for the patterns such characters can only kill
-    // (bit 17): a lead byte WITHOUT its continuation bytes swallows the ASCII bytes behind it (regex_vm.h: char_at), which the
-    // unit route would scan -- count_re(b|ab) counted the b of `4\xc3b` (found by the soak, round 5)
-    const int al = (int)((uintptr_t)row & 3);
-    int covered = 0;  // row offsets below this one belong to a character already checked
-    for (int i = -al; i < n && !row_bad; i += 4) {
-      uint32_t h = *reinterpret_cast<const uint32_t*>(row + i) & 0x80808080u;
-      if (i < 0) h &= 0xFFFFFFFFu << (8 * -i);
-      if (i + 4 > n) h &= ~(0xFFFFFFFFu << (8 * (n - i)));
-      while (h && !row_bad) {
-        const int p = i + (__builtin_ctz(h) >> 3);
-        h &= h - 1;
-        if (p < covered) continue;
-        const uint8_t b = row[p];
-        const unsigned w = csrow::lead_width(b);
-        row_bad = w < 2 || p + (int)w > n;
-        for (unsigned k = 1; k < w && !row_bad; ++k) row_bad = !csrow::is_cont(row[p + (int)k]);
-        if (!row_bad) {
-          csrow::Char ch;
-          csrow::decode_at(row, p, n, ch);
-          const unsigned u = csrow::packed_to_cp(ch);
-          row_bad = ((D.units >> 18) & 1u) != 0 && u <= 0xFFFFu && (flags[u] & fmask) != 0;
-        }
-        covered = p + (int)w;
-      }
-    }
-  }
-  uint32_t zr = row_bad ? 0x80u : 0u;
-  for (int i = lane * 16; i < want; i += 64 * 16) {
-    const uint4 q = *reinterpret_cast<const uint4*>(lds_in + i);
-    zr |= ((q.x - 0x01010101u) & ~q.x) | ((q.y - 0x01010101u) & ~q.y) | ((q.z - 0x01010101u) & ~q.z) | ((q.w - 0x01010101u) & ~q.w);
-    uint32_t bits;
-    if (has_r2)
-      bits = cstile::gather16_bit7(cstd::Tdfa::cand_bits_ascii<true>(D, q.x) & ~q.x, cstd::Tdfa::cand_bits_ascii<true>(D, q.y) & ~q.y,
-                                   cstd::Tdfa::cand_bits_ascii<true>(D, q.z) & ~q.z, cstd::Tdfa::cand_bits_ascii<true>(D, q.w) & ~q.w);
-    else
-      bits = cstile::gather16_bit7(cstd::Tdfa::cand_bits_ascii<false>(D, q.x) & ~q.x, cstd::Tdfa::cand_bits_ascii<false>(D, q.y) & ~q.y,
-                                   cstd::Tdfa::cand_bits_ascii<false>(D, q.z) & ~q.z, cstd::Tdfa::cand_bits_ascii<false>(D, q.w) & ~q.w);
-    cstile::put_bits16(bitmap, i, bits);
-  }
-  cstile::wave_lds_fence();
-  // (a zero byte below a byte >= 0x80 may go unseen by the borrow trick's neighbour term; a byte >= 0x80 never looks like one)
-  return __any((zr & 0x80808080u) != 0);
-}
 
 
 // The backrefs template in registers (the replace kernel's BREFS form).  The struct lives in device memory; read per match
@@ -1125,44 +815,6 @@ __device__ __forceinline__ TemplateRegs template_regs(const csvm::BackrefTemplat
   r.pos8hi = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(hi >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)hi);
   return r;
 }
-
-// ---- the bit-parallel form (regex_bits.h): staging helpers shared by the stream kernels ------------------
-// LDS image of the form: the program words as built by the host, then 128 words of the SPREAD class table --
-// entry b holds byte b's class set with class k at bit 4k, so that the entries of four bytes, shifted by 0..3
-// and OR-ed, leave a nibble per class: the four bytes' membership bits.
-__device__ __forceinline__ const uint32_t* bits_stage(const int32_t* g_bits, int words, int32_t* lds) {
-  for (int i = threadIdx.x; i < words; i += blockDim.x) lds[i] = g_bits[i];
-  uint32_t* sp = reinterpret_cast<uint32_t*>(lds + ((words + 3) & ~3));
-  if (threadIdx.x < 128) {
-    const uint32_t set = ((uint32_t)g_bits[csbits::kHeaderWords + (threadIdx.x >> 2)] >> (8 * (threadIdx.x & 3))) & 255u;
-    sp[threadIdx.x] = csbits::spread_entry(set);
-  }
-  __syncthreads();
-  return sp;
-}
-__host__ __device__ inline int bits_lds_bytes(int words) { return ((words + 3) & ~3) * 4 + 128 * 4; }
-// sixteen staged bytes -> for every class the sixteen membership bits (regex_bits.h: classify16)
-__device__ __forceinline__ void bits_classify16(const uint32_t* spread, const uint4& q, uint32_t pair[4]) {
-  csbits::classify16(spread, q.x, q.y, q.z, q.w, pair);
-}
-// a row lane's mask of class k, shifted right by `off`: cut out of the class's bitmap on demand (regex_bits.h: cls(k, off))
-#define CS_BITS_CLS(bitmap, bm_words, p0, n)                                                                       \
-  [&](int k_, int off_) -> csbits::M96 {                                                                           \
-    uint32_t m0_, m1_, m2_;                                                                                        \
-    cstile::row_bits96((bitmap) + __builtin_amdgcn_readfirstlane(k_) * (bm_words), (p0) + off_, max((n) - off_, 0), m0_, m1_, m2_); \
-    return csbits::m96(m0_, m1_, m2_);                                                                             \
-  }
-// ... without the cut at the row's end (regex_bits.h: raw(k, off)): three funnel shifts over four words of the bitmap
-#define CS_BITS_RAW(bitmap, bm_words, p0)                                                                          \
-  [&](int k_, int off_) -> csbits::M96 {                                                                           \
-    const int q_ = (p0) + off_;                                                                                    \
-    const uint32_t* w_ = (bitmap) + __builtin_amdgcn_readfirstlane(k_) * (bm_words) + (q_ >> 5);                   \
-    const uint32_t a_ = w_[0], b_ = w_[1], c_ = w_[2], d_ = w_[3];                                                 \
-    const unsigned sh_ = (unsigned)q_ & 31u;                                                                       \
-    const uint32_t m0_ = __builtin_amdgcn_alignbit(b_, a_, sh_), m1_ = __builtin_amdgcn_alignbit(c_, b_, sh_),     \
-                   m2_ = __builtin_amdgcn_alignbit(d_, c_, sh_);                                                   \
-    return csbits::m96(m0_, m1_, m2_);                                                                             \
-  }
 
 // UNITS (with !INPLACE, RESCAN, !LONG): the scan runs per UNIT instead of per row (regex_tdfa.cpp, header word 31).
 // Row lanes cut their rows into units with bit arithmetic on two per-byte bitmaps (candidate bytes, bytes equal
@@ -2158,751 +1810,6 @@ __global__ void __launch_bounds__(256, ((BREFS && !CHAIN) || (BITS && IN_LDS)) ?
 }
 
 
-
-
-// ---- persistent contains_re / count_re over row tiles -----------------------------------
-// Same staging as the replace kernel (contiguous tile runs per wave, next tile's chars in
-// flight), no output assembly: LDS holds the DFA table and one input tile per wave, so seven
-// workgroups fit a CU.  MODE 0 contains_re, 2 count_re, 3 findall spans (begins / lens [k * rows + row]),
-// 4 extract spans (leftmost match, then Tdfa::group_find per capture group, all on the staged row),
-// 5 / 6 replace_with_backrefs sizes / bytes (csvm::row_backrefs on the staged row; the bytes go out per row lane).
-struct ScanStreamArgs {
-  ColView in;
-  const uint8_t* flags;
-  TLaunch L;
-  uint8_t* out8;
-  int32_t* out32;
-  unsigned long long* found;
-  long long nsub;
-  int cap_in, tbl_bytes;
-  int rows_per_tile;  // LONG variant: 64, 32 or 16
-  int32_t* begins;    // MODE 3, 4
-  int32_t* lens;
-  int ncols;
-  int* maxp;             // MODE 3 (optional): receives the largest match count of a row
-  // MODE 3, 4 (optional): the spans as ONE word per (column, row) -- begin << 16 | length, 0xFFFFFFFF = null -- instead of
-  // begins / lens (half the span traffic; rows of a tile are far shorter than 64 KiB), and the bytes every 64-row tile
-  // gives to each column, [column][tile] (rows_per_tile == 64 only): k_spans_write_tile2 sizes the columns from those
-  uint32_t* spans;
-  int32_t* tile_tot;
-  const int32_t* gtags;  // MODE 4, 5, 6: capture-group tag image
-  int gt_off, gt_words;  // when gt_words > 0 the image is staged into LDS at byte offset gt_off (inside tbl_bytes)
-  const csvm::BackrefTemplate* tmpl;  // MODE 5, 6 (device memory: indexed per reference, must not live in the kernel arguments)
-  const int64_t* out_off;      // MODE 6
-  uint8_t* out_chars;
-  // BITS: the bit-parallel form of the pattern (regex_bits.h), staged at byte offset bits_off of the LDS (inside tbl_bytes)
-  const int32_t* bits;
-  int bits_off, bits_words, bits_k;
-  // MODE 0 / 2, 64-row tiles (optional): rows that hold a byte >= 0x80 or a NUL are not scanned here -- their indices go to
-  // this list (k_tdfa_scan_list scans them afterwards, a thread a row), and the tile's other rows keep the form the launch was
-  // chosen for (bit form, chain arithmetic, unit scan, lean scan) instead of the whole sub-tile going to the row-by-row scan
-  int32_t* deferred;
-  unsigned* ndeferred;
-  unsigned deferred_cap;
-};
-// UNITS (MODE 0 and 2, !LONG): the unit scan of the replace kernel -- units queued by the row lanes, one unit per lane
-// whatever its row, the per-row result summed (count_re) / OR-ed (contains_re) in LDS.
-// CHAIN (a UNITS form, count_re / findall): the pattern is a chain and the column's sample holds no byte >= 0x80 -- the unit
-// and lean scans are compiled out, a sub-tile the chain arithmetic does not take is scanned row by row by the generic executor.
-// BITS (a CHAIN form, contains_re / count_re): the pattern has a bit-parallel form (regex_bits.h) and the column's sample holds
-// no byte >= 0x80 -- every staged byte is classified into one bitmap per character class by table lookup, the row lanes
-// read their rows' class masks and derive the matches by mask arithmetic; no automaton on a plain-ASCII sub-tile.
-template <int MODE, bool IN_LDS, bool LONG = false, bool UNITS = false, bool CHAIN = false, bool BITS = false>
-__global__ void __launch_bounds__(256, MODE == 4 ? ((CHAIN && !IN_LDS) ? 4 : 3) : CHAIN ? 4 : (UNITS && MODE == 3) ? 3 : (UNITS || MODE == 3) ? 4 : (MODE <= 1 && !LONG) ? 5 : 1) k_tdfa_scan_stream(ScanStreamArgs a) {
-  static_assert(!UNITS || ((MODE == 0 || MODE == 2 || MODE == 3 || (MODE == 4 && CHAIN)) && !LONG), "unit scan: contains_re / count_re / findall on rows within the 96-byte masks");
-  static_assert(!CHAIN || (UNITS && (MODE == 2 || MODE == 3 || MODE == 4 || (BITS && MODE == 0))), "the chain form: count_re / findall / extract");
-  static_assert(!BITS || (CHAIN && (MODE == 0 || MODE == 2)), "the bit form: contains_re / count_re");
-  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-  uint8_t* base = reinterpret_cast<uint8_t*>(smem);
-  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;  // (scalar: what derives from it stays in SGPRs)
-  const int bm_bytes = (a.cap_in >> 3) + 32;
-  const int nbm = BITS ? max(a.bits_k, 2) : 2;  // bitmaps per wave (BITS: one per character class)
-  // (MODE 4 keeps a lane-private byte per step of a group run behind the bitmap: regex_tdfa.h, group_find_back)
-  const int unit_bytes = UNITS ? (nbm - 1) * bm_bytes + kUnitQueue * 4 + 64 * 4 + 16 : (MODE == 4 ? cstd::Tdfa::kBackSteps * 64 + kMaxGroups * 4 : 0);  // x bitmap, unit queue, per-row results, bail word
-  uint8_t* lds_in = base + a.tbl_bytes + (size_t)wv * (a.cap_in + 32 + bm_bytes + unit_bytes + (((MODE == 0 || MODE == 2) && !LONG && a.deferred) ? bm_bytes + 64 * 4 : 0));
-  uint32_t* bitmap = reinterpret_cast<uint32_t*>(lds_in + a.cap_in + 32);
-  uint32_t* xbitmap = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(bitmap) + bm_bytes);
-  uint32_t* uqueue = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(bitmap) + (size_t)nbm * bm_bytes);
-  uint32_t* rowres = uqueue + kUnitQueue;
-  uint32_t* bailw = rowres + 64;
-  constexpr bool kDefer = (MODE == 0 || MODE == 2) && !LONG;
-  const bool deferring = kDefer && a.deferred != nullptr;  // (wave-uniform)
-  uint32_t* oddmap = reinterpret_cast<uint32_t*>(lds_in + a.cap_in + 32 + bm_bytes + unit_bytes);  // (behind everything else of the wave)
-  // the wave's rows put off and not yet in the list: one atomic on the list's counter per 64 of them at most (one per sub-tile
-  // with such a row was 600K on one address for the C5 column's pieces -- 2 ms of a 4 ms kernel)
-  int32_t* pend = reinterpret_cast<int32_t*>(reinterpret_cast<uint8_t*>(oddmap) + bm_bytes);
-  int npend = 0;  // (wave-uniform)
-  auto flush_pend = [&] {
-    cstile::wave_lds_fence();
-    unsigned at = 0;
-    if (lane == 0) at = atomicAdd(a.ndeferred, (unsigned)npend);
-    at = (unsigned)__builtin_amdgcn_readfirstlane((int)at);
-    if (lane < npend && at + (unsigned)lane < a.deferred_cap) a.deferred[at + lane] = pend[lane];
-    cstile::wave_lds_fence();
-    npend = 0;
-  };
-  // MODE 4: per group, the tile's bytes (the chain form keeps the "equals x" bitmap where the plain form has its history bytes)
-  uint32_t* gtot = UNITS ? rowres : reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(xbitmap) + cstd::Tdfa::kBackSteps * 64);
-  if (MODE == 4 && lane < kMaxGroups) gtot[lane] = 0;
-  const TCtx c = tsetup<IN_LDS>(a.L, a.flags, smem);
-  const cstd::View& D = c.D;
-  const csvm::ProgView& P = c.P;
-  const ColView& in = a.in;
-  if (MODE >= 4 && a.gt_words > 0) {  // the group-tag tables are read once per DFA step: keep them next to the DFA table
-    int32_t* g = reinterpret_cast<int32_t*>(base + a.gt_off);
-    for (int i = threadIdx.x; i < a.gt_words; i += blockDim.x) g[i] = a.gtags[i];
-    __syncthreads();
-    a.gtags = g;
-  }
-  const uint32_t* spread = nullptr;
-  csbits::View BV{};
-  if (BITS) {
-    int32_t* bl = reinterpret_cast<int32_t*>(base + a.bits_off);
-    spread = bits_stage(a.bits, a.bits_words, bl);
-    BV = csbits::make_view(bl);
-  }
-  const bool has_r2 = (((uint32_t)D.img[30] & 255u) <= (((uint32_t)D.img[30] >> 8) & 255u));
-  const uint32_t unit_x = (D.units >> 8) & 127u, unit_xpat = unit_x * 0x01010101u;
-  const int R = LONG ? a.rows_per_tile : 64;
-  const long long waves = (long long)gridDim.x * 4;
-  const long long per = (a.nsub + waves - 1) / waves;
-  long long tile = ((long long)blockIdx.x * 4 + wv) * per;
-  const long long tile_end = min(a.nsub, tile + per);
-  if (tile >= tile_end) return;
-  cstile::TileOffs cur = cstile::load_tile_offsets_r(in.offsets, in.rows, tile, R, lane);
-  cstile::TileOffs nxt = cur;
-  if (tile + 1 < tile_end) nxt = cstile::load_tile_offsets_r(in.offsets, in.rows, tile + 1, R, lane);
-  cstile::TileChars pf;
-#pragma unroll
-  for (int j = 0; j < cstile::kPfChunks; ++j) pf.v[j] = make_uint4(0, 0, 0, 0);
-  cstile::issue_chars(in.chars, cstile::rl64(cur.o0, 0), cstile::rl64(cur.o1, 63), lane, pf);
-  int hits = 0;
-  for (;;) {
-    const long long r0 = tile * R;
-    const int nrows = (int)min((long long)R, in.rows - r0);
-    const long long g0 = cstile::rl64(cur.o0, 0), g1 = cstile::rl64(cur.o1, 63);
-    const bool live0 = lane < nrows && row_is_valid(in.validity, r0 + lane);
-    const int rbeg = (int)(cur.o0 - g0);
-    const int n0 = live0 ? (int)(cur.o1 - cur.o0) : 0;
-    const int lead = (int)((uintptr_t)(in.chars + g0) & 15);
-    const int want = (int)(g1 - g0) + lead;
-    cstile::stage_chars(lds_in, want, lane, pf);
-    uint32_t odd = 0;
-#pragma unroll
-    for (int j = 0; j < cstile::kPfChunks; ++j)
-      if (j * 1024 + lane * 16 < want) {
-        const uint4 q = pf.v[j];
-        const uint32_t ox = q.x | ((q.x - 0x01010101u) & ~q.x), oy = q.y | ((q.y - 0x01010101u) & ~q.y);
-        const uint32_t oz = q.z | ((q.z - 0x01010101u) & ~q.z), ow = q.w | ((q.w - 0x01010101u) & ~q.w);
-        odd |= ox | oy | oz | ow;
-        if (deferring) cstile::put_bits16(oddmap, j * 1024 + lane * 16, cstile::gather16_bit7(ox & 0x80808080u, oy & 0x80808080u, oz & 0x80808080u, ow & 0x80808080u));
-        if (BITS) {
-          uint32_t pair[4];
-          bits_classify16(spread, q, pair);
-#pragma unroll
-          for (int k = 0; k < csbits::kMaxClasses; ++k)
-            if (k < BV.K) cstile::put_bits16(bitmap + k * (bm_bytes >> 2), j * 1024 + lane * 16, (pair[k >> 1] >> (16 * (k & 1))) & 0xFFFFu);
-          continue;
-        }
-        uint32_t bits;
-        if (has_r2)
-          bits = cstile::gather16_bit7(cstd::Tdfa::cand_bits_ascii<true>(D, q.x), cstd::Tdfa::cand_bits_ascii<true>(D, q.y), cstd::Tdfa::cand_bits_ascii<true>(D, q.z),
-                                       cstd::Tdfa::cand_bits_ascii<true>(D, q.w));
-        else
-          bits = cstile::gather16_bit7(cstd::Tdfa::cand_bits_ascii<false>(D, q.x), cstd::Tdfa::cand_bits_ascii<false>(D, q.y), cstd::Tdfa::cand_bits_ascii<false>(D, q.z),
-                                       cstd::Tdfa::cand_bits_ascii<false>(D, q.w));
-        cstile::put_bits16(bitmap, j * 1024 + lane * 16, bits);
-        if (UNITS && unit_x != 0) cstile::put_bits16(xbitmap, j * 1024 + lane * 16, unit_xbits16(q, unit_xpat));
-      }
-    const bool has_next = tile + 1 < tile_end;
-    // (the offsets two tiles ahead are fetched unconditionally, at a clamped index, and become `nxt` at the bottom of
-    // the iteration: see the note in k_tdfa_replace_stream)
-    const cstile::TileOffs nn = cstile::load_tile_offsets_r(in.offsets, in.rows, tile + 2 < tile_end ? tile + 2 : tile_end - 1, R, lane);
-    if (has_next) {
-      cur = nxt;
-      cstile::issue_chars(in.chars, cstile::rl64(cur.o0, 0), cstile::rl64(cur.o1, 63), lane, pf);
-    }
-    cstile::wave_lds_fence();
-    bool has_odd = __any((odd & 0x80808080u) != 0);
-    bool live = live0;
-    if (deferring && has_odd) {  // (wave-uniform)
-      uint32_t d0, d1, d2;
-      cstile::row_bits96(oddmap, lead + rbeg, n0 < 96 ? n0 : 96, d0, d1, d2);
-      // (a row beyond the masks is not looked at: the tile is scanned row by row as before)
-      const bool fits = !__any(live0 && n0 + ((lead + rbeg) & 3) > cstd::Tdfa::kMaskBytes);
-      const bool put_off = fits && live0 && (d0 | d1 | d2) != 0;
-      const unsigned long long who = __ballot(put_off);
-      if (who) {
-        const int k = __builtin_popcountll(who);
-        if (npend + k > 64) flush_pend();
-        if (put_off) pend[npend + __builtin_popcountll(who & ((1ull << lane) - 1ull))] = (int32_t)(r0 + lane);
-        npend += k;
-      }
-      if (fits) {
-        live = live0 && !put_off;
-        has_odd = false;  // (what is left of the tile is plain)
-        odd = 0;
-      }
-    }
-    const int n = live ? n0 : 0;
-    int v = 0;
-    if (MODE == 5 || MODE == 6) {
-      const uint8_t* p = lds_in + lead + rbeg;
-      cstd::Tdfa vm(D, P, p, n, (lead + rbeg) & 3);
-      auto find = [&](auto&& f) { csvm::walk_matches(vm, f); };
-      // the groups of a match come four at a time from ONE anchored run (regex_tdfa.h: group_find_all) and are kept
-      // until the walk moves to the next match: a template with four references costs one run, not four
-      int c_mb = -1, c_batch = -1, c_ok = 0, c_end = 0;
-      int c_gb[cstd::Tdfa::kGroupBatch], c_ge[cstd::Tdfa::kGroupBatch];
-      const int tgroups = a.tmpl->groups;
-      auto group = [&](int mb, int g, int& x, int& y) -> bool {
-        if (n >= 255 || !a.gtags) return g == 0 ? vm.find(mb, mb + 1, x, y) > 0 : vm.group_find(mb, a.gtags, g, x, y) > 0;
-        const int batch = g == 0 ? (c_mb == mb ? c_batch : 0) : (g - 1) / cstd::Tdfa::kGroupBatch;
-        if (c_mb != mb || c_batch != batch) {
-          const int first = batch * cstd::Tdfa::kGroupBatch + 1;
-          int cnt = tgroups - first + 1;
-          cnt = cnt < 0 ? 0 : (cnt > cstd::Tdfa::kGroupBatch ? cstd::Tdfa::kGroupBatch : cnt);
-          c_ok = vm.group_find_all(mb, a.gtags, first, cnt, c_gb, c_ge, c_end);
-          c_mb = mb;
-          c_batch = batch;
-        }
-        if (g == 0) {
-          x = mb;
-          y = c_end;
-        } else {
-          const int k = (g - 1) % cstd::Tdfa::kGroupBatch;
-#pragma unroll
-          for (int i = 0; i < cstd::Tdfa::kGroupBatch; ++i)
-            if (i == k) {
-              x = c_gb[i];
-              y = c_ge[i];
-            }
-        }
-        return c_ok > 0;
-      };
-      if (MODE == 5) {
-        int len = -1;
-        if (live) {
-          len = 0;
-          csvm::row_backrefs(p, n, *a.tmpl, find, group, [&](const uint8_t*, int k) { len += k; });
-        }
-        if (lane < nrows) a.out32[r0 + lane] = len;
-      } else if (live) {
-        uint8_t* o = a.out_chars + a.out_off[r0 + lane];
-        csvm::row_backrefs(p, n, *a.tmpl, find, group, [&](const uint8_t* q, int k) {
-          for (int i = 0; i < k; ++i) *o++ = q[i];
-        });
-      }
-    } else if (MODE == 1) {
-      // match (count.cu:113-165): the anchored run on the staged row -- the rows arrive through the same coalesced
-      // tiles as contains_re's instead of a thread per row reading its bytes from HBM
-      cstd::Tdfa vm(D, P, lds_in + lead + rbeg, n, (lead + rbeg) & 3);
-      v = live ? csvm::row_contains_re(vm, true) : 0;
-    } else if (MODE >= 7) {
-      // programs of five to eight live threads (MODE 7 contains_re, 8 match, 9 count_re): the generic executor with
-      // eight start offsets on the staged row (regex_tdfa.h: TdfaWide)
-      cstd::TdfaWide vm(D, P, lds_in + lead + rbeg, n, (lead + rbeg) & 3);
-      v = !live ? 0 : (MODE == 9 ? csvm::row_count_re(vm) : csvm::row_contains_re(vm, MODE == 8));
-    } else if (MODE == 4) {
-      cstd::Tdfa vm(D, P, lds_in + lead + rbeg, n, (lead + rbeg) & 3);
-      int mb = 0, me = 0;
-      bool chain_done = false;
-      if (CHAIN) {
-        // extract on a chain pattern whose groups are runs of items (regex_tdfa.h: chain_match, chain_group_bounds) on a
-        // sub-tile of plain ASCII: the row's first match and its group ranges from the row's two masks, no table walk
-        const bool plain = D.nskip > 0 && D.img[12] <= 4 && !__any((odd & 0x80808080u) != 0) && !__any(live && !vm.masks_fit());
-        if (plain && (D.chain >> 16) && (((uint32_t)D.img[30] >> 20) & 1u) && a.ncols <= 4 && a.spans) {  // (wave-uniform)
-          using namespace cstd;
-          uint32_t r0w, r1w, r2w, x0w = 0, x1w = 0, x2w = 0;
-          cstile::row_bits96(bitmap, lead + rbeg, n, r0w, r1w, r2w);
-          if (unit_x != 0) cstile::row_bits96(xbitmap, lead + rbeg, n, x0w, x1w, x2w);
-          const U128 Rm = u128(r0w | ((unsigned long long)r1w << 32), r2w), Xm = u128(x0w | ((unsigned long long)x1w << 32), x2w);
-          U128 S = u128(0, 0), E = u128(0, 0);
-          if (live) chain_match96(r0w, r1w, r2w, x0w, x1w, x2w, D.chain, D.img, S, E, D.sfx, n, [&](int i) { return lds_in[lead + rbeg + i]; });
-          const bool hit = live && u128_any(S);
-          v = hit;
-          int gb[4], ge[4];
-          chain_group_bounds(Rm, Xm, D.chain, D.img, (uint32_t)D.img[D.img[15] - 1], hit ? u128_ctz(S) : 0, gb, ge);
-          if (lane < nrows) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-              if (k < a.ncols) {
-                const bool ok = hit && gb[k] >= 0 && ge[k] > gb[k];
-                a.spans[(long long)k * in.rows + r0 + lane] = ok ? (((uint32_t)gb[k] << 16) | (uint32_t)(ge[k] - gb[k])) : 0xFFFFFFFFu;
-                if (a.tile_tot && ok) __hip_atomic_fetch_add(gtot + k, (uint32_t)(ge[k] - gb[k]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-              }
-          }
-          chain_done = true;
-        }
-      }
-      if (__builtin_expect(!chain_done, !CHAIN)) {  // (the chain form: a cold path)
-      // leftmost match: the lean scan on ASCII tiles of short rows (as contains_re), else the generic find
-      const bool lean = !LONG && D.nskip > 0 && D.img[12] <= 4 && !__any((odd & 0x80808080u) != 0) && !__any(live && !vm.masks_fit());
-      int f = -1;
-      if (lean && live) {
-        uint32_t m0, m1, m2;
-        cstile::row_bits96(bitmap, lead + rbeg, n, m0, m1, m2);
-        f = vm.scan_lean_first(m0, m1, m2, [&](int b0, int e0, int) {
-          mb = b0;
-          me = e0;
-        });
-      }
-      if (live && f < 0) f = vm.find(0, n, mb, me);
-      const bool hit = live && f > 0;
-      v = hit;
-      if (lane < nrows) {
-        if (n < 255) {  // every group of the match from one anchored run, four at a time (regex_tdfa.h: group_find_all)
-          for (int g0 = 0; g0 < a.ncols; g0 += cstd::Tdfa::kGroupBatch) {
-            int gb[cstd::Tdfa::kGroupBatch], ge[cstd::Tdfa::kGroupBatch], mend = 0;
-            const int cnt = min(cstd::Tdfa::kGroupBatch, a.ncols - g0);
-            // (backwards from the match where that applies -- short ASCII matches: regex_tdfa.h -- else the forward run)
-            int got = -1;
-            if (!UNITS && hit) got = vm.group_find_back(mb, a.gtags, g0 + 1, cnt, gb, ge, mend, cstd::Tdfa::HistBytes{reinterpret_cast<uint8_t*>(xbitmap) + lane, 64});
-            if (hit && got < 0) got = vm.group_find_all(mb, a.gtags, g0 + 1, cnt, gb, ge, mend);
-            const bool found = hit && got > 0;
-#pragma unroll
-            for (int k = 0; k < cstd::Tdfa::kGroupBatch; ++k)
-              if (k < cnt) {
-                const bool ok = found && gb[k] >= 0 && ge[k] > gb[k];
-                if (a.spans) {
-                  a.spans[(long long)(g0 + k) * in.rows + r0 + lane] = ok ? (((uint32_t)gb[k] << 16) | (uint32_t)(ge[k] - gb[k])) : 0xFFFFFFFFu;
-                } else {
-                  a.begins[(long long)(g0 + k) * in.rows + r0 + lane] = ok ? gb[k] : 0;
-                  a.lens[(long long)(g0 + k) * in.rows + r0 + lane] = ok ? ge[k] - gb[k] : -1;
-                }
-                if (a.tile_tot && ok) __hip_atomic_fetch_add(gtot + g0 + k, (uint32_t)(ge[k] - gb[k]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-              }
-          }
-        } else {
-          for (int g = 0; g < a.ncols; ++g) {
-            int x = -1, y = -1;
-            const bool ok = hit && vm.group_find(mb, a.gtags, g + 1, x, y) && x >= 0 && y > x;
-            if (a.tile_tot && ok) __hip_atomic_fetch_add(gtot + g, (uint32_t)(y - x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-            if (a.spans) {
-              a.spans[(long long)g * in.rows + r0 + lane] = ok ? (((uint32_t)x << 16) | (uint32_t)(y - x)) : 0xFFFFFFFFu;
-            } else {
-              a.begins[(long long)g * in.rows + r0 + lane] = ok ? x : 0;
-              a.lens[(long long)g * in.rows + r0 + lane] = ok ? y - x : -1;
-            }
-          }
-        }
-      }
-      }  // (!chain_done)
-      if (a.tile_tot) {  // the bytes this tile gives to each group's column (summed in LDS by the row lanes above)
-        cstile::wave_lds_fence();
-        if (lane < a.ncols) {
-          a.tile_tot[(long long)lane * a.nsub + tile] = (int32_t)gtot[lane];
-          gtot[lane] = 0;
-        }
-        cstile::wave_lds_fence();
-      }
-    } else {
-      cstd::Tdfa vm(D, P, lds_in + lead + rbeg, n, (lead + rbeg) & 3);
-      bool hi_units = false;  // (bytes >= 0x80 that can only kill: the unit route alone -- reclassify_high)
-      if (!CHAIN && UNITS && (MODE == 0 || MODE == 2 || MODE == 3) && has_odd && ((D.units >> 17) & 3u) && (D.units & 1u))
-        hi_units = !reclassify_high(D, has_r2, lds_in, want, lane, bitmap, a.flags, lds_in + lead + rbeg, n);
-      const bool lean = D.nskip > 0 && D.img[12] <= 4 && (!has_odd || hi_units) &&
-                        !__any(live && (LONG ? n > cstd::Tdfa::kLongBytes : !vm.masks_fit()));
-      bool redo = live && !lean;
-      int k = 0;  // MODE 3: matches reported so far
-      int cl[4] = {0, 0, 0, 0};  // (packed spans: the lengths of the row's first four matches, for the tile's column totals)
-      auto span = [&](int mb, int me, int) {
-        if (k < a.ncols) {
-          if (a.spans) {
-            a.spans[(long long)k * in.rows + r0 + lane] = ((uint32_t)mb << 16) | (uint32_t)(me - mb);
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-              if (c == k) cl[c] = me - mb;
-          } else {
-            a.begins[(long long)k * in.rows + r0 + lane] = mb;
-            a.lens[(long long)k * in.rows + r0 + lane] = me - mb;
-          }
-        }
-        ++k;
-      };
-      bool units_done = false;
-      if (UNITS && MODE == 3) {
-        // findall: the units leave each match's first and last byte in the two bitmaps (as in the replace kernel);
-        // the row lanes read their matches back in order
-        if (lean && !has_odd && (D.chain >> 16)) {  // (wave-uniform) a chain pattern on plain ASCII: regex_tdfa.h, chain_match
-          using namespace cstd;
-          uint32_t r0, r1, r2, x0 = 0, x1 = 0, x2 = 0;
-          cstile::row_bits96(bitmap, lead + rbeg, n, r0, r1, r2);
-          if (unit_x != 0) cstile::row_bits96(xbitmap, lead + rbeg, n, x0, x1, x2);
-          if (live) {
-            U128 S, E;
-            chain_match96(r0, r1, r2, x0, x1, x2, D.chain, D.img, S, E, D.sfx, n, [&](int i) { return lds_in[lead + rbeg + i]; });
-            while (u128_any(S)) {
-              const int mb = u128_ctz(S), me = u128_ctz(E) + 1;
-              S = u128_clear_lowest(S);
-              E = u128_clear_lowest(E);
-              span(mb, me, 0);
-            }
-            v = k;
-          }
-          redo = false;
-          units_done = true;
-        } else if (!CHAIN && lean && (D.units & 1u)) {  // (wave-uniform)
-          using namespace cstd;
-          uint32_t m0, m1, m2;
-          const int total_units = unit_discover(D, bitmap, xbitmap, lead + rbeg, n, lane, uqueue, m0, m1, m2, [&] {
-            for (int i = lane * 16; i < bm_bytes; i += 64 * 16) {
-              *reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(bitmap) + i) = make_uint4(0, 0, 0, 0);
-              *reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(xbitmap) + i) = make_uint4(0, 0, 0, 0);
-            }
-            if (lane < 2) bailw[lane] = 0;
-          });
-          if (total_units >= 0) {
-            for (int u0 = 0; u0 < total_units; u0 += 64) {
-              const bool act = u0 + lane < total_units;
-              int r, rbeg_r, n_r;
-              uint32_t c0, c1, c2;
-              unit_take(act ? uqueue[u0 + lane] : 0u, rbeg, n, m0, m1, m2, r, rbeg_r, n_r, c0, c1, c2, hi_units);
-              if (act) {
-                const int pu = lead + rbeg_r;
-                cstd::Tdfa vu(D, P, lds_in + pu, n_r, pu & 3);
-                bool ubail = false;
-                auto recu = [&](int mb, int me, int) {
-                  const int ps = pu + mb, pe = pu + me - 1;
-                  __hip_atomic_fetch_or(bitmap + (ps >> 5), 1u << (ps & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                  __hip_atomic_fetch_or(xbitmap + (pe >> 5), 1u << (pe & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                };
-                vu.scan_lean_dispatch(-1, c0, c1, c2, recu, ubail);
-                if (ubail) __hip_atomic_fetch_or(bailw + (r >> 5), 1u << (r & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-              }
-            }
-            cstile::wave_lds_fence();
-            uint32_t s0, s1, s2, e0, e1, e2;
-            cstile::row_bits96(bitmap, lead + rbeg, n, s0, s1, s2);
-            cstile::row_bits96(xbitmap, lead + rbeg, n, e0, e1, e2);
-            const bool rbail = ((bailw[lane >> 5] >> (lane & 31)) & 1u) != 0;
-            if (live && !rbail) {
-              U128 S = u128(s0 | ((unsigned long long)s1 << 32), s2), E = u128(e0 | ((unsigned long long)e1 << 32), e2);
-              while (u128_any(S)) {
-                const int mb = u128_ctz(S), me = u128_ctz(E) + 1;
-                S = u128_clear_lowest(S);
-                E = u128_clear_lowest(E);
-                span(mb, me, 0);
-              }
-              v = k;
-            }
-            redo = live && rbail;  // (such a row is scanned whole)
-            units_done = true;
-          }
-        }
-      } else if (UNITS) {
-        // (contains_re stops at a row's first match: its ASCII tiles keep the row lanes' scan -- scanning every unit cost more
-        // than the balance won --, the unit route serves its tiles with bytes >= 0x80, which the row lanes' scan cannot take)
-        if (BITS && !has_odd && !__any(live && n > csbits::kMaxRowBytes)) {  // (wave-uniform) plain ASCII, rows within the masks
-          using namespace cstd;
-          auto cls = CS_BITS_CLS(bitmap, bm_bytes >> 2, lead + rbeg, n);
-          auto raw = CS_BITS_RAW(bitmap, bm_bytes >> 2, lead + rbeg);
-          if (MODE == 0) {
-            v = live && csbits::contains(BV, cls, raw, n) ? 1 : 0;
-          } else {
-            U128 S = u128(0, 0), E;
-            if (live) csbits::match(BV, cls, raw, n, S, E);
-            v = u128_popc(S);
-          }
-          redo = false;
-          units_done = true;
-        } else if (!BITS && lean && !has_odd && (D.chain >> 16)) {  // (wave-uniform) a chain pattern on plain ASCII: regex_tdfa.h, chain_match
-          using namespace cstd;
-          uint32_t r0, r1, r2, x0 = 0, x1 = 0, x2 = 0;
-          cstile::row_bits96(bitmap, lead + rbeg, n, r0, r1, r2);
-          if (unit_x != 0) cstile::row_bits96(xbitmap, lead + rbeg, n, x0, x1, x2);
-          const U128 R = u128(r0 | ((unsigned long long)r1 << 32), r2), X = u128(x0 | ((unsigned long long)x1 << 32), x2);
-          if (MODE == 0 && !(D.chain & kChainLeadB)) {  // (a `\b` in front of the chain is checked per match: chain_match)
-            v = live && u128_any(chain_suffix_filter(chain_ends(R, X, D.chain, D.img), D.chain, D.sfx, n, [&](int i) { return lds_in[lead + rbeg + i]; })) ? 1 : 0;
-          } else if (MODE == 0) {
-            U128 S = u128(0, 0), E;
-            if (live) chain_match96(r0, r1, r2, x0, x1, x2, D.chain, D.img, S, E, D.sfx, n, [&](int i) { return lds_in[lead + rbeg + i]; });
-            v = u128_any(S) ? 1 : 0;
-          } else {
-            U128 S = u128(0, 0), E;
-            if (live) chain_match96(r0, r1, r2, x0, x1, x2, D.chain, D.img, S, E, D.sfx, n, [&](int i) { return lds_in[lead + rbeg + i]; });
-            v = u128_popc(S);
-          }
-          redo = false;
-          units_done = true;
-        } else if (!CHAIN && lean && (D.units & 1u) && (MODE != 0 || hi_units)) {  // (wave-uniform)
-          constexpr int KIND = MODE == 0 ? cstd::Tdfa::K_CONTAINS : cstd::Tdfa::K_COUNT;
-          uint32_t m0, m1, m2;
-          const int total_units = unit_discover(D, bitmap, xbitmap, lead + rbeg, n, lane, uqueue, m0, m1, m2, [&] {
-            rowres[lane] = 0;
-            if (lane < 2) bailw[lane] = 0;
-          });
-          if (total_units >= 0) {
-            for (int u0 = 0; u0 < total_units; u0 += 64) {
-              const bool act = u0 + lane < total_units;
-              int r, rbeg_r, n_r;
-              uint32_t c0, c1, c2;
-              unit_take(act ? uqueue[u0 + lane] : 0u, rbeg, n, m0, m1, m2, r, rbeg_r, n_r, c0, c1, c2, hi_units);
-              if (act) {
-                const int pu = lead + rbeg_r;
-                cstd::Tdfa vu(D, P, lds_in + pu, n_r, pu & 3);
-                const int got = vu.template scan_lean_count<KIND>(c0, c1, c2);
-                if (got < 0) __hip_atomic_fetch_or(bailw + (r >> 5), 1u << (r & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                else if (got > 0 && MODE == 0) __hip_atomic_fetch_or(rowres + r, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                else if (got > 0) __hip_atomic_fetch_add(rowres + r, (uint32_t)got, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-              }
-            }
-            cstile::wave_lds_fence();
-            v = live ? (int)rowres[lane] : 0;
-            redo = live && ((bailw[lane >> 5] >> (lane & 31)) & 1u) != 0;  // (such a row is scanned whole)
-            units_done = true;
-          }
-        }
-      }
-      if (hi_units && !units_done) redo = live;  // (never the lean scan over whole rows of such a tile)
-      if (CHAIN && !units_done) redo = live;       // (the generic scan)
-      if (!CHAIN && !units_done && lean && !hi_units && live) {
-        uint32_t m0, m1, m2;
-        constexpr int KIND = MODE == 0 ? cstd::Tdfa::K_CONTAINS : cstd::Tdfa::K_COUNT;
-        if (LONG) {
-          const int p0 = lead + rbeg;
-          cstile::row_bits96(bitmap, p0, min(n, 96), m0, m1, m2);
-          auto refill = [&](int wb, uint32_t& x0, uint32_t& x1, uint32_t& x2) {
-            cstile::row_bits96(bitmap, p0 + wb, min(n - wb, 96), x0, x1, x2);
-          };
-          if (MODE == 3) v = vm.scan_lean_spans_long(m0, m1, m2, span, refill);
-          else v = vm.template scan_lean_count_long<KIND>(m0, m1, m2, refill);
-        } else {
-          cstile::row_bits96(bitmap, lead + rbeg, n, m0, m1, m2);
-          if (MODE == 3) v = vm.scan_lean_spans(m0, m1, m2, span);
-          else v = vm.template scan_lean_count<KIND>(m0, m1, m2);
-        }
-        redo = v < 0;
-      }
-      // (count_re / findall: a cold path, and saying so straightens the hot one -- findall 6.3 -> 5.7 ms; contains_re measured
-      // slower with the hint, 2.09 -> 2.22, and keeps the plain branch)
-      if ((MODE == 2 || MODE == 3) ? __builtin_expect(__any(redo), 0) : __any(redo)) {
-        if (redo) {
-          if (MODE == 3) {
-            k = 0;  // (the spans reported so far are written again, identically)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) cl[c] = 0;
-            v = csvm::row_findall(vm, [&](int, int mb, int me) {
-              span(mb, me, 1);
-              return true;
-            });
-          } else {
-            v = MODE == 2 ? csvm::row_count_re(vm) : csvm::row_contains_re(vm, false);
-          }
-        }
-      }
-      if (MODE == 3 && lane < nrows) {
-        if (a.spans)
-          for (int j = live ? k : 0; j < a.ncols; ++j) a.spans[(long long)j * in.rows + r0 + lane] = 0xFFFFFFFFu;
-        else
-          for (int j = live ? k : 0; j < a.ncols; ++j) a.lens[(long long)j * in.rows + r0 + lane] = -1;
-      }
-      if (MODE == 3 && a.tile_tot) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-          if (c < a.ncols) {
-            // (most tiles give the later columns nothing: no reduction then)
-            const int t = __any(live && k > c) ? wave_reduce_sum(live ? cl[c] : 0) : 0;
-            if (lane == 0) a.tile_tot[(long long)c * a.nsub + tile] = t;
-          }
-        // (columns beyond the fourth -- rows with many matches, `[a-z]+` on log lines: eighteen --: no registers kept their lengths;
-        // every lane reads its own spans back, just written, and the wave adds them up.  The exact-width pass then leaves packed
-        // spans and tile totals like the provisional one, where it used to write begins / lens for a scan over the lengths of
-        // every column: findall([a-z]+) on the C3 column 31.8 ms)
-        for (int c = 4; c < a.ncols; ++c) {
-          int t = 0;
-          if (__any(live && k > c)) {  // (wave-uniform)
-            const uint32_t w = (live && k > c) ? a.spans[(long long)c * in.rows + r0 + lane] : 0u;
-            t = wave_reduce_sum((int)(w & 0xFFFFu));
-          }
-          if (lane == 0) a.tile_tot[(long long)c * a.nsub + tile] = t;
-        }
-      }
-      if (MODE == 3 && a.maxp) {
-        int m = live ? k : 0;
-        for (int o = 32; o > 0; o >>= 1) m = max(m, __shfl_xor(m, o));
-        // (only a wave that would raise the maximum issues the same-address atomic)
-        if (lane == 0 && m > __hip_atomic_load(a.maxp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(a.maxp, m);
-      }
-    }
-    if (lane < nrows) {
-      if (MODE == 2 || MODE == 9) a.out32[r0 + lane] = v;
-      else if (MODE == 0 || MODE == 1 || MODE == 7 || MODE == 8) a.out8[r0 + lane] = (uint8_t)v;
-    }
-    hits += v > 0;
-    cstile::wave_lds_fence();  // the next tile overwrites lds_in
-    if (!has_next) break;
-    ++tile;
-    nxt = nn;
-  }
-  if (kDefer && npend > 0) flush_pend();
-  const int t = wave_reduce_sum(hits);
-  if (lane == 0 && t) atomicAdd(a.found, (unsigned long long)t);
-}
-
-struct TPlan {
-  TLaunch d;
-  size_t lds_bytes;
-  unsigned grid;
-};
-// the tagged DFA with at most four live threads: every DFA kernel (lean scans, unit decomposition, capture groups)
-bool use_tdfa(const cs_regex* re) { return !re->tdfa.empty() && re->tdfa[12] <= cstd::kMaxSlots && !cs::cfg("CS_REGEX_NO_TDFA"); }
-// ... with five to eight (counted repetitions): contains_re / match / count_re and replace_re run it on the generic executor
-// with eight start offsets (regex_tdfa.h: TdfaWide); the other ops keep the list simulator for such programs
-bool use_tdfa_wide(const cs_regex* re) { return !re->tdfa.empty() && re->tdfa[12] > cstd::kMaxSlots && !cs::cfg("CS_REGEX_NO_TDFA"); }
-// The bit-parallel form (regex_bits.h) is taken when the pattern has one, is no chain (chains run on two SWAR-classified
-// bitmaps, cheaper than the class-table lookup), the column's sample is plain ASCII, and the automaton's candidate bytes --
-// the bytes at which its idle skip has to stop -- make up a good part of the column's sample: with few candidates the lean
-// scans skip most of every row and win; with candidates everywhere (alternations of word-bounded literals, small sets in
-// a `+` loop) they walk every byte in a dependent chain of table reads (VERDICT r4 missing #3: 8.9 / 21.4 ms on C3).
-// Thresholds from tools/probe_bits.py on the C3 column (profiles/r05/probe_bits.txt): share of candidate bytes -> bits / automaton ms
-//   contains_re: 86.6 % ([^ ]+) 2.15 / 1.82 (a match at once: the first-match scan wins), 11.9 % ([aeiou]+) 2.2 / 4.4, 7.2 % (the
-//   gtest pattern) 3.9 / 8.9, 2.4 % with three live threads (cat|cot|cut) 3.3 / 5.3, 2.4-2.6 % with one 2.3-2.7 / 2.5-2.7, below 1 % 2.3-3.3 / 1.4-2.9
-//   count_re:    from 2 % up the bit form wins or ties (1.9 / 41.6 at 11.9 %, 2.5 / 4.1 at 2.4 %), below 1 % it loses (2.2 / 1.6)
-//   replace_re:  (two workgroups a CU against three) 7.3 / 21.4 at 7.2 %, 8.6 / 51.7 at 11.9 %, 6.4 / 9.3 at 2.4 % with three threads;
-//   5.4-5.8 / 4.6-4.9 at 2.4 % with one thread
-enum { BITS_CONTAINS = 0, BITS_COUNT = 2, BITS_REPLACE = 3 };
-// the share of the column's sampled bytes at which the automaton's idle skip has to stop
-double candidate_share(const cs_regex* re, const cs_column* col, hipStream_t s) {
-  if (re->tdfa.empty()) return 1.0;
-  const uint32_t* hist = sample_byte_hist(col, s);
-  uint64_t all = 0, cand = 0;
-  for (unsigned c = 0; c < 256; ++c) {
-    all += hist[c];
-    if (c < 128 && (((uint32_t)re->tdfa[21 + (c >> 5)] >> (c & 31)) & 1u)) cand += hist[c];
-  }
-  return all ? (double)cand / (double)all : 0.0;
-}
-// Rows with a byte >= 0x80 or a NUL, by the column's sample: are they few enough (at most about one row in thirty -- an upper
-// bound: every lead byte and every NUL counted as a row of its own) for a scan to put them off (ScanStreamArgs::deferred) and run
-// as on plain ASCII?  (Measured on the C2 column, one row in twenty: the bit form's ops gain -- gtest contains_re 1.08 -> 0.57 ms,
-// replace_re 2.31 -> 1.56 --, but a pattern whose generic scan is slow pays more for its rows on the list, a thread each, than the
-// sub-tiles cost row by row: `[a-z]+ing\b` replace_re 3.9 -> 5.6, `\d+` 0.72 -> 1.35.  At one row in 170 -- C5 -- everything gains.)
-bool odd_rows_few(const cs_column* col, hipStream_t s) {
-  if (cs::cfg("CS_NO_DEFERRED_ROWS") || col->rows == 0) return false;
-  const uint32_t* hist = sample_byte_hist(col, s);
-  uint64_t all = 0, oddb = hist[0];
-  for (unsigned c = 0; c < 256; ++c) {
-    all += hist[c];
-    if (c >= 0xC0) oddb += hist[c];  // (one lead byte a character; a stray continuation byte has no lead in front of it -- rare enough not to matter for a hint)
-  }
-  if (all == 0) return false;
-  return (double)oddb / (double)all * ((double)col->nbytes / (double)col->rows) <= cs::cfg_int("CS_ODD_ROWS_PERMILLE", 30) / 1000.0;
-}
-bool bits_route(const cs_regex* re, const cs_column* col, hipStream_t s, int op, bool high_ok = false) {
-  if (re->bits.empty() || cs::cfg("CS_NO_BITS_FORM")) return false;
-  if (!re->tdfa.empty() && ((re->tdfa[30] >> 16) & 15) != 0) return false;  // a chain
-  if (sample_has_high_bytes(col, s) && !high_ok) return false;
-  if (cs::cfg("CS_BITS_ALWAYS")) return true;
-  if (re->tdfa.empty()) return true;  // (no automaton: the list simulator is the alternative)
-  const uint32_t* hist = sample_byte_hist(col, s);
-  uint64_t all = 0, cand = 0;
-  for (unsigned c = 0; c < 128; ++c) {
-    all += hist[c];
-    if (((uint32_t)re->tdfa[21 + (c >> 5)] >> (c & 31)) & 1u) cand += hist[c];
-  }
-  if (cs::cfg("CS_STREAM_INFO"))
-    fprintf(stderr, "bits route: candidates %.2f %% of the sample (%d classes, %d alternatives, %d states, %d threads)\n", all ? 100.0 * (double)cand / (double)all : 0.0,
-            re->bits[1], re->bits[3], re->tdfa[1], re->tdfa[12]);
-  if (all == 0) return false;
-  const double f = (double)cand / (double)all;
-  const bool threads3 = re->tdfa[12] >= 3;
-  if (op == BITS_COUNT) return f >= 0.02;
-  // (the C5 column's pieces, the gtest pattern, 4.8 %: 4.0 / 7.1 -- the line between the 2.4 % tie and 7.2 % moved from 5 % to 3.5 %)
-  // (candidates everywhere and assertions behind the `+` loop -- `[^ ]+$` --: the first-match scan does not "find a match at once",
-  // it fails at every start: 8.4 ms on the C3 column against the bit form's 2.3)
-  const bool tail = (re->bits[2] & csbits::F_TAIL) != 0;
-  if (op == BITS_CONTAINS) return (f >= 0.035 && (f <= 0.5 || tail)) || (threads3 && f >= 0.02 && f <= 0.5);
-  // (a pattern whose shortest match is one byte matches at most of its candidates: the automaton's routes then pay per match --
-  // replace_re('e') on the C3 column, 4 % candidates: units 7.65, the bit form 6.45 ms)
-  return f >= 0.05 || ((threads3 || re->tdfa[13] == 1) && f >= 0.02);
-}
-void upload(cs_regex* re, hipStream_t s) {
-  // a compiled pattern may be shared between host threads (and is kept in the process-wide pattern cache): the device
-  // images are made once.  All three are built into locals and committed together only after the copies completed --
-  // an allocation or copy that throws half way must not leave d_image set with the DFA images missing (the guard
-  // below would then skip the upload for every later caller of the cached pattern).
-  static std::mutex mu;
-  std::lock_guard<std::mutex> lk(mu);
-  if (re->d_image) return;
-  Buf image = dev_alloc(re->image.size() * 4, s), tdfa, gtags, bits;
-  CS_HIP(hipMemcpyAsync(image->p, re->image.data(), re->image.size() * 4, hipMemcpyHostToDevice, s));
-  if (!re->bits.empty()) {
-    bits = dev_alloc(re->bits.size() * 4, s);
-    CS_HIP(hipMemcpyAsync(bits->p, re->bits.data(), re->bits.size() * 4, hipMemcpyHostToDevice, s));
-  }
-  if (!re->tdfa.empty()) {
-    tdfa = dev_alloc(re->tdfa.size() * 4, s);
-    CS_HIP(hipMemcpyAsync(tdfa->p, re->tdfa.data(), re->tdfa.size() * 4, hipMemcpyHostToDevice, s));
-    if (!re->gtags.empty()) {
-      gtags = dev_alloc(re->gtags.size() * 4, s);
-      CS_HIP(hipMemcpyAsync(gtags->p, re->gtags.data(), re->gtags.size() * 4, hipMemcpyHostToDevice, s));
-    }
-  }
-  CS_HIP(hipStreamSynchronize(s));
-  re->d_tdfa = std::move(tdfa);
-  re->d_gtags = std::move(gtags);
-  re->d_bits = std::move(bits);
-  re->d_image = std::move(image);  // (last: it is what the guard looks at)
-}
-TPlan tplan(cs_regex* re, int64_t rows, hipStream_t s) {
-  require_device();
-  upload(re, s);
-  if (!re->d_tdfa) fail(CS_ERR_INTERNAL, "regex: the tagged-DFA image is not on the device");
-  TPlan pl{};
-  pl.d.tdfa = ptr<const int32_t>(re->d_tdfa);
-  pl.d.tdfa_words = (int)re->tdfa.size();
-  pl.d.image = ptr<const int32_t>(re->d_image);
-  pl.d.in_lds = re->tdfa.size() * 4 <= kLdsBudget && !cs::cfg("CS_TDFA_GLOBAL_TABLE");
-  pl.lds_bytes = pl.d.in_lds ? ((re->tdfa.size() * 4 + 15) & ~size_t(15)) : 0;
-  int64_t nblk = (rows + 255) / 256;
-  pl.grid = (unsigned)std::min<int64_t>(std::max<int64_t>(nblk, 1), 256 * 8);
-  return pl;
-}
-
-Plan plan(cs_regex* re, int64_t rows, hipStream_t s) {
-  require_device();
-  upload(re, s);
-  Plan pl{};
-  Launch& L = pl.d;
-  L.image = ptr<const int32_t>(re->d_image);
-  L.image_words = (int)re->image.size();
-  const int ninst = (int)re->prog.insts.size();
-  pl.small = ninst <= 64;
-  L.slots = csvm::vm_slots(ninst);
-  const size_t img_bytes = (((size_t)L.image_words + 3) & ~size_t(3)) * 4;
-  L.image_in_lds = img_bytes <= kLdsBudget / 2;
-  L.arena = nullptr;
-  pl.threads = 0;
-  for (int t : {256, 128, 64}) {
-    size_t need = (L.image_in_lds ? img_bytes : 0) + (size_t)t * L.slots * 4;
-    if (need <= kLdsBudget) {
-      pl.threads = t;
-      pl.lds_bytes = need;
-      break;
-    }
-  }
-  if (pl.threads) {
-    int64_t nblk = (rows + pl.threads - 1) / pl.threads;
-    pl.grid = (unsigned)std::min<int64_t>(nblk, 256 * 16);
-  } else {
-    // lists in a global arena, one region per resident workgroup
-    pl.threads = 256;
-    pl.lds_bytes = L.image_in_lds ? img_bytes : 0;
-    int64_t nblk = (rows + pl.threads - 1) / pl.threads;
-    pl.grid = (unsigned)std::min<int64_t>(nblk, 256 * 4);
-    if (pl.grid == 0) pl.grid = 1;
-    size_t bytes = (size_t)pl.grid * pl.threads * L.slots * 4;
-    pl.arena_buf = dev_alloc(bytes, s);
-    L.arena = ptr<uint32_t>(pl.arena_buf);
-  }
-  if (pl.grid == 0) pl.grid = 1;
-  return pl;
-}
-
-// Rows per tile and staging capacity for the stream kernels: 64 rows when their widest span fits
-// the prefetch registers and no row outgrows the 96-byte candidate masks; otherwise the long-row
-// variants (rows up to 255 bytes) with 64, 32 or 16 rows per tile.  R == 0: no stream kernel.
 // matches per tile of R rows out of count_re's per-row counts: the column's total and the busiest tile's (replace_re with a
 // growing replacement sizes its out tile and its output from them instead of provisioning for the worst case)
 __global__ void __launch_bounds__(256) k_match_stats(const int32_t* __restrict__ counts, int64_t rows, int R, unsigned long long* __restrict__ total, unsigned* __restrict__ tilemax) {
@@ -2923,491 +1830,7 @@ __global__ void __launch_bounds__(256) k_match_stats(const int32_t* __restrict__
   }
 }
 
-__global__ void k_counts_to_flags(const int32_t* __restrict__ counts, int64_t rows, uint8_t* __restrict__ flags) {
-  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (r < rows) flags[r] = counts[r] > 0 ? 1 : 0;
-}
-
-struct TileChoice {
-  int R, cap;
-  bool lng;
-  int64_t span;  // the largest span of R consecutive rows (cap = that plus slack, rounded up to 128)
-};
-// `small`: also tiles of eight and four rows, also for rows beyond the sliding window (replace_re: its alternative is the
-// two-pass thread-per-row kernels; the scans' row-wise kernels beat such tiles: contains_re 1.9 against 4.6 ms, findall 27
-// against 64 ms on 520-byte rows)
-// (replace_re on 64-row tiles of up to 8 KB for long rows -- eight prefetch chunks a lane -- was built and measured in round 6:
-// 14.5 ms on the C5 column either way.  What such a column waits for is its tiles' PREFIXES, and twice the work per tile does
-// not shorten that; nor does drawing the tickets an iteration later (4.33 ms on C3, 14.7 on C5 either way): profiles/r06/prefix_latency.txt.)
-TileChoice choose_tile(const cs_column* col, hipStream_t s, bool small = false) {
-  const int64_t longest = max_row_bytes(col, s);
-  auto cap_of = [](int64_t span) { return (int64_t)((span + 15 + 32 + 127) & ~(int64_t)127); };
-  const int64_t span64 = max_span64(col, s);
-  const int64_t cap64 = cap_of(span64);
-  const bool fits64 = cap64 <= cstile::kPfBytes;
-  if (fits64 && longest + 3 <= cstd::Tdfa::kMaskBytes) return {64, (int)cap64, false, span64};
-  if (longest > cstd::Tdfa::kLongBytes && (fits64 || !small)) return {fits64 ? 64 : 0, (int)cap64, false, span64};  // (such tiles scan generically)
-  if (fits64) return {64, (int)cap64, true, span64};
-  // (eight and four rows a tile: rows of hundreds of bytes -- few lanes of a wave hold a row then, but the rows still arrive
-  // through coalesced tiles and are scanned in LDS; the thread-per-row kernels read them byte by byte from memory)
-  for (int r : {32, 16, 8, 4}) {
-    if (r < 16 && !small) break;
-    const int64_t sp = max_span_rows(col, r, s);
-    const int64_t c = cap_of(sp);
-    if (c <= cstile::kPfBytes) return {r, (int)c, true, sp};
-  }
-  return {0, (int)cap64, false, span64};
-}
-
-// A column with rows beyond the 96-bit masks, a program for which white space is a safe cut (regex_tdfa.cpp, header word 31
-// bit 25): the op runs on the column's PIECES (cs_virtual.hip) -- chain arithmetic, bit form, unit scan as on short rows --
-// and the rows' results follow from the pieces'.
-// Not for a single class, once or in a `+` loop (cs_runs.hip takes rows of any length byte-parallel: count_re([aeiou]+) on the
-// C5 column 3.0 ms there, 5.6 on the pieces), and not -- `replacing` -- for a program that would take the unit scan on a column
-// whose sample holds bytes >= 0x80: the unit route hands every sub-tile with such a byte to the row-by-row scan, and more,
-// shorter rows make that worse (replace_re of the gtest pattern on C5: 40 ms on the pieces, 30 on the long-row form).
-const VirtualRows* pieces_for(const cs_column* col, const cs_regex* re, hipStream_t s, bool replacing, bool containing = false) {
-  if (cs::cfg("CS_NO_VIRTUAL_ROWS") || col->virt_state < 0 || !use_tdfa(re) || !((re->tdfa[31] >> 25) & 1)) return nullptr;
-  if (max_row_bytes(col, s) + 3 <= cstd::Tdfa::kMaskBytes) return nullptr;  // (the masks hold the rows as they are)
-  const bool chain = ((re->tdfa[30] >> 16) & 15) != 0;
-  // One class, once or in a `+` loop: cs_runs.hip counts and replaces such a pattern byte-parallel on rows of any length -- and
-  // keeps the patterns that would take the chain arithmetic here (`[a-z]+` -> '_' on the C5 column: 11.2 ms there, 13.1 on the
-  // pieces) and the columns where bytes >= 0x80 are common (it takes them as they come; the mask forms do not).  The others go to
-  // the pieces' bit form once such rows are put off / left holes: `\w+` 27.7 -> 7.9 ms (cs_runs.hip sends every tile with such a
-  // byte row by row for a class with builtins), `[aeiou]+` 11.1 -> 8.0, count_re 2.9 -> 2.5; contains_re has no form there at all.
-  if (!containing && !re->bits.empty() && (re->bits[2] & (csbits::F_BYTE_CLASS | csbits::F_FLAG_CLASS)) && !cs::cfg("CS_NO_CLASS_RUNS") &&
-      (chain || (sample_has_high_bytes(col, s) && !odd_rows_few(col, s)) || cs::cfg("CS_CLASS_RUNS_ALWAYS")))
-    return nullptr;
-  // (... unless such bytes are rare: the single pass then leaves the rows that hold them holes -- StreamArgs::hole_mask)
-  if (replacing && (re->tdfa[31] & 1) && !chain && sample_has_high_bytes(col, s) && !odd_rows_few(col, s)) return nullptr;
-  // The executor ends a row's scan at a NUL byte and takes a character's width from its lead byte (an ASCII byte behind a
-  // lead without its continuation bytes is swallowed -- a cut byte too): a piece behind such a byte would be scanned where
-  // the row is not.  Columns of well-formed text only (`plain_bytes`: column metadata, one pass when nobody has looked yet).
-  if (!bytes_plain(col, s)) return nullptr;
-  return virtual_rows(col, s);
-}
-
-// ---- shared by the scans and the span ops (extract, findall, replace_with_backrefs) -------------------------------------
-// The column's rows for a kernel that reads them from memory: chars from the pool carry 64 bytes of slack that may be read.
-// (cs_replace_re_multi passes col->nbytes without the slack; left as it is.)
-RowSrc row_src(const cs_column* col) { return RowSrc{view_of(col), d_unicode_flags(), col->nbytes + (col->chars && col->chars->capacity ? 64 : 0)}; }
-// The group tags' share of a stream launch's LDS: 0 when there are none or they take more than 16 KB (they stay in memory
-// then), else their size rounded up to 16.
-size_t gtags_lds_bytes(const cs_regex* re) {
-  const size_t bytes = re->gtags.size() * 4;
-  return bytes && bytes <= 16 * 1024 ? (bytes + 15) & ~size_t(15) : 0;
-}
-// What every launch of k_tdfa_scan_stream says about its input: the column, the tables, the tiles.  The caller adds its own
-// fields (tbl_bytes, the group tags, the outputs, L.in_lds = 2 for tables in memory).
-ScanStreamArgs stream_args(const cs_column* col, const TPlan& tp, const TileChoice& tc) {
-  ScanStreamArgs sa{};
-  sa.in = view_of(col);
-  sa.flags = d_unicode_flags();
-  sa.L = tp.d;
-  sa.nsub = (col->rows + tc.R - 1) / tc.R;
-  sa.rows_per_tile = tc.R;
-  sa.cap_in = tc.cap;
-  return sa;
-}
-
-// ---- contains_re / match_re / count_re: the host route ------------------------------------------------------------------
-// scan<MODE> (MODE 0 contains_re, 1 match_re, 2 count_re) runs a ScanCall as the sequence it is -- the column's pieces,
-// contains by counts, class runs, the stream kernel and the rows it put off, the row-wise kernels -- each step a function
-// that says whether it took the call.  The stream kernel in turn: its FORM (scan_form: which variant runs, on how much
-// LDS), the KERNEL (scan_stream_kernel: the one place that names the instantiations) and the LAUNCH (scan_stream).
-// Several questions below launch kernels or wait on the stream the first time they are asked of a column (pieces_for,
-// sample_has_high_bytes, odd_rows_few, max_row_bytes, bits_route, candidate_share, choose_tile): the order of the `&&`
-// chains decides whether they are asked at all.  Keep it.
-struct ScanCall {
-  const cs_column* col;
-  cs_regex* re;
-  void* results;     // one per row: uint8 flags (contains_re, match_re) or int32 counts (count_re) ...
-  size_t esz;        // ... of this many bytes each
-  int on_device;     // `results` is device memory
-  hipStream_t s;
-  int64_t* found;    // out: rows that hold a match / matches in the column (may be null)
-  const char* name;  // the ProfScope of the stream or row-wise launch
-};
-template <int MODE>
-void scan(const ScanCall& c);
-
-// A column with rows beyond the 96-bit masks, white space a safe cut for the program (pieces_for): the pieces' flags or
-// counts, folded into the rows' (cs_virtual.hip).  Not match_re: it looks at a row's start only.
-template <int MODE>
-bool scan_on_pieces(const ScanCall& c) {
-  if (MODE == 1) return false;
-  const VirtualRows* vr = pieces_for(c.col, c.re, c.s, false, MODE == 0);
-  if (!vr) return false;
-  const cs_column* pc = vr->col.get();
-  Buf piece_res = dev_alloc(c.esz * (size_t)pc->rows, c.s);
-  scan<MODE>(ScanCall{pc, c.re, piece_res->p, c.esz, 1, c.s, nullptr, c.name});
-  note_route_pieces();
-  const ResultsOut res(c.results, c.esz * (size_t)c.col->rows, c.on_device, c.s);
-  const int64_t hits = MODE == 2 ? virtual_reduce_i32(vr, ptr<const int32_t>(piece_res), c.col->rows, static_cast<int32_t*>(res.dev), c.s)
-                                 : virtual_reduce_u8(vr, ptr<const uint8_t>(piece_res), c.col->rows, static_cast<uint8_t*>(res.dev), c.s);
-  if (!c.on_device) res.finish(c.s);  // (the reduction brought its count back: a device caller's results are complete)
-  if (c.found) *c.found = hits;
-  return true;
-}
-
-// contains_re of a program with a unit decomposition whose candidate bytes are most of the column (`\w+@\w+` on log lines):
-// the row lanes' scan restarts at every candidate -- 9.0 ms on the C3 column where count_re, on the unit scan, takes 1.9.
-// "Holds a match" is "counts at least one": the unit scan's counts, turned into flags.
-template <int MODE>
-bool contains_by_counts(const ScanCall& c) {
-  const cs_column* col = c.col;
-  cs_regex* re = c.re;
-  const hipStream_t s = c.s;
-  if (!(MODE == 0 && use_tdfa(re) && (re->tdfa[31] & 1) && ((re->tdfa[30] >> 16) & 15) == 0 && !cs::cfg("CS_NO_CONTAINS_BY_COUNT") && !cs::cfg("CS_REGEX_ROWWISE") &&
-        !cs::cfg("CS_NO_UNITS") && (((re->tdfa[31] >> 17) & 3) != 0 || !sample_has_high_bytes(col, s) || odd_rows_few(col, s)) && max_row_bytes(col, s) + 3 <= cstd::Tdfa::kMaskBytes &&
-        !bits_route(re, col, s, BITS_CONTAINS, odd_rows_few(col, s)) && !bits_route(re, col, s, BITS_COUNT, odd_rows_few(col, s)) &&
-        candidate_share(re, col, s) >= 0.5))
-    return false;
-  Buf counts = dev_alloc(sizeof(int32_t) * (size_t)col->rows, s);
-  int64_t hits = 0;
-  scan<2>(ScanCall{col, re, counts->p, sizeof(int32_t), 1, s, &hits, c.name});
-  const ResultsOut flags(c.results, (size_t)col->rows, c.on_device, s);
-  hipLaunchKernelGGL(k_counts_to_flags, dim3(blocks_for(col->rows)), dim3(256), 0, s, ptr<const int32_t>(counts), col->rows, static_cast<uint8_t*>(flags.dev));
-  CS_HIP(hipGetLastError());
-  flags.finish(s);
-  if (c.found) *c.found = hits;
-  return true;
-}
-
-// count_re of ONE class, once or in a `+` loop, on a column the 96-bit-mask forms do not take (long rows, non-ASCII text) and
-// whose candidates are everywhere: the byte-parallel size pass of cs_runs.hip counting matches -- count_re(\w+), the words of
-// a row, on the C5 column: 15.8 ms on the long-row automaton form
-template <int MODE>
-bool count_by_class_runs(const ScanCall& c, const ResultsOut& res) {
-  const cs_column* col = c.col;
-  cs_regex* re = c.re;
-  const hipStream_t s = c.s;
-  if (MODE != 2 || re->bits.empty() || !(re->bits[2] & (csbits::F_BYTE_CLASS | csbits::F_FLAG_CLASS))) return false;
-  upload(re, s);
-  const TileChoice tc0 = choose_tile(col, s, true);
-  const bool masks_form = tc0.R == 64 && !tc0.lng && (!sample_has_high_bytes(col, s) || odd_rows_few(col, s));
-  const bool chain_there = !re->tdfa.empty() && ((re->tdfa[30] >> 16) & 15) != 0 && tc0.R == 64 && !tc0.lng;
-  const bool flag_class = (re->bits[2] & csbits::F_BYTE_CLASS) == 0;
-  int64_t hits = 0;
-  if (!(re->d_bits && (cs::cfg("CS_CLASS_RUNS_ALWAYS") || (!masks_form && !(flag_class && chain_there) && candidate_share(re, col, s) >= 0.05)) &&
-        count_class_runs(col, ptr<const int32_t>(re->d_bits), re->bits, s, static_cast<int32_t*>(res.dev), &hits)))
-    return false;
-  note_route("runs");
-  if (!c.on_device) res.finish(s);  // (as on the pieces: the pass brought its count back)
-  if (c.found) *c.found = hits;
-  return true;
-}
-
-struct ScanRun {  // a call and what its launches share
-  const ScanCall& c;
-  bool tdfa, wide;            // the tagged DFA runs the program; ... with five to eight live threads (TdfaWide on the same kernels' generic row path)
-  TPlan tp;                   // (tdfa || wide)
-  Plan pl;                    // (neither: the list simulator)
-  void* out;                  // the rows' results on the device (ResultsOut::dev)
-  unsigned long long* found;  // the zeroed count the kernels add to
-  RowSrc src;
-};
-// The kernels take a flags pointer and a counts pointer: the one MODE means is the results buffer, the other null.
-template <int MODE>
-uint8_t* out8_of(const ScanRun& r) {
-  return MODE == 2 ? nullptr : static_cast<uint8_t*>(r.out);
-}
-template <int MODE>
-int32_t* out32_of(const ScanRun& r) {
-  return MODE == 2 ? static_cast<int32_t*>(r.out) : nullptr;
-}
-
-// Which variant of k_tdfa_scan_stream runs, and on how much LDS.
-using ScanStreamKernel = void (*)(ScanStreamArgs);
-struct ScanForm {
-  // a column whose sample holds a few bytes >= 0x80: the rows that hold them are put off -- ScanStreamArgs::deferred,
-  // k_tdfa_scan_list -- and the forms are chosen as on plain ASCII; the C5 column, one row in 170: contains_re of the gtest
-  // pattern 9.9 ms when every sub-tile with such a row went to the row-by-row scan
-  bool put_off;
-  // the unit scan (k_tdfa_scan_stream<.., UNITS>): patterns whose tagged DFA offers the decomposition, rows within the masks
-  // (count_re only: contains_re stops at a row's first match, and scanning every unit of the row cost more than the
-  // balance won -- 3.87 against 2.66 ms on the 100M-row C3 column)
-  // (... but the unit form of the kernel is taken for contains_re too when the pattern lets the unit route serve tiles with
-  // bytes >= 0x80 -- header word 31 bits 17 / 18 -- and a sample of the chars holds such bytes: ASCII tiles keep the row
-  // lanes' scan inside it, at a few per cent more than the plain form)
-  // (chain patterns -- header words 29 / 30 -- were tried on the unit form for contains_re as well: 2.18 against 2.10 ms; the
-  // plain form's first-match scan stays)
-  // (a chain pattern without a unit decomposition -- one with a suffix, regex_tdfa.cpp -- takes the same kernels: their unit
-  // routes test header word 31 bit 0 themselves)
-  bool units;
-  // the bit-parallel form (regex_bits.h): contains_re / count_re of patterns whose candidates are everywhere
-  bool bits_form;
-  int bits_k;
-  size_t bits_lds;
-  // a chain pattern on a column whose sample is plain ASCII: count_re by the chain's arithmetic
-  bool chain_scan;
-  // (a chain's arithmetic reads no table: where the tables cost the launch a workgroup per CU -- four fit in 40 KB each --
-  // they stay in memory, as in cs_replace_re)
-  // (the bit form is such a form too: its sub-tiles of plain ASCII never touch the automaton)
-  bool chain_global;
-  bool wide;        // (ScanRun::wide)
-  size_t scan_tbl;  // bytes of the automaton's tables in LDS: all of them, or -- chain_global -- header + tail words (tsetup)
-  size_t lds;       // dynamic LDS of a workgroup; beyond 150 KB there is no stream launch
-  const char* note;  // cs_debug_last_route
-  ScanStreamKernel kern;
-};
-
-// The instantiation of k_tdfa_scan_stream a form runs on: every one the scans hold is named here, once, from the plainest
-// form on.  The parameters are <MODE, IN_LDS, LONG, UNITS, CHAIN, BITS> (their meaning: at the kernel); MODE + 7 is the
-// WIDE executor.  match_re has the plain and wide forms only; the unit, chain and bit forms are count_re's and contains_re's.
-template <int MODE>
-ScanStreamKernel scan_stream_kernel(const ScanForm& f, bool lng) {
-  constexpr int M = MODE == 2 ? 2 : 0;
-  if (!f.wide && !f.units && !f.bits_form) return lng ? &k_tdfa_scan_stream<MODE, true, true> : &k_tdfa_scan_stream<MODE, true, false>;
-  if (f.units && !f.chain_scan && !f.bits_form) return &k_tdfa_scan_stream<M, true, false, true>;
-  if (f.chain_scan) {
-    if (!f.chain_global) return &k_tdfa_scan_stream<2, true, false, true, true>;
-    return &k_tdfa_scan_stream<2, false, false, true, true>;
-  }
-  if (f.bits_form) return f.chain_global ? &k_tdfa_scan_stream<M, false, false, true, true, true> : &k_tdfa_scan_stream<M, true, false, true, true, true>;
-  return lng ? &k_tdfa_scan_stream<MODE + 7, true, true> : &k_tdfa_scan_stream<MODE + 7, true, false>;
-}
-
-template <int MODE>
-ScanForm scan_form(const ScanRun& r, const TileChoice& tc) {
-  const cs_column* col = r.c.col;
-  const cs_regex* re = r.c.re;
-  const hipStream_t s = r.c.s;
-  const int cap = tc.cap;
-  ScanForm f{};
-  f.wide = r.wide;
-  f.put_off = (MODE == 0 || MODE == 2) && !f.wide && !tc.lng && tc.R == 64 && sample_has_high_bytes(col, s) && odd_rows_few(col, s);
-  const bool high_sample = sample_has_high_bytes(col, s) && !f.put_off;
-  f.units = !f.wide && (MODE == 2 || (MODE == 0 && ((re->tdfa[31] >> 17) & 3) != 0 && high_sample)) &&
-            ((re->tdfa[31] & 1) != 0 || (MODE == 2 && ((re->tdfa[30] >> 16) & 15) != 0)) &&
-            !tc.lng && tc.R == 64 && !cs::cfg("CS_NO_UNITS");
-  f.bits_form = !f.wide && (MODE == 0 || MODE == 2) && !tc.lng && tc.R == 64 && bits_route(re, col, s, MODE == 2 ? BITS_COUNT : BITS_CONTAINS, f.put_off);
-  f.bits_k = f.bits_form ? std::max(re->bits[1], 2) : 0;
-  f.bits_lds = f.bits_form ? (size_t)bits_lds_bytes((int)re->bits.size()) : 0;
-  f.lds = f.bits_form ? r.tp.lds_bytes + f.bits_lds + (size_t)(cap + 32 + f.bits_k * ((cap >> 3) + 32) + kUnitQueue * 4 + 64 * 4 + 16) * 4
-                      : r.tp.lds_bytes + (size_t)(cap + 32 + (cap >> 3) + 32 + (f.units ? (cap >> 3) + 32 + kUnitQueue * 4 + 64 * 4 + 16 : 0)) * 4;
-  if (f.put_off) f.lds += (size_t)((cap >> 3) + 32 + 64 * 4) * 4;  // (the bitmap of such bytes and the rows waiting for the list, a wave)
-  f.chain_scan = f.units && MODE == 2 && !f.bits_form && ((re->tdfa[30] >> 16) & 15) != 0 && !high_sample && !cs::cfg("CS_NO_CHAIN_FORM");
-  f.chain_global = (f.chain_scan || f.bits_form) && f.lds > 40 * 1024 && f.lds - r.tp.lds_bytes + cstd::kHeadTailWords * 4 <= 40 * 1024 && !cs::cfg("CS_CHAIN_TABLES_IN_LDS");
-  f.scan_tbl = f.chain_global ? (size_t)cstd::kHeadTailWords * 4 : r.tp.lds_bytes;
-  if (f.chain_global) f.lds -= r.tp.lds_bytes - f.scan_tbl;
-  f.note = f.bits_form ? "bits" : f.wide ? "wide" : f.chain_scan ? "chain" : f.units ? "units" : "plain";
-  f.kern = scan_stream_kernel<MODE>(f, tc.lng);
-  return f;
-}
-
-// The rows a stream launch put off: the list kernel, a thread a row.  More such rows than the sample promised and the
-// list holds: the count is zeroed again, the call is not taken and the column is scanned once more, row-wise, with
-// nothing put off.
-template <int MODE>
-bool scan_put_off_rows(const ScanRun& r, const ScanStreamArgs& sa, const Buf& later, const Buf& nlater) {
-  const hipStream_t s = r.c.s;
-  note_route_put_off();
-  const unsigned lgrid = (unsigned)std::min<int64_t>(((int64_t)sa.deferred_cap + 255) / 256, 2048);
-  const size_t list_lds = r.tp.lds_bytes + (size_t)256 * kListRowBytes;  // (the tables and a row a thread)
-  if (list_lds > 48 * 1024)
-    CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tdfa_scan_list<MODE == 2 ? 2 : 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)list_lds));
-  ProfScope ps("k_tdfa_scan_list", s);
-  hipLaunchKernelGGL((k_tdfa_scan_list<MODE == 2 ? 2 : 0>), dim3(lgrid), dim3(256), list_lds, s, r.src, r.tp.d, ptr<const int32_t>(later), ptr<const unsigned>(nlater),
-                     sa.deferred_cap, out8_of<MODE>(r), out32_of<MODE>(r), r.found);
-  unsigned* hn = (unsigned*)pinned_scratch(sizeof(unsigned));
-  CS_HIP(hipMemcpyAsync(hn, nlater->p, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-  CS_HIP(hipStreamSynchronize(s));
-  if (*hn <= sa.deferred_cap) return true;
-  note_fallback("regex-deferred-rows-overflow");
-  CS_HIP(hipMemsetAsync(r.found, 0, 8, s));
-  return false;
-}
-
-// The stream kernel: row tiles through LDS on a persistent grid, for a tagged DFA whose tables fit LDS.
-template <int MODE>
-bool scan_stream(const ScanRun& r) {
-  const cs_column* col = r.c.col;
-  const cs_regex* re = r.c.re;
-  const hipStream_t s = r.c.s;
-  if (!r.tdfa || !r.tp.d.in_lds || cs::cfg("CS_REGEX_ROWWISE")) return false;
-  const TileChoice tc = choose_tile(col, s);
-  const ScanForm f = scan_form<MODE>(r, tc);
-  if (!tc.R || f.lds > 150 * 1024) return false;
-  ScanStreamArgs sa = stream_args(col, r.tp, tc);
-  if (f.chain_global) sa.L.in_lds = 2;
-  sa.out8 = out8_of<MODE>(r);
-  sa.out32 = out32_of<MODE>(r);
-  sa.found = r.found;
-  sa.tbl_bytes = (int)(f.scan_tbl + f.bits_lds);
-  sa.bits = f.bits_form ? ptr<const int32_t>(re->d_bits) : nullptr;
-  sa.bits_off = (int)f.scan_tbl;
-  sa.bits_words = f.bits_form ? (int)re->bits.size() : 0;
-  sa.bits_k = f.bits_form ? re->bits[1] : 0;
-  note_route(f.note);
-  Buf later, nlater;
-  if (f.put_off) {
-    sa.deferred_cap = (unsigned)std::min<int64_t>(col->rows, col->rows / 8 + 4096);
-    later = dev_alloc(sizeof(int32_t) * (size_t)sa.deferred_cap, s);
-    nlater = dev_alloc(sizeof(unsigned), s);
-    CS_HIP(hipMemsetAsync(nlater->p, 0, sizeof(unsigned), s));
-    sa.deferred = ptr<int32_t>(later);
-    sa.ndeferred = ptr<unsigned>(nlater);
-  }
-  {
-    ProfScope ps(r.c.name, s);
-    launch_resident(f.kern, f.lds, (sa.nsub + 3) / 4, s, sa);
-  }
-  return !f.put_off || scan_put_off_rows<MODE>(r, sa, later, nlater);
-}
-
-// The row-wise kernels, a thread a row: the tagged DFA (wide or not, tables in LDS or in memory) or the list simulator.
-template <int MODE>
-void scan_rowwise(const ScanRun& r) {
-  const hipStream_t s = r.c.s;
-  const TPlan& tp = r.tp;
-  const Plan& pl = r.pl;
-  uint8_t* out8 = out8_of<MODE>(r);
-  int32_t* out32 = out32_of<MODE>(r);
-  ProfScope ps(r.c.name, s);
-  if (r.wide)
-    if (tp.d.in_lds)
-      hipLaunchKernelGGL((k_tdfa_scan<MODE, true, true>), dim3(tp.grid), dim3(256), tp.lds_bytes, s, r.src, tp.d, out8, out32, r.found);
-    else
-      hipLaunchKernelGGL((k_tdfa_scan<MODE, false, true>), dim3(tp.grid), dim3(256), 0, s, r.src, tp.d, out8, out32, r.found);
-  else if (r.tdfa)
-    if (tp.d.in_lds)
-      hipLaunchKernelGGL((k_tdfa_scan<MODE, true>), dim3(tp.grid), dim3(256), tp.lds_bytes, s, r.src, tp.d, out8, out32, r.found);
-    else
-      hipLaunchKernelGGL((k_tdfa_scan<MODE, false>), dim3(tp.grid), dim3(256), 0, s, r.src, tp.d, out8, out32, r.found);
-  else if (pl.small)
-    hipLaunchKernelGGL((k_regex_scan<true, MODE>), dim3(pl.grid), dim3(pl.threads), pl.lds_bytes, s, r.src, pl.d, out8, out32, r.found);
-  else
-    hipLaunchKernelGGL((k_regex_scan<false, MODE>), dim3(pl.grid), dim3(pl.threads), pl.lds_bytes, s, r.src, pl.d, out8, out32, r.found);
-}
-
-template <int MODE>
-void scan(const ScanCall& c) {
-  const cs_column* col = c.col;
-  const hipStream_t s = c.s;
-  if (c.found) *c.found = 0;
-  note_route("");
-  if (col->rows == 0) return;
-  if (scan_on_pieces<MODE>(c)) return;
-  if (contains_by_counts<MODE>(c)) return;
-  const bool wide = use_tdfa_wide(c.re);
-  const bool tdfa = use_tdfa(c.re) || wide;
-  Plan pl{};
-  TPlan tp{};
-  if (tdfa) tp = tplan(c.re, col->rows, s);
-  else pl = plan(c.re, col->rows, s);
-  const ResultsOut res(c.results, c.esz * (size_t)col->rows, c.on_device, s);  // (before the class-runs attempt; the count after it)
-  if (count_by_class_runs<MODE>(c, res)) return;
-  const Buf cnt = zeroed_count(s);
-  const ScanRun r{c, tdfa, wide, tp, pl, res.dev, ptr<unsigned long long>(cnt), row_src(col)};
-  if (!scan_stream<MODE>(r)) scan_rowwise<MODE>(r);
-  CS_HIP(hipGetLastError());
-  res.copy_back(s);
-  const int64_t n = read_count(cnt, s);
-  if (c.found) *c.found = n;
-}
-
 }  // namespace
-
-extern "C" {
-
-// Reprog::create_from + dreprog::create_from -- regcomp.cpp:954-960, regexec.cpp:12-73
-int cs_regex_compile(const char* pattern, cs_regex** out) {
-  return guard([&] {
-    if (!pattern || !out) fail(CS_ERR_INVALID_ARG, "regex pattern cannot be null");
-    // A compiled pattern is immutable (the device images are uploaded once, under a lock) and costs 0.6 - 1.6 ms of host
-    // time to build -- a tenth of the replace_re kernel on 100M rows, more than the kernel on a few million -- while
-    // the callers above the C ABI compile per call, as the reference does.  The last 32 patterns are kept; a handle
-    // is a counted reference to the shared object.
-    static std::mutex& mu = *new std::mutex;  // (never destroyed: see the note on process exit in cs_core.hip's buffer cache)
-    static auto& kept = *new std::list<std::pair<std::string, cs_regex*>>;
-    const bool keep = !cs::cfg("CS_REGEX_NO_CACHE");
-    if (keep) {
-      std::lock_guard<std::mutex> lk(mu);
-      for (auto it = kept.begin(); it != kept.end(); ++it)
-        if (it->first == pattern) {
-          kept.splice(kept.begin(), kept, it);
-          it->second->refs.fetch_add(1);
-          *out = it->second;
-          return;
-        }
-    }
-    std::unique_ptr<cs_regex> re(new cs_regex);
-    re->empty_pattern = *pattern == 0;
-    re->prog = csrx::compile(pattern);
-    re->blob = re->prog.to_blob();
-    re->image = re->prog.to_device_image(h_unicode_flags());
-    re->tdfa = csrx::build_tdfa(re->prog, re->image, h_unicode_flags(), &re->gtags);
-    re->bits = csrx::build_bits(re->prog, re->image, h_unicode_flags());
-    cs_regex* dropped = nullptr;
-    if (keep) {
-      std::lock_guard<std::mutex> lk(mu);
-      re->refs.store(2);
-      kept.emplace_front(pattern, re.get());
-      if (kept.size() > 32) {
-        dropped = kept.back().second;
-        kept.pop_back();
-      }
-    }
-    *out = re.release();
-    if (dropped && dropped->refs.fetch_sub(1) == 1) delete dropped;
-  });
-}
-int cs_regex_destroy(cs_regex* re) {
-  return guard([&] {
-    if (re && re->refs.fetch_sub(1) == 1) delete re;
-  });
-}
-int cs_regex_inst_count(const cs_regex* re) { return re ? (int)re->prog.insts.size() : 0; }
-int cs_regex_engine(const cs_regex* re) {
-  if (!re) return 0;
-  int e = 0;
-  if (!re->tdfa.empty()) {
-    e |= 1;                               // the tagged DFA (regex_tdfa.h) runs the pattern
-    if (re->tdfa[31] & 1) e |= 2;         // ... and offers the unit decomposition (regex_tdfa.cpp)
-    if (!re->gtags.empty()) e |= 4;       // ... and carries the capture-group tags
-    e |= (re->tdfa[12] & 15) << 8;        // live threads the automaton keeps at most
-    e |= (re->tdfa[1] & 0xFFFF) << 16;    // states
-  }
-  return e;
-}
-int cs_regex_blob(const cs_regex* re, const int32_t** words, int* nwords) {
-  return guard([&] {
-    if (!re || !words || !nwords) fail(CS_ERR_INVALID_ARG, "null argument");
-    *words = re->blob.data();
-    *nwords = (int)re->blob.size();
-  });
-}
-
-// NVStrings::contains_re -- count.cu:59-110
-int cs_contains_re(const cs_column* col, const cs_regex* re, uint8_t* results, int on_device, cs_stream stream,
-                   int64_t* found) {
-  return guard([&] {
-    if (found) *found = -1;
-    if (!col || !re || !results) fail(CS_ERR_INVALID_ARG, "contains_re: null argument");
-    scan<0>(ScanCall{col, const_cast<cs_regex*>(re), results, sizeof(uint8_t), on_device, S(stream), found, "k_contains_re"});
-  });
-}
-// NVStrings::match -- count.cu:113-165
-int cs_match_re(const cs_column* col, const cs_regex* re, uint8_t* results, int on_device, cs_stream stream,
-                int64_t* found) {
-  return guard([&] {
-    if (found) *found = -1;
-    if (!col || !re || !results) fail(CS_ERR_INVALID_ARG, "match: null argument");
-    scan<1>(ScanCall{col, const_cast<cs_regex*>(re), results, sizeof(uint8_t), on_device, S(stream), found, "k_match_re"});
-  });
-}
-// NVStrings::count_re -- count.cu:168-250
-int cs_count_re(const cs_column* col, const cs_regex* re, int32_t* results, int on_device, cs_stream stream,
-                int64_t* found) {
-  return guard([&] {
-    if (found) *found = -1;
-    if (!col || !re || !results) fail(CS_ERR_INVALID_ARG, "count_re: null argument");
-    scan<2>(ScanCall{col, const_cast<cs_regex*>(re), results, sizeof(int32_t), on_device, S(stream), found, "k_count_re"});
-  });
-}
-
-}  // extern "C"
 
 // ---- replace_re: the host route ---------------------------------------------------------------------------------------
 // cs::replace_re_column runs a cs::ReplaceCall (cs_internal.h) as the sequence it is -- the column's pieces, class runs,

@@ -1,6 +1,6 @@
 // VIRTUAL ROWS: a column whose rows exceed the 96-bit masks, seen as a column of pieces that fit them.
 //
-// The fast regex forms -- chain arithmetic, the bit-parallel form, the unit scan (cs_regex.hip) -- hold a row in three
+// The fast regex forms -- chain arithmetic, the bit-parallel form, the unit scan (regex_stream.h, cs_regex.hip) -- hold a row in three
 // 32-bit mask words: rows of at most 92-93 bytes.  BASELINE.json's C5 column (tweet-like rows of 40-150 bytes) left them
 // for the long-row automaton form: 3-20 times the time per byte (profiles/r06/c5regex.jsonl).  The reference's functors take
 // any row length (regexec.inl:204-442, custring_view.cuh:36-42).  Instead of widening every mask, the COLUMN is narrowed:
@@ -9,7 +9,7 @@
 // whose tagged DFA says those four bytes are safe cuts (regex_tdfa.cpp, header word 31 bit 25: whatever state consumes one
 // keeps nothing, and a scan begun behind it behaves as one begun at a row's first byte) no match spans a cut and no piece
 // can tell itself from a row (on well-formed text without NUL bytes: the executor ends a row's scan at a NUL and lets a lead
-// byte swallow what follows it -- cs_regex.hip: pieces_for asks the column's `plain_bytes`), so
+// byte swallow what follows it -- cs_regex_pattern.hip: pieces_for asks the column's `plain_bytes`), so
 //   contains_re(row) = OR of contains_re(piece),  count_re(row) = sum of count_re(piece),
 //   replace_re(row)  = the concatenation of replace_re(piece)  -- i.e. the pieces' output chars ARE the rows' output chars,
 //                      and a row's output offset is the output offset of its first piece.

@@ -659,7 +659,7 @@ WIDE_PATTERNS = [r"\d{1,3}\.\d{1,3}\.\d{1,3}\.\d{1,3}", r"\w{5}", r"[a-z]{3,8}@"
 def test_gpu_unit_route_on_tiles_with_non_ascii_bytes(gpu_engine, oracle_engine):
     """Sub-tiles that hold bytes >= 0x80 and a pattern such bytes can only kill (ASCII classes and literals, no anchors, no
     \\b: regex_tdfa.cpp header word 31 bit 17): the unit route takes them, a unit's scan ending at the unit's end
-    (cs_regex.hip: reclassify_high) -- replace_re / count_re / findall against the oracle, with the characters next to the
+    (regex_stream.h: reclassify_high) -- replace_re / count_re / findall against the oracle, with the characters next to the
     matches, between units and at the row ends; \\d patterns (non-ASCII digits exist) keep the generic scan and must agree too."""
     import random
 

@@ -172,7 +172,7 @@ def test_gpu_bits_route_on_c3(pat, monkeypatch):
 
 
 def test_gpu_bits_route_chosen_by_candidate_density():
-    """Without the switch the route follows the column and the op (cs_regex.hip: bits_route): candidates in a good share of
+    """Without the switch the route follows the column and the op (cs_regex_pattern.hip: bits_route): candidates in a good share of
     the sampled bytes -> the bit form; a rare first byte -> the automaton's skipping scans; chains keep the chain form."""
     L = gpuutil.lib()
     g = gpuutil.synth(3, 0, 50_000)
@@ -209,7 +209,7 @@ def test_gpu_bits_route_meets_other_tiles(monkeypatch):
     orc = cpulibs.Oracle()
     base = orc.synth(3, 0, 40_000)
     rows = base.to_list()
-    # (the host gives a column to the 96-bit-mask forms while its longest row has at most 93 bytes: cs_regex.hip, choose_tile)
+    # (the host gives a column to the 96-bit-mask forms while its longest row has at most 93 bytes: cs_regex_pattern.hip, choose_tile)
     specials = ["naïve in a the", "in\x00a the", "a" * 93, "é", "", None, "in a the", "x" * 92 + "a", "a " * 46 + "a", "in" + " " * 91, "the " * 23,
                 "the end in a\n", "\nthe", "ünder the a", "a\x00", "in a the " * 10]
     for k, sp in enumerate(specials):
@@ -253,7 +253,7 @@ def test_gpu_counted_chain_with_its_tables_in_memory():
     g = gpuutil.from_col(o)
     f0 = L.lib.cs_fallback_count()
     # (the third: counted items, a literal suffix and the tables in memory -- the suffix and the counts come from the image's
-    # last words, staged in LDS beside the header: cs_regex.hip, tsetup)
+    # last words, staged in LDS beside the header: regex_exec.h, tsetup)
     for pat in (IPV4B, r"\b\d+\.\d+\b", r"\b\d{1,3}\.\d{1,3}\.\d{1,3}\.\d{1,3} -", r"\b(\d{1,3})\.(\d{1,3})\b", r"\d+\.\d{2}\.\d+"):
         check_regex_ops(g, o, pat, orc, repls=("<IP>", "", "<a-much-longer-one>"))
         g.replace(pat, "#")
@@ -641,7 +641,7 @@ def test_gpu_class_runs_on_arbitrary_bytes(pat, monkeypatch):
 def test_gpu_class_runs_route_is_for_long_or_non_ascii_columns():
     """The route is taken where the 96-bit-mask forms are not: C5 (long rows) for the patterns that would take the chain
     arithmetic on the column's pieces or that no piece can hold (a class with white space in it); since round 6 the other
-    single classes go to the pieces' bit form, the few rows with bytes >= 0x80 left holes (cs_regex.hip: pieces_for); C3 keeps
+    single classes go to the pieces' bit form, the few rows with bytes >= 0x80 left holes (cs_regex_pattern.hip: pieces_for); C3 keeps
     the single pass."""
     g5 = gpuutil.synth(5, 0, 40_000)
     g5.replace(r"[a-z]+", "*")  # (a chain)

@@ -106,7 +106,7 @@ def test_gpu_unit_route_lead_byte_swallows_the_ascii_byte_behind_it():
     """count_re / contains_re / replace_re of `b|ab` (a unit-route program) on rows where a lead byte >= 0xC0 stands without its
     continuation bytes: the byte behind it belongs to the 'character' and is no match.  Round 5's last soak (seed 70058) found
     the unit route counting the `b` of `4\\xc3b`: its whole-character check ran only for patterns that look flags up
-    (cs_regex.hip: reclassify_high; fix 35b5107, which landed without a test)."""
+    (regex_stream.h: reclassify_high; fix 35b5107, which landed without a test)."""
     L = gpuutil.lib()
     pat = r"b|ab"
     re = gpuutil.compile_re(pat)
@@ -365,7 +365,7 @@ def test_gpu_replace_re_on_rows_of_94_to_188_bytes(pat, repl):
 # ---- rows beyond the masks as PIECES (cs_virtual.hip) -----------------------------------------------------------------------------
 
 # (pattern, replacement, does replace_re take the pieces too?  None: not asserted -- a program that would take the unit scan stays
-# on the long-row form when the column's sample holds bytes >= 0x80: cs_regex.hip, pieces_for)
+# on the long-row form when the column's sample holds bytes >= 0x80: cs_regex_pattern.hip, pieces_for)
 PIECE_PATTERNS = [(IPV4, "<IP>", True), (r"(\bin\b)|(\ba\b)|(\bthe\b)", "=", None), (r"\w+@\w+", "<m>", None), (r"#\w+", "<a-longer-tag>", True),
                   (r"\b\d{1,3}\.\d{1,3}\.\d{1,3}\.\d{1,3}\b", "", True), (r"\d+$", "N", None), (r"[a-z]+ing\b", "ING", None), (r"GET|POST|the", "V", True)]
 
@@ -462,7 +462,7 @@ def test_gpu_growing_replacement_sized_from_count_re(pat, repl, monkeypatch):
 @pytest.mark.parametrize("pat", [r"\w+@\w+", r"[a-z]+\.[a-z]+", r"\w+-\w+"])
 def test_gpu_contains_re_of_a_dense_unit_program_by_its_counts(pat, monkeypatch):
     """contains_re of a program with a unit decomposition whose candidate bytes are most of the column runs count_re's unit scan
-    and turns the counts into flags (cs_regex.hip: scan<0>): flags and the number of rows that hold a match against the oracle,
+    and turns the counts into flags (cs_regex_scan.hip: scan<0>): flags and the number of rows that hold a match against the oracle,
     null rows included, and the row lanes' scan (CS_NO_CONTAINS_BY_COUNT) says the same."""
     orc = cpulibs.Oracle()
     blob = blob_of(pat)
@@ -487,7 +487,7 @@ def test_gpu_contains_re_of_a_dense_unit_program_by_its_counts(pat, monkeypatch)
         gpuutil.lib().lib.cs_regex_destroy(re)
 
 
-# ---- rows with bytes >= 0x80 put off to a second launch (cs_regex.hip: ScanStreamArgs::deferred, k_tdfa_scan_list) ----
+# ---- rows with bytes >= 0x80 put off to a second launch (regex_stream.h: ScanStreamArgs::deferred; cs_regex_scan.hip: k_tdfa_scan_list) ----
 LATER_PATTERNS = [r"\w+@\w+", r"(\bin\b)|(\ba\b)|(\bthe\b)", r"[aeiou]+", r"\d+\.\d+\.\d+\.\d+", r"[a-z]+ing\b", r"\d+", r"#\w+"]
 
 

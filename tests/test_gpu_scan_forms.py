@@ -1,4 +1,4 @@
-"""The scan route as a table (cs_regex.hip: scan<MODE>): one case per step of the sequence -- pieces, contains by counts,
+"""The scan route as a table (cs_regex_scan.hip: scan<MODE>): one case per step of the sequence -- pieces, contains by counts,
 class runs, stream kernel, put-off rows, row-wise kernels -- and per row of the stream kernel's table (scan_stream_kernel),
 for contains_re, match_re and count_re, on the columns of tests/test_gpu_replace_forms.py and two more (`even-90`, `even-62`).  Every case runs with host
 results and with device results and asserts the oracle's values, the returned count, that nothing fell back

@@ -74,7 +74,7 @@ def make_column(seed, max_rows=40_000):
         chars = np.frombuffer(data[:int(offs[-1])], dtype=np.uint8).copy()
     if flavour == 1 and (seed // 28) % 2 == 1 and int(offs[-1]) >= 2:
         # ASCII text with a FEW rows that hold a two-byte character or a NUL -- and such a byte where the sample's first
-        # window sees it: the rows the scans put off and the single-pass replace leaves holes (cs_regex.hip: deferred / hole_mask)
+        # window sees it: the rows the scans put off and the single-pass replace leaves holes (regex_stream.h: deferred; cs_regex.hip: hole_mask)
         for r in np.flatnonzero((rng.random(rows) < 0.01) & (lens >= 2)):
             k = int(offs[r]) + int(rng.integers(0, int(lens[r]) - 1))
             if rng.random() < 0.8:
