@@ -186,6 +186,10 @@ _PROTOS = {
     "cs_extract": (i32, [vp, vp, vp, P(P(vp)), P(i32)]),
     "cs_findall": (i32, [vp, vp, vp, P(P(vp)), P(i32)]),
     "cs_records_from_columns": (i32, [P(vp), i32, i32, vp, i32, vp, P(vp)]),
+    "cs_split_re": (i32, [vp, vp, i32, vp, P(P(vp)), P(i32)]),
+    "cs_rsplit_re": (i32, [vp, vp, i32, vp, P(P(vp)), P(i32)]),
+    "cs_split_record_re": (i32, [vp, vp, i32, vp, i32, vp, P(vp)]),
+    "cs_rsplit_record_re": (i32, [vp, vp, i32, vp, i32, vp, P(vp)]),
     "cs_category_build": (i32, [vp, vp, P(vp)]),
     "cs_category_merge": (i32, [P(vp), i32, vp, P(vp)]),
     "cs_category_merge_gathered": (i32, [vp, P(vp), i32, i32, vp, P(vp), vp]),

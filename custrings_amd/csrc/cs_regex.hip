@@ -22,6 +22,7 @@
 #include "tile_utils.h"
 #include "regex_exec.h"
 #include "regex_stream.h"
+#include "splitre_ops.h"
 
 using namespace cs;
 using namespace csdev;
@@ -2804,7 +2805,9 @@ int read_max(const Buf& dmax, hipStream_t s) {
 // The stream kernel reports spans and the largest match count in ONE pass when the rows hold at most kProvisional matches
 // (the span arrays are laid out [k * rows + row], so unused columns cost only memory); a column with busier rows is scanned
 // a second time with the exact column count, into span buffers of its own.  Returns the column count, -1: not taken.
-int findall_stream(SpanRun& r, const Buf& dmax, SpanBufs& sp) {
+// `exact_width` (split_re: the count scan ran first, the width is known): one launch at that width, packed up to
+// `pack_limit` columns, no maximum reported or read back.
+int findall_stream(SpanRun& r, const Buf& dmax, SpanBufs& sp, int exact_width = 0, int pack_limit = kMaxGroups) {
   constexpr int kProvisional = 4;
   const hipStream_t s = r.s;
   const int64_t rows = r.col->rows;
@@ -2817,19 +2820,20 @@ int findall_stream(SpanRun& r, const Buf& dmax, SpanBufs& sp) {
   sa.found = ptr<unsigned long long>(hits);  // (hit counter: nobody reads it, the kernel writes through it)
   sa.tbl_bytes = (int)f.scan_tbl;
   if (f.chain_global) sa.L.in_lds = 2;
-  sa.maxp = ptr<int>(dmax);
+  sa.maxp = exact_width ? nullptr : ptr<int>(dmax);
   sp.cap = tc.cap;
-  int ncols = 0, width = kProvisional;
+  int ncols = 0, width = exact_width ? exact_width : kProvisional;
   for (int pass = 0; pass < 2; ++pass) {
     // (the provisional pass on 64-row tiles leaves packed spans and tile totals: k_spans_write_tile2 needs no pass
     // over the lengths; a second pass -- rows with more than kProvisional matches -- writes begins / lens)
-    sp.alloc(rows, width, tc.R == 64 && width <= kMaxGroups && (pass == 0 || !cs::cfg("CS_SPANS_EXACT_UNPACKED")) && !cs::cfg("CS_SPANS_UNPACKED"), s);
+    sp.alloc(rows, width, tc.R == 64 && width <= pack_limit && (pass == 0 || !cs::cfg("CS_SPANS_EXACT_UNPACKED")) && !cs::cfg("CS_SPANS_UNPACKED"), s);
     CS_HIP(hipMemsetAsync(dmax->p, 0, 8, s));
     sp.give(sa, width);
     {
       ProfScope ps("k_findall_spans", s);
       launch_resident(f.kern, f.lds, (sa.nsub + 3) / 4, s, sa);
     }
+    if (exact_width) return width;
     ncols = read_max(dmax, s);
     if (ncols <= width) break;
     width = ncols;  // busier rows than provisioned for: once more, exactly
@@ -2838,10 +2842,12 @@ int findall_stream(SpanRun& r, const Buf& dmax, SpanBufs& sp) {
 }
 
 // Matches per row (count_re: scan<2>), their maximum = the number of columns.
-int findall_count_rows(const SpanRun& r, const Buf& dmax) {
+// `keep` (split_re): receives the counts.
+int findall_count_rows(const SpanRun& r, const Buf& dmax, Buf* keep = nullptr) {
   const hipStream_t s = r.s;
   const int64_t rows = r.col->rows;
   Buf counts = dev_alloc(sizeof(int32_t) * rows, s);
+  if (keep) *keep = counts;
   scan<2>(ScanCall{r.col, r.re, counts->p, sizeof(int32_t), 1, s, nullptr, "k_count_re"});
   CS_HIP(hipMemsetAsync(dmax->p, 0, 8, s));
   hipLaunchKernelGGL(k_max_i32, dim3((unsigned)std::min<int64_t>((rows + 255) / 256, 2048)), dim3(256), 0, s, ptr<int32_t>(counts), rows,
@@ -3033,9 +3039,203 @@ cs_column* backrefs_two_pass(const cs_column* col, cs_regex* re, const csvm::Bac
   return b.col.release();
 }
 
+// ---- split_re / rsplit_re (splitre_ops.h) ----
+// Token spans from match spans.  A wave takes a 64-row tile, a lane a row: for token column k the lanes read their
+// rows' cut k -- match span k, or for rsplit_re with a limit match span m - s + k, m from the count scan -- from the
+// span arrays [k * rows + row], form token k from the end of the previous cut, the begin of this one and the row's
+// byte length (cssre::token_span), and write it in the layout the match spans came in.  PACKED: one word a span and
+// every column's bytes of the tile, summed over the wave, as tile_tot[column][tile] (what k_spans_write_tile2 sizes
+// the columns from); otherwise begins / lens.  No LDS.
+struct TokenSpanArgs {
+  ColView in;
+  const int32_t* counts;  // matches per row (count_re)
+  int maxsplit, reverse;
+  int mwidth;  // match columns the scan left
+  int ncols;   // token columns
+  const uint32_t* mspans;  // PACKED
+  const int32_t* mbegins;  // otherwise
+  const int32_t* mlens;
+  uint32_t* tspans;   // PACKED
+  int32_t* tile_tot;
+  int32_t* tbegins;   // otherwise
+  int32_t* tlens;
+  long long nsub;
+};
+template <bool PACKED>
+__global__ void __launch_bounds__(256) k_token_spans(TokenSpanArgs a) {
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+  const long long rows = a.in.rows;
+  for (long long tile = (long long)blockIdx.x * 4 + wv; tile < a.nsub; tile += (long long)gridDim.x * 4) {
+    const long long r = tile * 64 + lane;
+    const bool in_rows = r < rows;
+    const bool live = in_rows && row_is_valid(a.in.validity, r);
+    int n = 0, m = 0;
+    if (live) {
+      n = (int)(a.in.offsets[r + 1] - a.in.offsets[r]);
+      m = max(a.counts[r], 0);
+    }
+    const int s = live ? cssre::cuts(m, a.maxsplit) : -1;  // (-1: no token 0 either)
+    const int c0 = cssre::first_cut(m, max(s, 0), a.reverse != 0);
+    cssre::Walk w;
+    for (int k = 0; k < a.ncols; ++k) {
+      int mb = n, ml = 0;
+      if (in_rows && c0 + k < a.mwidth) {  // (not `k < s`: the address does not wait for the row's cut count)
+        const long long at = (long long)(c0 + k) * rows + r;
+        if (PACKED) {
+          const uint32_t x = a.mspans[at];
+          if (x != cssre::kNullSpan) {
+            mb = (int)(x >> 16);
+            ml = (int)(x & 0xFFFFu);
+          }
+        } else {
+          const int len = a.mlens[at];
+          if (len >= 0) {
+            mb = a.mbegins[at];
+            ml = len;
+          }
+        }
+      }
+      // (the span writers trust begin + length to lie inside the row: a cut is kept behind the previous one and inside the row)
+      mb = min(max(mb, w.prev_end), n);
+      ml = min(ml, n - mb);
+      int tb = 0, tl = 0;
+      const bool has = live && cssre::token_span(w, k, s, n, mb, ml, tb, tl);
+      const long long to = (long long)k * rows + r;
+      if (PACKED) {
+        if (in_rows) a.tspans[to] = has ? ((uint32_t)tb << 16) | (uint32_t)tl : cssre::kNullSpan;
+        const int tot = wave_reduce_sum(has ? tl : 0);
+        if (lane == 0) a.tile_tot[(long long)k * a.nsub + tile] = tot;
+      } else if (in_rows) {
+        a.tbegins[to] = has ? tb : 0;
+        a.tlens[to] = has ? tl : -1;
+      }
+    }
+  }
+}
+
+// One split_re / rsplit_re call and what its steps share.
+struct SplitReCall {
+  SpanRun r;
+  int maxsplit;
+  bool reverse;
+  Buf counts;          // matches per row
+  int most = 0;        // ... of the busiest row (M)
+  int width = 0;       // match columns scanned (W)
+  int ntokens = 0;     // token columns
+  SpanBufs matches, tokens;
+  Plan pl{};           // (findall_rowwise: the list simulator's arena lives until the columns are written)
+};
+// Step 1: matches per row and their maximum; with it the widths of the match scan and of the result.
+void splitre_count(SplitReCall& c) {
+  Buf dmax = dev_alloc(8, c.r.s);
+  c.most = findall_count_rows(c.r, dmax, &c.counts);
+  const int cut = c.maxsplit > 0 ? std::min(c.most, c.maxsplit) : c.most;
+  c.width = c.reverse ? c.most : cut;  // (from the right the last matches cut: all of them are needed)
+  c.ntokens = cut + 1;
+}
+// Step 2: the first `width` match spans of every row -- the stream kernel on its tiles (packed while the token columns
+// fit one launch of the packed writer), else a thread a row.
+void splitre_match_spans(SplitReCall& c) {
+  Buf unused = dev_alloc(8, c.r.s);
+  const bool stream = use_tdfa(c.r.re) && !cs::cfg("CS_REGEX_ROWWISE") && findall_stream(c.r, unused, c.matches, c.width, kMaxGroups - 1) >= 0;
+  if (!stream) c.pl = findall_rowwise(c.r, c.width, c.matches);
+  CS_HIP(hipGetLastError());
+  note_route(c.matches.packed ? "splitre-packed" : stream ? "splitre-stream" : "splitre-rowwise");
+}
+// Step 3: token spans, in the layout of the match spans.
+void splitre_token_spans(SplitReCall& c) {
+  const hipStream_t s = c.r.s;
+  const int64_t rows = c.r.col->rows;
+  c.tokens.alloc(rows, c.ntokens, c.matches.packed, s);
+  c.tokens.cap = c.matches.cap;
+  TokenSpanArgs a{};
+  a.in = view_of(c.r.col);
+  a.counts = ptr<const int32_t>(c.counts);
+  a.maxsplit = c.maxsplit;
+  a.reverse = c.reverse ? 1 : 0;
+  a.mwidth = c.width;
+  a.ncols = c.ntokens;
+  a.mspans = ptr<const uint32_t>(c.matches.spans);
+  a.mbegins = ptr<const int32_t>(c.matches.begins);
+  a.mlens = ptr<const int32_t>(c.matches.lens);
+  a.tspans = ptr<uint32_t>(c.tokens.spans);
+  a.tile_tot = ptr<int32_t>(c.tokens.tile_tot);
+  a.tbegins = ptr<int32_t>(c.tokens.begins);
+  a.tlens = ptr<int32_t>(c.tokens.lens);
+  a.nsub = (rows + 63) / 64;
+  const unsigned grid = (unsigned)std::min<long long>((a.nsub + 3) / 4, 256 * 16);
+  ProfScope ps("k_token_spans", s);
+  if (c.matches.packed) hipLaunchKernelGGL(k_token_spans<true>, dim3(grid), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(k_token_spans<false>, dim3(grid), dim3(256), 0, s, a);
+  CS_HIP(hipGetLastError());
+}
+// The whole route; step 4 is columns_from on the token spans.
+void split_re_columns(const cs_column* col, const cs_regex* cre, int maxsplit, bool reverse, hipStream_t s,
+                      std::vector<std::unique_ptr<cs_column>>& cols) {
+  if (cre->empty_pattern) fail(CS_ERR_INVALID_ARG, "split_re: the pattern cannot be null or empty");
+  if (csrx::min_match_chars(cre->prog) == 0) fail(CS_ERR_INVALID_ARG, "split_re: the pattern matches the empty string");
+  if (col->rows == 0) {  // (as cs_split: one column of no rows)
+    cols.emplace_back(make_all_null(0, s));
+    return;
+  }
+  SplitReCall c{SpanRun{col, const_cast<cs_regex*>(cre), s}, maxsplit, reverse};
+  splitre_count(c);
+  if (c.most == 0) {  // no row is cut: the one column is the input's rows
+    cols.emplace_back(share_column(col, s));
+    return;
+  }
+  splitre_match_spans(c);
+  splitre_token_spans(c);
+  columns_from(col, c.ntokens, c.tokens, s, cols);
+}
+int split_re_entry(const cs_column* col, const cs_regex* cre, int maxsplit, bool reverse, cs_stream stream, cs_column*** out_cols, int* ncols_out) {
+  return guard([&] {
+    if (!col || !cre || !out_cols || !ncols_out) fail(CS_ERR_INVALID_ARG, "split_re: null argument");
+    *out_cols = nullptr;
+    *ncols_out = 0;
+    require_device();
+    std::vector<std::unique_ptr<cs_column>> cols;
+    split_re_columns(col, cre, maxsplit, reverse, S(stream), cols);
+    release_columns(cols, out_cols, ncols_out);
+  });
+}
+// The record form: the columns above through the transposition of cs_records_from_columns(ragged = 1) -- a row's
+// leading non-null columns are its tokens.
+int split_record_re_entry(const cs_column* col, const cs_regex* cre, int maxsplit, bool reverse, int64_t* list_offsets, int on_device,
+                          cs_stream stream, cs_column** out) {
+  int transposed = CS_OK;
+  const int made = guard([&] {
+    if (!col || !cre || !out || !list_offsets) fail(CS_ERR_INVALID_ARG, "split_record_re: null argument");
+    *out = nullptr;
+    require_device();
+    std::vector<std::unique_ptr<cs_column>> cols;
+    split_re_columns(col, cre, maxsplit, reverse, S(stream), cols);
+    std::vector<const cs_column*> view;
+    for (const auto& c : cols) view.push_back(c.get());
+    transposed = cs_records_from_columns(view.data(), (int)view.size(), 1, list_offsets, on_device, stream, out);
+  });
+  return made != CS_OK ? made : transposed;
+}
+
 }  // namespace
 
 extern "C" {
+
+// split_re / rsplit_re and their record forms (no member of the reference: DESIGN.md section 4l; splitre_ops.h).
+int cs_split_re(const cs_column* col, const cs_regex* re, int maxsplit, cs_stream stream, cs_column*** out_cols, int* ncols) {
+  return split_re_entry(col, re, maxsplit, false, stream, out_cols, ncols);
+}
+int cs_rsplit_re(const cs_column* col, const cs_regex* re, int maxsplit, cs_stream stream, cs_column*** out_cols, int* ncols) {
+  return split_re_entry(col, re, maxsplit, true, stream, out_cols, ncols);
+}
+int cs_split_record_re(const cs_column* col, const cs_regex* re, int maxsplit, int64_t* list_offsets, int on_device, cs_stream stream,
+                       cs_column** out) {
+  return split_record_re_entry(col, re, maxsplit, false, list_offsets, on_device, stream, out);
+}
+int cs_rsplit_record_re(const cs_column* col, const cs_regex* re, int maxsplit, int64_t* list_offsets, int on_device, cs_stream stream,
+                        cs_column** out) {
+  return split_record_re_entry(col, re, maxsplit, true, list_offsets, on_device, stream, out);
+}
 
 // NVStrings::extract(pattern, results) (NVStrings.h:682; extract.cu:69-151): one column per
 // capture group; a pattern without groups, or an empty column, yields no columns.

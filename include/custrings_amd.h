@@ -391,6 +391,25 @@ int cs_split_record(const cs_column* col, const char* delimiter, int maxsplit,
                     int64_t* list_offsets, int on_device, cs_stream stream, cs_column** out);
 int cs_rsplit_record(const cs_column* col, const char* delimiter, int maxsplit,
                      int64_t* list_offsets, int on_device, cs_stream stream, cs_column** out);
+/* split_re / rsplit_re: split every row at the matches of a compiled pattern (no
+ * member of the reference; pandas / Spark semantics).  A row's matches are those
+ * cs_count_re counts and cs_findall returns.  With m matches a row has s = m cuts
+ * (maxsplit <= 0) or min(m, maxsplit): cs_split_re cuts at the first s matches,
+ * cs_rsplit_re at the last s; the row has s + 1 tokens, empty strings where two
+ * cuts are adjacent or a cut touches an end of the row.  Column-major result as
+ * cs_split (same ownership): column k holds token k, null from a row's token count
+ * on and for null rows; zero rows and only null rows answer as cs_split.  The
+ * record forms return the flat column and list offsets of cs_split_record (a null
+ * row has no entries).  The empty pattern and a pattern that can match the empty
+ * string are CS_ERR_INVALID_ARG. */
+int cs_split_re(const cs_column* col, const cs_regex* re, int maxsplit, cs_stream stream,
+                cs_column*** out_cols, int* ncols);
+int cs_rsplit_re(const cs_column* col, const cs_regex* re, int maxsplit, cs_stream stream,
+                 cs_column*** out_cols, int* ncols);
+int cs_split_record_re(const cs_column* col, const cs_regex* re, int maxsplit,
+                       int64_t* list_offsets, int on_device, cs_stream stream, cs_column** out);
+int cs_rsplit_record_re(const cs_column* col, const cs_regex* re, int maxsplit,
+                        int64_t* list_offsets, int on_device, cs_stream stream, cs_column** out);
 /* NVStrings::partition / rpartition (NVStrings.h:537,549; split.cu:1165-1361):
  * three strings per row -- head, delimiter, tail around the first (last)
  * occurrence; no occurrence: (row, "", "") / ("", "", row); a null row: three

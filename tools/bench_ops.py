@@ -61,7 +61,7 @@ def report(config, op, rows, in_bytes, alg_bytes, dt):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scale", type=float, default=1.0, help="row-count multiplier (1.0 = BASELINE.json single-GPU sizes)")
-    ap.add_argument("--only", default="C2,C3,C4,C5", help="comma-separated configs to run (CONV: the conversion ops, TS: the timestamp ones, PAD: substring / padding / wrapping, CHR: character types and swapcase / capitalize / title, TXT: the NVText matches, edit distance, stemmer measure and scatter_count, URL: url_encode / url_decode / translate / fillna, NUM: the numeric categories -- from_numbers, to_numbers, merge_and_remap -- beside two yardsticks, CSV: from_csv -- the line-start kernels, the field locator and the whole call, STATS: compute_statistics / get_info -- the fused pass beside the separate ops, the histogram layouts, the whole call, MINHASH: minhash on short and long rows at nperm 1 / 64 / 256 and the band keys)")
+    ap.add_argument("--only", default="C2,C3,C4,C5", help="comma-separated configs to run (CONV: the conversion ops, TS: the timestamp ones, PAD: substring / padding / wrapping, CHR: character types and swapcase / capitalize / title, TXT: the NVText matches, edit distance, stemmer measure and scatter_count, URL: url_encode / url_decode / translate / fillna, NUM: the numeric categories -- from_numbers, to_numbers, merge_and_remap -- beside two yardsticks, CSV: from_csv -- the line-start kernels, the field locator and the whole call, STATS: compute_statistics / get_info -- the fused pass beside the separate ops, the histogram layouts, the whole call, MINHASH: minhash on short and long rows at nperm 1 / 64 / 256 and the band keys, SPLITRE: split_re at three patterns with its steps' kernel times beside split and findall)")
     a = ap.parse_args()
     only = set(a.only.split(","))
     ov = 8.125  # native offset + validity bytes per row
@@ -94,6 +94,44 @@ def main():
         run_stats(a)
     if "MINHASH" in only:
         run_minhash(a)
+    if "SPLITRE" in only:
+        run_splitre(a)
+
+
+def run_splitre(a):
+    """split_re (cs_split_re) on the C3 and C5 columns at 2M rows (x --scale): the whole call at ' ', '\\s+' and
+    ' - | \\[|\\] ', the steps' kernel times from the profiling hooks in a run of their own (count scan, span scan, token
+    spans, writers) and k_token_spans' share; beside them two yardsticks on the same column -- the literal split(' ') and
+    findall('[^ ]+'), the same scan and writers at a width found by a provisional pass."""
+    from custrings_amd import splitre
+
+    rows = int(2_000_000 * a.scale)
+    kernels = (b"k_count_re", b"k_findall_spans", b"k_token_spans", b"k_extract_write")
+    for name, kind in (("C3", 3), ("C5", 5)):
+        col = synth(kind, rows)
+        n, nb = col.size(), nbytes(col)
+        calls = [("split(' ')", lambda: col.split(" ")), ("findall('[^ ]+')", lambda: col.findall("[^ ]+"))]
+        calls += [("split_re(%r)" % p, (lambda p: lambda: splitre.split_re(col, p))(p)) for p in (" ", r"\s+", r" - | \[|\] ")]
+        for op, fn in calls:
+            ncols = len(fn())
+            dt = timed(fn, reps=5)
+            line = {"config": "SPLITRE " + name, "op": op, "rows": n, "bytes": nb, "columns": ncols, "ms": round(dt * 1e3, 3),
+                    "input_GBps": round((nb + 8.125 * n) / dt / 1e9, 1)}
+            if op.startswith("split_re"):
+                L.cs_prof_reset()
+                L.cs_prof_enable(1)
+                reps = 3
+                for _ in range(reps):
+                    fn()
+                torch.cuda.synchronize()
+                L.cs_prof_enable(0)
+                for kern in kernels:
+                    ms, k = C.c_double(), C.c_int64()
+                    L.cs_prof_get(kern, C.byref(ms), C.byref(k))
+                    line[kern.decode() + "_ms"] = round(ms.value / reps, 3)
+                line["token_spans_share"] = round(line["k_token_spans_ms"] / (dt * 1e3), 4)
+            print(json.dumps(line), flush=True)
+        del col
 
 
 def run_minhash(a):
