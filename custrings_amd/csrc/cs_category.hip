@@ -840,6 +840,23 @@ cs_category* cs::category_build(const cs_column* col, hipStream_t s) {
   cat->keys = keys_column(in, t, r, d.uniq, shift, s);
   return cat.release();
 }
+void cs::remap_codes(const int32_t* codes, int64_t n, const int32_t* table, int32_t* out, hipStream_t s) {
+  if (n) hipLaunchKernelGGL(k_remap, dim3(blocks_for(n)), dim3(kBlock), 0, s, codes, n, table, out);
+  CS_HIP(hipGetLastError());
+}
+cs_category* cs::merge_key_sets(const cs_category* local, const std::vector<const cs_column*>& sets, int rank, Buf values, hipStream_t s) {
+  int64_t before = 0;
+  for (int r = 0; r < rank; ++r) before += sets[r]->rows;
+  std::unique_ptr<cs_column> all_keys(concat_columns(sets, s));
+  std::unique_ptr<cs_category> all(category_build(all_keys.get(), s));
+  auto merged = std::make_unique<cs_category>();
+  merged->rows = local->rows;
+  merged->values = values ? values : dev_alloc(sizeof(int32_t) * (size_t)std::max<int64_t>(local->rows, 1), s);
+  remap_codes(ptr<const int32_t>(local->values), local->rows, ptr<const int32_t>(all->values) + before, ptr<int32_t>(merged->values), s);
+  merged->keys = std::move(all->keys);
+  CS_HIP(hipStreamSynchronize(s));
+  return merged.release();
+}
 
 extern "C" {
 
@@ -879,10 +896,7 @@ int cs_category_merge(const cs_category* const* cats, int ncats, cs_stream strea
     int64_t key_base = 0, row_base = 0;
     for (int i = 0; i < ncats; ++i) {
       const cs_category* c = cats[i];
-      if (c->rows)
-        hipLaunchKernelGGL(k_remap, dim3(blocks_for(c->rows)), dim3(kBlock), 0, s, ptr<const int32_t>(c->values),
-                           c->rows, ptr<const int32_t>(merged->values) + key_base,
-                           ptr<int32_t>(res->values) + row_base);
+      remap_codes(ptr<const int32_t>(c->values), c->rows, ptr<const int32_t>(merged->values) + key_base, ptr<int32_t>(res->values) + row_base, s);
       key_base += c->keys->rows;
       row_base += c->rows;
     }
@@ -905,24 +919,11 @@ int cs_category_merge_gathered(const cs_category* local, const cs_column* const*
     if (!local || !keysets || !merged_keys || nranks < 1 || rank < 0 || rank >= nranks) fail(CS_ERR_INVALID_ARG, "merge_gathered: bad arguments");
     if (local->rows > 0 && !values) fail(CS_ERR_INVALID_ARG, "merge_gathered: no room for the values");
     require_device();
-    hipStream_t s = S(stream);
-    std::vector<const cs_column*> sets;
-    int64_t before = 0;
-    for (int r = 0; r < nranks; ++r) {
+    for (int r = 0; r < nranks; ++r)
       if (!keysets[r]) fail(CS_ERR_INVALID_ARG, "merge_gathered: null key set");
-      if (r < rank) before += keysets[r]->rows;
-      sets.push_back(keysets[r]);
-    }
     if (keysets[rank]->rows != local->keys->rows) fail(CS_ERR_INVALID_ARG, "merge_gathered: keysets[rank] is not the local key set");
-    // the category of the concatenated key sets: its keys are the merged key set, its codes the old-code -> new-code
-    // tables of the ranks, back to back
-    std::unique_ptr<cs_column> all_keys(concat_columns(sets, s));
-    std::unique_ptr<cs_category> merged(category_build(all_keys.get(), s));
-    if (local->rows)
-      hipLaunchKernelGGL(k_remap, dim3(blocks_for(local->rows)), dim3(kBlock), 0, s, ptr<const int32_t>(local->values), local->rows,
-                         ptr<const int32_t>(merged->values) + before, values);
-    CS_HIP(hipGetLastError());
-    CS_HIP(hipStreamSynchronize(s));
+    const std::vector<const cs_column*> sets(keysets, keysets + nranks);
+    std::unique_ptr<cs_category> merged(merge_key_sets(local, sets, rank, dev_wrap(values, sizeof(int32_t) * (size_t)local->rows), S(stream)));
     *merged_keys = merged->keys.release();
   });
 }
@@ -953,8 +954,7 @@ int cs_remap_codes(const int32_t* codes, int64_t n, const int32_t* table, int32_
   return guard([&] {
     if (n < 0 || (n > 0 && (!codes || !table || !out))) fail(CS_ERR_INVALID_ARG, "null argument");
     require_device();
-    if (n) hipLaunchKernelGGL(k_remap, dim3(blocks_for(n)), dim3(kBlock), 0, S(stream), codes, n, table, out);
-    CS_HIP(hipGetLastError());
+    remap_codes(codes, n, table, out, S(stream));
   });
 }
 

@@ -390,6 +390,13 @@ int split_single(const SplitCall& c, const SplitPlan& p, std::vector<std::unique
 void radix_sort_pairs64(uint64_t* keys, int32_t* items, int64_t n, hipStream_t s);
 // cs_category.hip: keys = sorted unique rows (null first), values[r] = index of row r's key
 cs_category* category_build(const cs_column* col, hipStream_t s);
+// cs_category.hip: out[i] = table[codes[i]] for n codes (a negative code stays as it is); queued on `s`, not waited for
+void remap_codes(const int32_t* codes, int64_t n, const int32_t* table, int32_t* out, hipStream_t s);
+// cs_category.hip: the merge that follows the exchange of a distributed build.  `sets[r]` = rank r's sorted key set
+// (this rank's own, local->keys, at `rank`).  The category of their concatenation has the merged keys, and its codes are
+// the ranks' old-code -> new-code tables, back to back: the local rows' codes go through this rank's slice of them into
+// `values` (room for local->rows int32; null: allocated here, after the build).  Waits for `s`: the sets may leave scope.
+cs_category* merge_key_sets(const cs_category* local, const std::vector<const cs_column*>& sets, int rank, Buf values, hipStream_t s);
 // cs_array.hip: rows of `col` at the given device positions; with `null_when_negative` a negative
 // position yields a null row instead of CS_ERR_RANGE
 cs_column* gather_rows(const cs_column* col, const int32_t* d_pos, int64_t n, hipStream_t s, bool null_when_negative = false);

@@ -112,6 +112,146 @@ def test_gpu_two_rank_exchanges_with_the_gpu_ops(gpu_engine, world):
     assert sum((list(g[7][5]) for g in got), []) == list(want_values)
 
 
+class _Recorder:
+    """Records, while active, every collective that global_category_c_abi's callbacks make in this process -- the kind and
+    the sizes -- by wrapping the two module-level lookups of custrings_amd/dist.py (dist.all_gather, _all_to_all_by_gather)."""
+
+    def __init__(self, csd):
+        self.csd, self.calls = csd, []
+
+    def __enter__(self):
+        csd, calls = self.csd, self.calls
+        self.saved = gather, a2a = csd.dist.all_gather, csd._all_to_all_by_gather
+
+        def all_gather(parts, mine, group=None):
+            calls.append(("all_gather", int(mine.numel())))
+            return gather(parts, mine, group=group)
+
+        def all_to_all(ins, outs, group):
+            calls.append(("all_to_all", [int(t.numel()) for t in outs], [int(t.numel()) for t in ins]))
+            return a2a(ins, outs, group)
+
+        csd.dist.all_gather, csd._all_to_all_by_gather = all_gather, all_to_all
+        return self
+
+    def __exit__(self, *exc):
+        self.csd.dist.all_gather, self.csd._all_to_all_by_gather = self.saved
+
+
+def _assert_in_step(traces, what):
+    """`traces[r]` = rank r's recorded collectives: the same number of them on every rank, of the same kinds in the same
+    order; equal pieces in every all-gather; in every all-to-all rank a sends rank b what rank b expects from rank a."""
+    world = len(traces)
+    assert len({len(t) for t in traces}) == 1, (what, [len(t) for t in traces])
+    for i, calls in enumerate(zip(*traces)):
+        assert len({c[0] for c in calls}) == 1, (what, i, calls)
+        if calls[0][0] == "all_gather":
+            assert len({c[1] for c in calls}) == 1, (what, i, calls)
+        else:
+            for a in range(world):
+                for b in range(world):
+                    assert calls[a][1][b] == calls[b][2][a], (what, i, a, b, calls)
+
+
+def _run_ranks(target, world, args_of, timeout=180):
+    """Starts `world` workers (`args_of(rank, queue)`: a worker's arguments), collects one result of each, and leaves no
+    child behind: a wrong exchange ends as a failed test and not as processes left waiting."""
+    import torch.multiprocessing as mp
+
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    procs = [ctx.Process(target=target, args=args_of(r, q)) for r in range(world)]
+    try:
+        for p in procs:
+            p.start()
+        got = sorted(q.get(timeout=timeout) for _ in range(world))
+        for p in procs:
+            p.join(timeout=60)
+    finally:
+        for p in procs:
+            if p.is_alive():
+                p.terminate()
+    assert all(g[1] == "ok" for g in got), [g[2] for g in got if g[1] != "ok"]
+    return got
+
+
+def _edge_cases():
+    """(name, rows of rank 0, 1, 2): the shapes that merge_partitioned guards by hand."""
+    skew = [["a%02d" % (i * 7 % 40) for i in range(50)], ["m%02d" % (i * 11 % 40) for i in range(45)] + ["t07"], ["t%02d" % (i * 3 % 40) for i in range(40)] + ["m05", None]]
+    return [
+        ("rank 1 has no rows", [["pear", "apple", "pear"], [], ["fig", "apple", "zebra"]]),
+        ("every row is null", [[None, None], [None], [None, None, None]]),
+        ("two keys, three ranks", [["a", "b"], ["b", "a", "a"], ["a"]]),
+        ("a null row and the empty string", [["", "x", ""], ["x", "y"], [None, "", "y"]]),
+        ("one key everywhere", [["k", "k"], ["k"], ["k", "k", "k"]]),
+        ("rank 0 below the others", skew),
+        ("multi-byte and long keys", [["\u00e9", "a", "a key longer than sixteen bytes", "zz"], ["\u65e5\u672c\u8a9e", "\u00df", "a"], ["\U0001f600", "zz", "\u00e9t\u00e9", "b"]]),
+    ]
+
+
+def _expected_category(shards):
+    """Plain Python: keys = [None] if any row is null, then the distinct strings sorted as UTF-8 bytes; values = each row's
+    index in that list, per rank."""
+    rows = [r for sh in shards for r in sh]
+    keys = ([None] if None in rows else []) + sorted({r for r in rows if r is not None}, key=lambda t: t.encode("utf-8"))
+    return keys, [[keys.index(r) for r in sh] for sh in shards]
+
+
+def _edge_worker(rank, world, port, q):
+    sys.path.insert(0, os.path.dirname(HERE))
+    sys.path.insert(0, HERE)
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
+    try:
+        import torch
+        import torch.distributed as dist
+
+        torch.cuda.set_device(0)
+        dist.init_process_group("gloo", rank=rank, world_size=world)
+        from custrings_amd import _lib, nvstrings
+        from custrings_amd import dist as csd
+
+        _lib.ensure_init(0)
+        res = []
+        for _name, shards in _edge_cases():
+            col = nvstrings.to_device(shards[rank])
+            for forced in (b"1", b"0"):
+                _lib.check(_lib.lib.cs_config_set(b"CS_DIST_PARTITIONED", forced))
+                try:
+                    with _Recorder(csd) as rec:
+                        cat = csd.global_category_c_abi(col)
+                finally:
+                    _lib.check(_lib.lib.cs_config_set(b"CS_DIST_PARTITIONED", None))
+                res.append((cat.keys().to_host(), list(cat.values()), rec.calls))
+        q.put((rank, "ok", res))
+        dist.barrier()
+        dist.destroy_process_group()
+    except Exception as e:
+        import traceback
+
+        q.put((rank, "error", traceback.format_exc() + repr(e)))
+
+
+def test_gpu_distributed_build_edge_table():
+    """The shapes the partitioned merge guards by hand (a rank without rows, null keys only, fewer splitters than ranges, the
+    null key beside the empty string, skew, multi-byte and long keys), three ranks, each through the key-range route and the
+    all-gather route: every rank returns exactly the keys and its own rows' values that plain Python computes from the
+    concatenated rows, and in every run the ranks made the same collectives with sizes that fit each other."""
+    world = 3
+    port = 39500 + (os.getpid() % 2000)
+    got = _run_ranks(_edge_worker, world, lambda r, q: (r, world, port, q))
+    runs = iter(zip(*(g[2] for g in got)))
+    for name, shards in _edge_cases():
+        want_keys, want_values = _expected_category(shards)
+        for route in ("partitioned", "gathered"):
+            per_rank = next(runs)
+            for r in range(world):
+                assert per_rank[r][0] == want_keys, (name, route, r, per_rank[r][0], want_keys)
+                assert per_rank[r][1] == want_values[r], (name, route, r, per_rank[r][1], want_values[r])
+            traces = [p[2] for p in per_rank]
+            _assert_in_step(traces, (name, route))
+            assert any(c[0] == "all_to_all" for c in traces[0]) == (route == "partitioned"), (name, route, traces[0])
+
+
 def _failing_worker(rank, world, port, rows, q, fail_at=None):
     sys.path.insert(0, os.path.dirname(HERE))
     sys.path.insert(0, HERE)
@@ -138,14 +278,16 @@ def _failing_worker(rank, world, port, rows, q, fail_at=None):
             _lib.check(_lib.lib.cs_config_set(b"CS_DIST_PARTITIONED", b"1"))
             _lib.check(_lib.lib.cs_config_set(b"CS_DIST_TEST_FAIL_AT", fail_at.encode()))
         try:
-            csd.global_category_c_abi(col)
+            with _Recorder(csd) as failed:
+                csd.global_category_c_abi(col)
             res = "no error"
         except RuntimeError as e:
             res = str(e)
         _lib.check(_lib.lib.cs_config_set(b"CS_DIST_TEST_FAIL", None))
         _lib.check(_lib.lib.cs_config_set(b"CS_DIST_TEST_FAIL_AT", None))
-        ok = csd.global_category_c_abi(col).keys_size()  # the ranks are still in step: the next build works
-        q.put((rank, "ok", res, ok))
+        with _Recorder(csd) as after:
+            ok = csd.global_category_c_abi(col).keys_size()  # the ranks are still in step: the next build works
+        q.put((rank, "ok", res, ok, failed.calls, after.calls))
         dist.barrier()
         dist.destroy_process_group()
     except Exception as e:
@@ -172,6 +314,8 @@ def test_gpu_distributed_build_fails_on_every_rank_together():
     assert all(g[1] == "ok" for g in got), [g[2] for g in got if g[1] != "ok"]
     assert all("rank 1 failed before the exchange" in g[2] for g in got), [g[2] for g in got]
     assert got[0][3] == got[1][3] > 0
+    _assert_in_step([g[4] for g in got], "the failed build")  # (all ranks stopped after the same number of collectives)
+    _assert_in_step([g[5] for g in got], "the build after it")
 
 
 @pytest.mark.parametrize("fail_at", ["1:1", "1:2", "0:3", "1:4"])
@@ -196,6 +340,20 @@ def test_gpu_partitioned_merge_fails_on_every_rank_together(fail_at):
     assert "simulated failure in stage %s" % stage in got[int(bad_rank)][2], got[int(bad_rank)][2]
     assert ("rank %s failed" % bad_rank) in got[1 - int(bad_rank)][2], got[1 - int(bad_rank)][2]
     assert got[0][3] == got[1][3] > 0
+    _assert_in_step([g[4] for g in got], "the failed build")  # (all ranks stopped after the same number of collectives)
+    _assert_in_step([g[5] for g in got], "the build after it")
+
+
+def test_gpu_partitioned_merge_fails_on_three_ranks_together():
+    """The same agreement with three ranks, the last one failing in the last stage: rank 2 reports its own (simulated)
+    failure, ranks 0 and 1 name rank 2, all three stop after the same collectives, and the next build works."""
+    port = 41500 + (os.getpid() % 2000)
+    got = _run_ranks(_failing_worker, 3, lambda r, q: (r, 3, port, 20_000, q, "2:4"))
+    assert "simulated failure in stage 4" in got[2][2], got[2][2]
+    assert all("rank 2 failed" in g[2] for g in got[:2]), [g[2] for g in got[:2]]
+    assert got[0][3] == got[1][3] == got[2][3] > 0
+    _assert_in_step([g[4] for g in got], "the failed build")
+    _assert_in_step([g[5] for g in got], "the build after it")
 
 
 def test_gpu_category_build_distributed_over_rccl():
