@@ -134,8 +134,10 @@ __global__ void __launch_bounds__(256) k_case_tile(CaseTileArgs a) {
         }
         malformed |= expect != 0;
         if (any && malformed) {
-          if (row_case_size(p, n, a.flags, a.cases, a.bit) != n) resized = true;
-          else row_case_write(p, n, a.flags, a.cases, a.bit, o);
+          // the sequential routine alone decides for such a row: a character that changes its width in front of the
+          // malformed bytes may be made up for behind them (what `resized` holds is of the walk above, which stopped)
+          resized = row_case_size(p, n, a.flags, a.cases, a.bit) != n;
+          if (!resized) row_case_write(p, n, a.flags, a.cases, a.bit, o);
         }
         if (resized) atomicOr(a.changed, 1u);
       }

@@ -458,7 +458,11 @@ static int change_case(const cs_column* col, unsigned bit, cs_stream stream, cs_
       }
       return true;
     }();
-    if (change_case_fast(col, bit, ascii_rule_ok, S(stream), out)) return;
+    if (change_case_fast(col, bit, ascii_rule_ok, S(stream), out)) {
+      note_route("tile");
+      return;
+    }
+    note_route("rows");
     *out = two_pass(col, CaseSize{d_unicode_flags(), d_charcases(), bit},
                     CaseWrite{d_unicode_flags(), d_charcases(), bit}, S(stream),
                     bit == 32 ? "k_lower_size" : "k_upper_size", nm);

@@ -309,45 +309,42 @@ CS_HD void row_strip(const uint8_t* p, int n, const CharSet& set, int side, int&
 
 // ---- lower / upper -------------------------------------------------------------
 // flag bit 32 = upper (lower() maps these), 64 = lower (upper() maps these)
-CS_HD int row_case_size(const uint8_t* p, int n, const uint8_t* flags, const uint16_t* cases,
-                        unsigned bit) {
-  int out = 0;
-  for (int i = 0; i < n;) {
-    uint8_t b = p[i];
-    if (b < 0x80) {  // ASCII maps to ASCII
-      ++out;
+// The reference walks a row with its character iterator (case.cu:49,81; custring_view.inl:361-392): one step for every byte
+// that is no continuation byte, each step decoding at the iterator's offset and advancing it by the width the byte there
+// implies.  On well-formed rows that is one step a character.  On any other row it is restated as it stands: a stray
+// continuation byte has width 0, so every remaining step reads it again; a lead byte takes the bytes behind it whatever
+// they are, and a step at or past the row's end reads the terminator (a zero byte of width 1).
+template <class Emit>
+CS_HD void row_case_walk(const uint8_t* p, int n, const uint8_t* flags, const uint16_t* cases, unsigned bit, Emit&& emit) {
+  int i = 0;
+  for (int left = count_chars(p, n); left > 0; --left) {
+    if (i < n && p[i] < 0x80) {  // ASCII maps to ASCII
+      const uint8_t b = p[i];
+      emit((Char)((flags[b] & bit) ? (uint8_t)cases[b] : b), 1u);
       ++i;
       continue;
     }
-    Char ch;
-    unsigned w = decode_at(p, i, n, ch);
-    if (w == 0) w = 1;
+    Char ch = 0;
+    unsigned w = 1;
+    if (i < n) w = decode_at(p, i, n, ch);
     unsigned u = packed_to_cp(ch);
     unsigned f = u <= 0xFFFF ? flags[u] : 0;
-    out += (f & bit) ? (int)packed_width(cp_to_packed(cases[u])) : (int)packed_width(ch);
+    if (f & bit) ch = cp_to_packed(cases[u]);
+    emit(ch, packed_width(ch));
     i += (int)w;
   }
+}
+CS_HD int row_case_size(const uint8_t* p, int n, const uint8_t* flags, const uint16_t* cases,
+                        unsigned bit) {
+  int out = 0;
+  row_case_walk(p, n, flags, cases, bit, [&](Char, unsigned ow) { out += (int)ow; });
   return out;
 }
 CS_HD void row_case_write(const uint8_t* p, int n, const uint8_t* flags, const uint16_t* cases,
                           unsigned bit, uint8_t* o) {
-  for (int i = 0; i < n;) {
-    uint8_t b = p[i];
-    if (b < 0x80) {
-      *o++ = (flags[b] & bit) ? (uint8_t)cases[b] : b;
-      ++i;
-      continue;
-    }
-    Char ch;
-    unsigned w = decode_at(p, i, n, ch);
-    if (w == 0) w = 1;
-    unsigned u = packed_to_cp(ch);
-    unsigned f = u <= 0xFFFF ? flags[u] : 0;
-    if (f & bit) ch = cp_to_packed(cases[u]);
-    unsigned ow = packed_width(ch);
+  row_case_walk(p, n, flags, cases, bit, [&](Char ch, unsigned ow) {
     for (unsigned k = 0; k < ow; ++k) *o++ = (uint8_t)(ch >> (8 * (ow - 1 - k)));
-    i += (int)w;
-  }
+  });
 }
 
 // ---- split on a delimiter string -------------------------------------------------

@@ -178,6 +178,7 @@ def test_known_answers_cpp_program():
 # ---- differential: generated columns against the harness ---------------------------------------------------------------------
 ROWS = 1 << 20
 KINDS = ["ascii", "keep", "wide", "bytes", "long", "huge"]
+CASE_KINDS = KINDS + ["bytes_keep"]  # (the case ops only: arbitrary bytes on which the tile kernel's answer is the one returned)
 
 
 class _CachedHarness(m.Harness):
@@ -212,8 +213,26 @@ def _arbitrary_bytes(n, seed):
     return rows
 
 
+def _size_keeping(rows, harness):
+    """the rows of `rows` that swapcase, capitalize and title all leave at their size, by the harness's tile mode (-2: the
+    row's size would change)"""
+    arrow = m.to_arrow(rows)
+    keep = np.ones(len(rows), dtype=bool)
+    for op in m.CASE_OPS:
+        keep &= harness.run_arrow(op, *arrow, mode="tile")[0] != -2
+    return [r for r, k in zip(rows, keep.tolist()) if k]
+
+
+def _is_utf8(b):
+    try:
+        b.decode("utf-8")
+        return True
+    except UnicodeDecodeError:
+        return False
+
+
 @pytest.fixture(scope="module")
-def generated():
+def generated(harness):
     wide = set(m.width_changing())
     ascii_pool = m.gen_rows(20_000, seed=31, kind="ascii") + m.gen_rows(10_000, seed=32, kind="uniform")
     ascii_pool = [r for r in ascii_pool if r is None or all(ord(ch) < 128 for ch in r)]
@@ -233,6 +252,9 @@ def generated():
     long_rows[20_000] = "é1 ".encode() * 3000
     cols["long"] = long_rows
     cols["huge"] = [(b"xY z9 " * 2000) if i % 3 else ("Ünï " * 1500).encode() for i in range(600)]  # no tile fits
+    # arbitrary bytes that keep their size in all three case ops: no row raises `changed`, the tile kernel's rows are the answer
+    cols["bytes_keep"] = _size_keeping(_arbitrary_bytes(60_000, 46), harness)
+    assert sum(r is not None and not _is_utf8(r) for r in cols["bytes_keep"]) >= 1000
     return {k: (m.to_arrow(v), column(v)) for k, v in cols.items()}
 
 
@@ -277,7 +299,7 @@ def test_case_ops_against_harness(generated, harness, monkeypatch, op, rowwise):
     if rowwise:
         monkeypatch.setenv("CS_CASE_ROWWISE", "1")
     L = _L()
-    for kind in KINDS:
+    for kind in CASE_KINDS:
         (chars, offs, nulls), g = generated[kind]
         lens, hchars = harness.answer(op, kind, (chars, offs, nulls))
         rows = len(offs) - 1
@@ -287,7 +309,7 @@ def test_case_ops_against_harness(generated, harness, monkeypatch, op, rowwise):
         route = _route()
         if rowwise:
             assert route == "rows", kind
-        elif kind in ("ascii", "keep", "long"):
+        elif kind in ("ascii", "keep", "long", "bytes_keep"):
             assert route == "tile", (kind, route)  # the fast route, nothing handed over
         elif kind == "wide":
             assert route == "rows", (kind, route)  # some row changes its width: the two-pass kernels recompute the column
