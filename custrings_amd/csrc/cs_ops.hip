@@ -198,7 +198,9 @@ int64_t run_counted(const cs_column* col, const Op& op, void* results, int on_de
   T* out = static_cast<T*>(res.dev);
   {
     ProfScope ps(prof_name, s);
-    if (!tiles(out, ptr<unsigned long long>(cnt)))
+    const bool tiled = tiles(out, ptr<unsigned long long>(cnt));
+    note_route(tiled ? "tile" : "rows");
+    if (!tiled)
       hipLaunchKernelGGL(k_counted_rows<Op>, dim3(std::min(blocks_for(col->rows), 8192u)), dim3(kBlock), 0, s, view_of(col), op,
                          out, ptr<unsigned long long>(cnt));
   }
@@ -261,7 +263,7 @@ struct ContainsOp {  // contains(str) by bytes; an empty needle and a null row a
   using T = uint8_t;
   const uint8_t* needle;
   int nb;
-  __device__ T operator()(int64_t, const uint8_t* p, int n, bool valid) const { return nb > 0 && valid && find_bytes(p, 0, n, needle, nb) >= 0; }
+  __device__ T operator()(int64_t, const uint8_t* p, int n, bool valid) const { return valid && row_contains(p, n, needle, nb); }
   static __device__ bool counts(T v) { return v; }
 };
 struct MatchStringsOp {  // match_strings(other): equal rows; two nulls are equal
@@ -509,6 +511,7 @@ int cs_strip(const cs_column* col, const char* to_strip, int side, cs_stream str
     if (col->rows > 0 && !cs::cfg("CS_STRIP_ROWWISE")) {
       Built b(col, s);
       if (strip_single(col, set, side, s, b.col.get())) {  // one pass (cs_rows.hip: k_strip_stream)
+        note_route("strip-stream");
         *out = b.col.release();
         return;
       }
@@ -516,10 +519,13 @@ int cs_strip(const cs_column* col, const char* to_strip, int side, cs_stream str
       if (col->plain_bytes == 1) b.col->plain_bytes = 1;  // (rows cut at character boundaries of a plain column stay plain)
       if (col->high_sample == 0) b.col->high_sample = 0;
       b.alloc_chars();
-      if (!strip_write_tiles(col, set, side, b.off, b.chars, s)) write_rows(col, StripWrite{set, side}, s, "k_strip_write", b);
+      const bool tiled = strip_write_tiles(col, set, side, b.off, b.chars, s);
+      note_route(tiled ? "tile" : "rows");
+      if (!tiled) write_rows(col, StripWrite{set, side}, s, "k_strip_write", b);
       *out = b.col.release();
       return;
     }
+    note_route("rows");
     *out = two_pass(col, StripSize{set, side}, StripWrite{set, side}, S(stream), "k_strip_size", "k_strip_write");
   });
 }
@@ -645,6 +651,7 @@ int cs_find_multiple(const cs_column* col, const cs_column* targets, int32_t* re
     require_device();
     hipStream_t s = S(stream);
     const int64_t total = col->rows * targets->rows;
+    note_route("rows");
     const Buf cnt = zeroed_count(s);
     const ResultsOut res(results, sizeof(int32_t) * total, on_device, s);
     int32_t* d_out = static_cast<int32_t*>(res.dev);

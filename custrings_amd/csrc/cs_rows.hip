@@ -121,6 +121,7 @@ __global__ void __launch_bounds__(256) k_find_tile(FindTileArgs a) {
   cstile::RowTileWalk walk(in, a.rows_per_tile, a.ntiles, wv, lane);
   if (walk.done()) return;
   const uint32_t first4 = (uint32_t)a.needle[0] * 0x01010101u;
+  const bool cont_needle = a.nb > 0 && is_cont(a.needle[0]);
   // bits 0..3: which bytes of w are zero (exact, no borrow between bytes)
   auto zero4 = [](uint32_t w) { return cstile::gather_bit7(~(((w & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | w) & 0x80808080u); };
   auto cont4 = [](uint32_t w) { return cstile::gather_bit7(w & ~(w << 1) & 0x80808080u); };
@@ -189,6 +190,9 @@ __global__ void __launch_bounds__(256) k_find_tile(FindTileArgs a) {
           break;
         }
       }
+      // (a row of continuation bytes alone has no character and the reference finds nothing in it: only a needle of such
+      // bytes can be in one)
+      if (cont_needle && at >= 0 && no_chars_before(p, n, at)) at = -1;
     }
     if (MODE == 0) {
       int v = -2;  // null row (find.cu:108)
@@ -211,7 +215,7 @@ __global__ void __launch_bounds__(256) k_find_tile(FindTileArgs a) {
     } else {
       int hit = 0;
       if (by_bits) hit = at >= 0;
-      else if (live && a.nb > 0) hit = find_bytes(p, 0, n, s_needle, a.nb) >= 0;
+      else if (live) hit = row_contains(p, n, s_needle, a.nb);
       if (in_tile) a.out8[r0 + lane] = (uint8_t)hit;
       hits += hit;
     }

@@ -100,15 +100,47 @@ CS_HD int find_bytes(const uint8_t* p, int from, int to, const uint8_t* needle, 
 }
 
 // ---- find: char-position window in, char position out -----------------------
+// byte offset of character position `chpos` by the reference's table of widths (custring_view.inl:261-281): 0 for position
+// 0, the size from the character count on, position k for a row with as many characters as bytes, else the widths the
+// first chpos lead bytes ANNOUNCE, added up -- whatever stands behind a lead byte.  On well-formed rows that is the
+// character's offset.  (A sum beyond the row: the reference compares what lies behind the row; here the row ends.)
+CS_HD int window_byte(const uint8_t* p, int n, int nchars, int chpos) {
+  if (chpos <= 0) return 0;
+  if (chpos >= nchars) return n;
+  if (nchars == n) return chpos;
+  int off = 0;
+  for (int i = 0; chpos > 0 && i < n; ++i) {
+    const unsigned w = lead_width(p[i]);
+    off += (int)w;
+    chpos -= w != 0;
+  }
+  return off < n ? off : n;
+}
+// a row of continuation bytes alone has no character: the reference's window over it is [0, 0) (custring_view.inl:486-495)
+CS_HD bool no_chars_before(const uint8_t* p, int n, int m) {
+  return is_cont(p[0]) && count_chars(p, m) == 0 && count_chars(p + m, n - m) == 0;
+}
 CS_HD int row_find(const uint8_t* p, int n, const uint8_t* needle, int nb, int start, int end) {
   if (nb == 0) return -1;  // an empty needle never matches
   if (start < 0) start = 0;
   // the reference turns (start,end) into a count: end - start, negative = rest
-  int lo = byte_of_char(p, n, start);
-  int hi = n;
-  if (end - start >= 0) hi = skip_chars(p, n, lo, end - start);
+  const int count = end - start;
+  int lo = 0, hi = n;
+  if (start > 0 || count >= 0) {
+    const int nchars = count_chars(p, n);
+    const int last = (count >= 0 && start <= nchars && count < nchars - start) ? start + count : nchars;
+    lo = window_byte(p, n, nchars, start);
+    hi = window_byte(p, n, nchars, last);
+  }
   int m = find_bytes(p, lo, hi, needle, nb);
-  return m < 0 ? -1 : count_chars(p, m);
+  if (m < 0 || no_chars_before(p, n, m)) return -1;
+  return count_chars(p, m);
+}
+// contains(str) by bytes: the reference's find over the whole row (find.cu:237-272), so nothing in a row without a character
+CS_HD bool row_contains(const uint8_t* p, int n, const uint8_t* needle, int nb) {
+  if (nb == 0) return false;
+  const int m = find_bytes(p, 0, n, needle, nb);
+  return m >= 0 && !no_chars_before(p, n, m);
 }
 
 // ---- the rest of the find family (find.cu:36-72, 123-236, 276-387; custring_view.inl:434-442, 481-515, 550-582, 1673-1703) ----
@@ -296,14 +328,22 @@ CS_HD void row_strip(const uint8_t* p, int n, const CharSet& set, int side, int&
     }
   }
   if (side != 1) {
-    while (hi > lo) {
-      int q = hi - 1;
-      while (q > lo && is_cont(p[q])) --q;
+    // The reference steps back to the byte in front that is no continuation byte and takes the WIDTH of the member it
+    // decodes there off the row's end (custring_view.inl:1426-1437, 1560-1571), a step for every character at the most: on a
+    // well-formed row the walk and the end move together; stray continuation bytes behind a member are walked over but stay
+    // counted as kept, and a walk that meets the stripped left end takes the row (lead + trail > size: :1439).
+    int q = n;
+    for (;;) {
+      int k = q - 1;
+      while (k >= 0 && is_cont(p[k])) --k;
+      if (k < 0) break;
       Char ch;
-      decode_at(p, q, n, ch);
+      const unsigned w = decode_at(p, k, n, ch);
       if (!in_set(set, ch)) break;
-      hi = q;
+      q = k;
+      hi -= (int)w;
     }
+    if (hi < lo) lo = hi = n;
   }
 }
 

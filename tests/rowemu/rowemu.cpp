@@ -198,7 +198,7 @@ int64_t emu_contains(const emu_col* c, const char* str, uint8_t* out) {
   int nb = (int)strlen(str);
   int64_t n = 0;
   for (int64_t r = 0; r < c->rows; ++r) {
-    out[r] = c->ok(r) && nb > 0 && find_bytes(c->row(r), 0, c->len(r), (const uint8_t*)str, nb) >= 0;
+    out[r] = c->ok(r) && row_contains(c->row(r), c->len(r), (const uint8_t*)str, nb);
     n += out[r];
   }
   return n;

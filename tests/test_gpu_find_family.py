@@ -80,10 +80,12 @@ def untouched(res):
     return bool(np.all(res.view(np.uint8) == FILL))
 
 
-def check(op, expect, n, *args, on_device=False, what=None):
+def check(op, expect, n, *args, on_device=False, what=None, route=None):
     expect = np.asarray(expect, dtype=DTYPE[op])
     st, res, count = call(op, n, *args, on_device=on_device)
     assert st == 0, (op, what)
+    if route is not None:
+        assert gpuutil.lib().lib.cs_debug_last_route().decode() == route, (op, what)
     assert np.array_equal(res[:n], expect), (op, what)
     assert count == int(np.count_nonzero(COUNTED[op](expect))), (op, what, "count")
     if n == 0:
@@ -126,6 +128,14 @@ def check_find_from(o, g, s, sub, bounds_on_device):
               what=(sub, a is None, e is None, bounds_on_device))
 
 
+def route_of(n, needle, rowwise):
+    """the route find / contains must report on the rows of BLOCK (every tile of them fits the staging buffer): the tile
+    kernel takes needles of up to 64 bytes, the empty one too; no rows: the entry returns before it takes one"""
+    if n == 0:
+        return None
+    return "rows" if rowwise or len(needle) > 64 else "tile"
+
+
 @pytest.mark.parametrize("rowwise", [False, True], ids=["default", "rowwise"])
 @pytest.mark.parametrize("n", SIZES)
 def test_find_and_contains_on_both_routes(oracle_engine, monkeypatch, n, rowwise):
@@ -135,9 +145,10 @@ def test_find_and_contains_on_both_routes(oracle_engine, monkeypatch, n, rowwise
     g = device(s)
     for sub in NEEDLES:
         b = sub.encode("utf8")
+        route = route_of(n, b, rowwise)
         for st, en in BOUNDS:
-            check("find", oracle_engine.find(s, sub, st, en)[0], n, g.m_cptr, b, st, en, what=(sub, st, en))
-        check("contains", oracle_engine.contains(s, sub)[0], n, g.m_cptr, b, what=sub)
+            check("find", oracle_engine.find(s, sub, st, en)[0], n, g.m_cptr, b, st, en, what=(sub, st, en), route=route)
+        check("contains", oracle_engine.contains(s, sub)[0], n, g.m_cptr, b, what=sub, route=route)
 
 
 @pytest.mark.parametrize("n", SIZES)
@@ -170,8 +181,9 @@ def test_results_and_bounds_in_device_memory(oracle_engine, monkeypatch):
             monkeypatch.setenv("CS_FIND_ROWWISE", "1")
         for sub in ("ab", "é", NEEDLE65):
             b = sub.encode("utf8")
-            check("find", o.find(s, sub, 1, 40)[0], n, g.m_cptr, b, 1, 40, on_device=True, what=(sub, rowwise))
-            check("contains", o.contains(s, sub)[0], n, g.m_cptr, b, on_device=True, what=(sub, rowwise))
+            route = route_of(n, b, rowwise)
+            check("find", o.find(s, sub, 1, 40)[0], n, g.m_cptr, b, 1, 40, on_device=True, what=(sub, rowwise), route=route)
+            check("contains", o.contains(s, sub)[0], n, g.m_cptr, b, on_device=True, what=(sub, rowwise), route=route)
     for sub in ("ab", "", "😀"):
         check_needle_ops(o, g, s, sub, on_device=True)
         check_find_from(o, g, s, sub, True)

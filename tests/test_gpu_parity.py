@@ -1146,6 +1146,9 @@ def test_gpu_tile_kernels_on_arbitrary_bytes(monkeypatch):
     g = gpuutil.from_col(col)
     L = gpuutil.lib()
 
+    route = lambda: L.lib.cs_debug_last_route().decode()  # noqa: E731
+    routes = {}
+
     def snapshot():
         out = {}
         out["replace"] = gpuutil.to_col(g.replace(IPV4, "<IP>"))
@@ -1157,6 +1160,7 @@ def test_gpu_tile_kernels_on_arbitrary_bytes(monkeypatch):
         out["tok"] = gpuutil.to_col(nvtext.tokenize(g))
         out["tok2"] = gpuutil.to_col(nvtext.tokenize(g, " ."))
         out["strip"] = gpuutil.to_col(g.strip())
+        routes["strip"] = route()
         re = gpuutil.compile_re(IPV4)
         out["contains"] = gpuutil.bools(g, "cs_contains_re", re)
         cnt = np.zeros(rows, dtype=np.int32)
@@ -1166,13 +1170,16 @@ def test_gpu_tile_kernels_on_arbitrary_bytes(monkeypatch):
         f = np.zeros(rows, dtype=np.int32)
         L.check(L.lib.cs_find(g.m_cptr, b"3.4", 0, -1, f.ctypes.data, 0, None, C.byref(found)))
         out["find"] = (f, found.value)
+        routes["find"] = route()
         return out
 
     fast = snapshot()
+    assert routes == {"strip": "tile", "find": "tile"}  # (the tile kernels answered, not their row-wise stand-ins)
     for var in ("CS_REGEX_TWO_PASS", "CS_REGEX_ROWWISE", "CS_SPLIT_GENERIC", "CS_TOKENIZE_ROWWISE", "CS_STRIP_ROWWISE",
                 "CS_FIND_ROWWISE", "CS_REPLACE_ROWWISE"):
         monkeypatch.setenv(var, "1")
     slow = snapshot()
+    assert routes == {"strip": "rows", "find": "rows"}
     for k in fast:
         a, b = fast[k], slow[k]
         if isinstance(a, list):
