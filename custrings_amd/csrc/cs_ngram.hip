@@ -8,7 +8,8 @@
 // input offsets of the tile sit in LDS relative to its first token, every lane assembles M
 // n-grams in the LDS output tile -- tokens as funnel-shifted dwords OR-ed into a zeroed
 // buffer (up to 16 bytes at once), separators the same way -- and the tile is flushed with
-// 16-byte stores.  Output offsets leave as coalesced 8-byte stores.
+// 16-byte stores.  Output offsets leave as coalesced 8-byte stores.  cs_ngrams notes the route:
+// "tile-m8" / "tile-m4" / "tile-m2" / "tile-m1" by the M launched, "rows" for everything else.
 #include <hip/hip_runtime.h>
 
 #include "cs_internal.h"
@@ -307,6 +308,7 @@ bool ngrams_fast(const cs_column* tokens, int n, const unsigned char* sep, int s
   CS_HIP(hipMemcpyAsync(h, err->p, sizeof(unsigned), hipMemcpyDeviceToHost, s));
   CS_HIP(hipStreamSynchronize(s));
   if (*h) return false;
+  note_route(M == 8 ? "tile-m8" : M == 4 ? "tile-m4" : M == 2 ? "tile-m2" : "tile-m1");
   *out = c.release();
   return true;
 }

@@ -362,10 +362,8 @@ __global__ void k_split_write(ColView in, SplitArgs a, const int32_t* __restrict
 }
 
 // ---- tokenize --------------------------------------------------------------------------------
-struct TokArgs {
-  CharSet set;
-  int use_set;  // 0 = whitespace
-};
+// (row_tok_walk, row_ops.h: the reference's walk over characters; cs_text.hip's counters keep row_ws_tokens / row_set_tokens)
+using TokArgs = TokDelims;
 __global__ void k_tok_count(ColView in, TokArgs a, int32_t* __restrict__ counts,
                             int64_t* __restrict__ block_sums) {
   int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -373,8 +371,7 @@ __global__ void k_tok_count(ColView in, TokArgs a, int32_t* __restrict__ counts,
   if (r < in.rows && row_is_valid(in.validity, r)) {
     int64_t b = in.offsets[r];
     int n = (int)(in.offsets[r + 1] - b);
-    if (a.use_set) c = row_set_tokens(in.chars + b, n, a.set, [](int, int, int) {});
-    else c = row_ws_count(in.chars + b, n);
+    c = row_tok_walk(in.chars + b, n, a, [](int, int, int) {});
   }
   if (r < in.rows) counts[r] = c;
   long long t = block_reduce_sum(c);
@@ -400,8 +397,7 @@ __global__ void k_tok_emit(ColView in, TokArgs a, const int64_t* __restrict__ to
       for (int i = lo; i < hi; ++i) *o++ = p[i];
     }
   };
-  if (a.use_set) row_set_tokens(p, n, a.set, emit);
-  else row_ws_tokens(p, n, 0, emit);
+  row_tok_walk(p, n, a, emit);
 }
 
 // ---- ngrams -----------------------------------------------------------------------------------
@@ -859,6 +855,7 @@ int cs_tokenize(const cs_column* col, const char* delimiter, cs_stream stream, c
     require_device();
     hipStream_t s = S(stream);
     const int64_t rows = col->rows;
+    note_route("rows");  // (tokenize_fast notes "tile" / "tile-segs" when it answers)
     if (rows == 0) {
       *out = make_all_null(0, s);
       return;
@@ -872,6 +869,7 @@ int cs_tokenize(const cs_column* col, const char* delimiter, cs_stream stream, c
     a.use_set = delimiter != nullptr;
     Buf set_more;
     a.set = make_charset(delimiter ? delimiter : "", set_more, s);
+    tokdelims_finish(a, reinterpret_cast<const uint8_t*>(delimiter ? delimiter : ""), delimiter ? (int)strlen(delimiter) : 0);
     const unsigned nb = blocks_for(rows);
     Buf counts = dev_alloc(sizeof(int32_t) * rows, s);
     Buf sums = dev_alloc(sizeof(int64_t) * nb, s);
@@ -913,6 +911,7 @@ int cs_ngrams(const cs_column* tokens, unsigned ngrams, const char* separator, c
     if (ngrams == 0) ngrams = 2;
     if (!separator) separator = "";
     const int64_t rows = tokens->rows;
+    note_route("rows");  // (ngrams_fast notes "tile-m8" .. "tile-m1" when it answers)
     if (rows == 0) {
       *out = share_column(tokens, s);
       return;

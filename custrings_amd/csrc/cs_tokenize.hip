@@ -13,7 +13,10 @@
 //           through LDS as 16-bit tile-relative positions and leave as 8-byte offsets.
 // Waves are persistent with contiguous tile runs and the next tile's chars in flight
 // (tile_utils.h).  Delimiters: whitespace (<= ' ') or up to four ASCII bytes; other delimiter
-// sets (multi-byte characters) keep the per-row kernels in cs_ops.hip.
+// sets (multi-byte characters) keep the per-row kernels in cs_ops.hip, and so does a column with
+// a row that is not well-formed UTF-8: the reference walks CHARACTERS there (row_tok_walk,
+// row_ops.h), which equals this per-byte walk only where every lead byte has its continuation
+// bytes.  cs_tokenize notes the route: "tile", "tile-segs" (SEGS) or "rows".
 #include <hip/hip_runtime.h>
 
 #include "cs_internal.h"
@@ -38,7 +41,7 @@ struct TokTileArgs {
   // pass 0
   int32_t* tile_bytes;   // [ntiles]
   int32_t* tile_tokens;  // [ntiles]
-  int* maxima;           // [0] most kept bytes in a tile, [1] most tokens in a tile, [2] malformed UTF-8 seen (set mode)
+  int* maxima;           // [0] most kept bytes in a tile, [1] most tokens in a tile, [2] malformed UTF-8 seen
   // pass 1
   const int64_t* byte_base;  // [ntiles + 1]
   const int64_t* tok_base;   // [ntiles + 1]
@@ -108,7 +111,7 @@ __global__ void __launch_bounds__(256) k_tok_tile(TokTileArgs a) {
     const bool has_next = walk.advance();
     long long tile_b = 0, tile_t = 0;  // kept bytes / tokens of the segments before this one
     uint32_t carry_keep = 0;           // was the last byte of the previous chunk row kept?
-    uint32_t carry_expect = 0;         // continuation bytes announced into the next chunk row (set mode check)
+    uint32_t carry_expect = 0;         // continuation bytes announced into the next chunk row (pass 0's check)
     for (int seg = 0; seg < (nseg > 0 ? nseg : 1); ++seg) {
       const long long seg_lo = (long long)seg * kSeg;
       const int want = (int)(want64 - seg_lo < kSeg ? want64 - seg_lo : kSeg);  // staged bytes of this segment
@@ -145,11 +148,12 @@ __global__ void __launch_bounds__(256) k_tok_tile(TokTileArgs a) {
           if (lane == 0) prev = carry_keep;
           const uint32_t before = ((keep << 1) | prev) & 0xFFFFu;  // bit b = byte b - 1 was kept
           const uint32_t starts = keep & (rs | ~before) & 0xFFFFu;
-          if (PASS == 0 && a.ndel > 0) {
-            // Delimiter SETS are matched per character by the row-wise routine (row_ops.h), which
-            // swallows the bytes a lead byte announces; that equals this per-byte classification only
-            // on well-formed UTF-8.  Check it: the continuation bytes must sit exactly where the lead
-            // bytes announce them, inside the lead's own row and inside the tile.
+          if (PASS == 0) {
+            // The row-wise routine (row_tok_walk, row_ops.h) walks characters as the reference does: it
+            // swallows the bytes a lead byte announces and stands still on a stray continuation byte;
+            // that equals this per-byte classification only on well-formed UTF-8, with whitespace as
+            // with a set.  Check it: the continuation bytes must sit exactly where the lead bytes
+            // announce them, inside the lead's own row and inside the tile.
             const uint32_t high = bit16_of(q.v[j], 7) & valid;
             uint32_t cont = 0, expect = 0;
             if (__any(high != 0)) {
@@ -264,7 +268,7 @@ bool tokenize_fast(const cs_column* col, const unsigned char* delims, int ndel, 
   int* hmax = (int*)pinned_scratch(4 * sizeof(int));
   CS_HIP(hipMemcpyAsync(hmax, maxima->p, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
   CS_HIP(hipStreamSynchronize(s));
-  if (hmax[2]) return false;  // malformed UTF-8 with a delimiter set: the row-wise routine defines the result
+  if (hmax[2]) return false;  // malformed UTF-8: the row-wise routine defines the result
   const int64_t nbytes = totals[0], ntok = totals[1];
   auto c = std::make_unique<cs_column>();
   c->rows = ntok;
@@ -275,6 +279,7 @@ bool tokenize_fast(const cs_column* col, const unsigned char* delims, int ndel, 
   c->chars = dev_alloc((size_t)nbytes, s);
   if (ntok == 0) {
     CS_HIP(hipMemsetAsync(c->offsets->p, 0, sizeof(int64_t), s));
+    note_route(segs ? "tile-segs" : "tile");
     *out = c.release();
     return true;
   }
@@ -293,6 +298,7 @@ bool tokenize_fast(const cs_column* col, const unsigned char* delims, int ndel, 
   // closing offset
   CS_HIP(hipMemcpyAsync(ptr<int64_t>(c->offsets) + ntok, &totals[0], sizeof(int64_t), hipMemcpyHostToDevice, s));
   CS_HIP(hipStreamSynchronize(s));
+  note_route(segs ? "tile-segs" : "tile");
   *out = c.release();
   return true;
 }

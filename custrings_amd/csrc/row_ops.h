@@ -543,4 +543,84 @@ CS_HD int row_set_tokens(const uint8_t* p, int n, const CharSet& set, Emit&& emi
   return k;
 }
 
+// ---- NVText::tokenize: the reference's walk of one row (tokens.cu:41-121) -------------------------
+// The delimiters of tokenize(): whitespace (use_set 0: a character <= ' '), or the characters of the
+// delimiter string.  The reference looks a character up with custring_view::find(Char), which decodes
+// the delimiter string at EVERY byte offset: a continuation byte of a member is found too, so a stray
+// byte 10xxxxxx of a row is a delimiter when a member holds the same byte (`cont`: one bit a byte
+// 0x80..0xBF); the character 0 is never found.
+struct TokDelims {
+  CharSet set;
+  int use_set;    // 0 = whitespace
+  uint64_t cont;  // the continuation bytes of the set's members
+};
+CS_HD void tokdelims_finish(TokDelims& d, const uint8_t* delim, int nb) {  // (d.set, d.use_set are the caller's)
+  d.cont = 0;
+  for (int i = 0; i < nb; ++i)
+    if (is_cont(delim[i])) d.cont |= 1ull << (delim[i] - 0x80u);
+}
+CS_HD bool is_tok_delim(const TokDelims& d, Char ch) {
+  if (!d.use_set) return ch <= 0x20u;
+  if (ch == 0) return false;
+  if (ch - 0x80u < 64u) return ((d.cont >> (ch - 0x80u)) & 1u) != 0;
+  return in_set(d.set, ch);
+}
+// emit(k, lo, hi) for the row's tokens in order; returns their number.  On well-formed UTF-8 this is
+// the walk over bytes of row_ws_tokens / row_set_tokens.  On other rows the reference's own steps
+// decide, and they are restated here:
+//   * the row has as many characters as it has bytes that are no continuation bytes (chars_count);
+//   * the iterator stands at a byte offset and moves on by the width THE BYTE UNDER IT announces
+//     (custring_view.inl:361): over bytes that are no continuation bytes when a lead byte announced
+//     them, and not at all from a stray continuation byte, which it then reads once for every
+//     character the row has left;
+//   * a token's character positions become byte offsets by the sum of the widths that the row's first
+//     k lead bytes announce (byte_offset_for, :261; position k of a row with as many characters as
+//     bytes is byte k, a position at or beyond the row's characters is the row's size).
+// Where the reference reads behind the row its result is undefined; here the byte at the row's size and
+// every byte behind it reads as 0 (the reference has its terminator there), a token ends at the row's
+// end at the latest, and a token that would begin there is dropped.
+template <class Emit>
+CS_HD int row_tok_walk(const uint8_t* p, int n, const TokDelims& d, Emit&& emit) {
+  int nch = 0;
+  for (int i = 0; i < n; ++i) nch += !is_cont(p[i]);
+  int scan = 0, seen = 0, sum = 0;  // byte_offset_for, asked with rising positions: one pass over the row
+  auto byte_of = [&](int k) {
+    if (k >= nch) return n;
+    if (nch == n) return k;
+    while (seen < k) {
+      const unsigned w = lead_width(p[scan++]);
+      if (w) sum += (int)w, ++seen;
+    }
+    return sum < n ? sum : n;
+  };
+  int spos = 0, epos = nch, off = 0, cpos = 0, k = 0;
+  bool spaces = true;
+  while (spos < nch) {
+    for (; cpos != nch; ++cpos) {
+      Char ch = 0;
+      unsigned w = 1;
+      if (off < n) w = decode_at(p, off, n, ch);  // (a continuation byte: itself, width 0)
+      if (spaces == is_tok_delim(d, ch)) {
+        if (spaces) spos = cpos + 1;
+        else epos = cpos + 1;
+      } else {
+        spaces = !spaces;
+        if (spaces) {
+          epos = cpos;
+          break;
+        }
+      }
+      off += (int)w;
+    }
+    if (!(spos < epos)) break;
+    const int lo = byte_of(spos), hi = byte_of(epos);
+    if (lo < hi) emit(k++, lo, hi);
+    spos = epos + 1;
+    epos = nch;
+    off += off < n ? (int)lead_width(p[off]) : 1;  // (the reference's ++itr behind a token)
+    ++cpos;
+  }
+  return k;
+}
+
 }  // namespace csrow

@@ -1021,12 +1021,17 @@ orc_col* orc_tokenize(const orc_col* c, const char* delim) {
     if (!c->is_valid(r)) continue;
     View v = make_view(*c, r);
     int nchars = (int)v.nchars, spos = 0, epos = nchars, pos = 0;
+    // the iterator (custring_view.inl:348-392): a byte offset that moves on by the width the byte under it announces -- not at
+    // all from a continuation byte.  On well-formed rows that is byte_pos(v, pos); on others the source decides.
+    unsigned off = 0;
+    auto step = [&] { off += off < v.bytes ? lead_width(v.d[off]) : 1; };
     bool spaces = true;
     for (;;) {
       // next_token
       if (spos >= nchars) break;
-      for (; pos < nchars; ++pos) {
-        Char ch = char_at(v, (unsigned)pos);
+      for (; pos < nchars; ++pos, step()) {
+        Char ch;
+        decode(v.d + off, v.d + v.bytes, ch);
         bool isd = delim ? find_char(dv, ch) >= 0 : (ch <= ' ');
         if (spaces == isd) {
           if (spaces) spos = pos + 1;
@@ -1045,6 +1050,7 @@ orc_col* orc_tokenize(const orc_col* c, const char* delim) {
       spos = epos + 1;
       epos = nchars;
       ++pos;
+      step();
     }
   }
   return b.finish();

@@ -43,6 +43,15 @@ def assert_same(g, ocol, what=""):
     assert np.array_equal(got.chars, ocol.chars), what + ": chars differ"
 
 
+def same_tokens(got, want, what):
+    """two flat columns (tokens, n-grams) byte for byte; names the first row that differs"""
+    assert np.array_equal(got.bitmask(), want.bitmask()), what + ("validity",)
+    if not (got.rows == want.rows and np.array_equal(got.offsets, want.offsets) and np.array_equal(got.chars, want.chars)):
+        a, b = got.to_bytes_list(), want.to_bytes_list()
+        bad = next((i for i in range(min(len(a), len(b))) if a[i] != b[i]), min(len(a), len(b)))
+        raise AssertionError(what + ("row", bad, "of", len(a), len(b), "got", a[bad:bad + 2], "want", b[bad:bad + 2]))
+
+
 def bools(g, fn_name, pat_or_re):
     L = lib()
     rows = g.size()

@@ -656,7 +656,10 @@ int emu_findall(const emu_col* c, const emu_regex* re, emu_col*** cols_out) {
 
 // ---- tokenize ----
 emu_col* emu_tokenize(const emu_col* c, const char* delim) {
-  CharSet set = make_set(delim ? delim : "");
+  TokDelims td;
+  td.set = make_set(delim ? delim : "");
+  td.use_set = delim != nullptr;
+  tokdelims_finish(td, (const uint8_t*)(delim ? delim : ""), delim ? (int)strlen(delim) : 0);
   std::vector<int64_t> src;
   std::vector<int> lo, hi;
   for (int64_t r = 0; r < c->rows; ++r) {
@@ -666,10 +669,7 @@ emu_col* emu_tokenize(const emu_col* c, const char* delim) {
       lo.push_back(a);
       hi.push_back(b);
     };
-    if (delim)
-      row_set_tokens(c->row(r), c->len(r), set, emit);
-    else
-      row_ws_tokens(c->row(r), c->len(r), 0, emit);
+    row_tok_walk(c->row(r), c->len(r), td, emit);
   }
   return two_pass(
       (int64_t)src.size(), [&](int64_t t) { return hi[t] - lo[t]; },

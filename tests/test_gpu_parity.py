@@ -601,8 +601,11 @@ def test_gpu_tokenize_tile_kernels(gpu_engine, oracle_engine, shape):
                 t += rnd.choice(words) + rnd.choice([" ", "  ", "\n", "_", "-", " \t "])
             s.append(t[: max(target, 1)])
     o, g = oracle_engine, gpu_engine
+    route = lambda: gpuutil.lib().lib.cs_debug_last_route().decode()  # noqa: E731
     for d in (None, " ", "_-", " _-\n", "é ", "abcde"):
         assert g.tokenize(s, d) == o.tokenize(s, d), (shape, d)
+        # (16 rows of 500 to 900 bytes fit no tile size: 64-row tiles in segments; a non-ASCII member or five delimiters: row-wise)
+        assert route() == ("rows" if d in ("é ", "abcde") else "tile-segs" if shape == "huge" else "tile"), (shape, d, route())
 
 
 @pytest.mark.parametrize("count", [3, 64, 65, 700, 9000])
@@ -613,13 +616,17 @@ def test_gpu_ngrams_tile_kernel(gpu_engine, oracle_engine, count):
     rnd = random.Random(count)
     toks = ["".join(rnd.choice("abcdé😀xyz") for _ in range(rnd.choice([1, 2, 3, 5, 8, 15, 16, 17, 33]))) for _ in range(count)]
     o, g = oracle_engine, gpu_engine
+    route = lambda: gpuutil.lib().lib.cs_debug_last_route().decode()  # noqa: E731
     for N in (2, 3, 5):
         for sep in ("_", "", " - ", "12345678", "123456789"):
             assert g.ngrams(toks, N, sep) == o.ngrams(toks, N, sep), (count, N, sep)
+            if len(sep) == 9:
+                assert route() == "rows", (count, N)
     holes = list(toks)
     for i in range(0, count, 7):
         holes[i] = None if i % 2 else ""
     assert g.ngrams(holes, 2, "_") == o.ngrams(holes, 2, "_")
+    assert route() == "rows"
 
 
 @pytest.mark.parametrize("rlen", [17, 21, 33, 64, 65, 200])
@@ -1158,7 +1165,9 @@ def test_gpu_tile_kernels_on_arbitrary_bytes(monkeypatch):
         out["split2"] = [gpuutil.to_col(c) for c in g.split(".", 2)]
         from custrings_amd import nvtext
         out["tok"] = gpuutil.to_col(nvtext.tokenize(g))
+        routes["tok"] = route()
         out["tok2"] = gpuutil.to_col(nvtext.tokenize(g, " ."))
+        routes["tok2"] = route()
         out["strip"] = gpuutil.to_col(g.strip())
         routes["strip"] = route()
         re = gpuutil.compile_re(IPV4)
@@ -1174,12 +1183,14 @@ def test_gpu_tile_kernels_on_arbitrary_bytes(monkeypatch):
         return out
 
     fast = snapshot()
-    assert routes == {"strip": "tile", "find": "tile"}  # (the tile kernels answered, not their row-wise stand-ins)
+    # (the tile kernels answered, not their row-wise stand-ins -- but tokenize: its pass 0 finds rows that are not well-formed
+    # UTF-8 and leaves the column to the walk over characters)
+    assert routes == {"strip": "tile", "find": "tile", "tok": "rows", "tok2": "rows"}
     for var in ("CS_REGEX_TWO_PASS", "CS_REGEX_ROWWISE", "CS_SPLIT_GENERIC", "CS_TOKENIZE_ROWWISE", "CS_STRIP_ROWWISE",
                 "CS_FIND_ROWWISE", "CS_REPLACE_ROWWISE"):
         monkeypatch.setenv(var, "1")
     slow = snapshot()
-    assert routes == {"strip": "rows", "find": "rows"}
+    assert routes == {"strip": "rows", "find": "rows", "tok": "rows", "tok2": "rows"}
     for k in fast:
         a, b = fast[k], slow[k]
         if isinstance(a, list):
