@@ -235,6 +235,13 @@ _PROTOS = {
     "cs_ngrams": (i32, [vp, C.c_uint, cp, vp, P(vp)]),
     "cs_minhash": (i32, [vp, i32, C.c_uint32, vp, vp, i32, vp, i32, vp]),
     "cs_minhash_bands": (i32, [vp, i64, i32, i32, vp, i32, vp]),
+    "cs_wordpiece_vocab_create": (i32, [vp, cp, cp, vp, P(vp)]),
+    "cs_wordpiece_vocab_destroy": (None, [vp]),
+    "cs_wordpiece_vocab_info": (i32, [vp, P(i64), P(i32), P(i32)]),
+    "cs_wordpiece_vocab_find": (i32, [vp, cp, i64, P(i32), vp]),
+    "cs_wordpiece_count": (i32, [vp, vp, i32, i32, vp, i32, vp, P(i64)]),
+    "cs_wordpiece_ids": (i32, [vp, vp, i32, i32, vp, vp, i32, vp]),
+    "cs_wordpiece_encode": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp]),
     "cs_synth_column": (i32, [i32, i64, i64, u64, i64, vp, P(vp)]),
     "cs_column_digest": (i32, [vp, vp, P(u64)]),
     "cs_prof_reset": (i32, []),

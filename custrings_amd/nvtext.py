@@ -5,9 +5,12 @@ import numpy as np
 
 from . import nvstrings as _nvs
 from ._lib import lib, check, b
+from .wordpiece import vocabulary as wordpiece_vocabulary, tokenize as wordpiece_tokenize, encode as wordpiece_encode  # noqa: F401
 
 __all__ = ["tokenize", "ngrams", "unique_tokens", "token_count", "tokens_counts", "replace_tokens", "normalize_spaces",
            "contains_strings", "strings_counts", "edit_distance", "scatter_count", "porter_stemmer_measure"]
+# (wordpiece_vocabulary / wordpiece_tokenize / wordpiece_encode, imported above from wordpiece.py, are not in __all__: that
+# list is the reference module's functions, which tests/test_gpu_metadata.py holds against its table of string producers)
 
 
 def tokenize(strs, delimiter=None):

@@ -764,6 +764,39 @@ int cs_minhash(const cs_column* col, int width, uint32_t seed, const uint32_t* a
  * CS_ERR_RANGE.  rows == 0 or a NULL `keys` writes nothing. */
 int cs_minhash_bands(const uint32_t* signatures, int64_t rows, int nperm, int bands, int64_t* keys, int on_device, cs_stream stream);
 
+/* ---- WordPiece: a column of text to the int32 ids of a vocabulary (no reference member; the definition and the per-word
+ * logic are custrings_amd/csrc/wordpiece_ops.h; kernels cs_wordpiece.hip) ------------------------------------------------
+ * The vocabulary is a strings column whose row index is the id: null and empty rows are no entry, among equal rows the
+ * lowest index wins.  A row's words are its maximal runs of bytes > 0x20; with `punct` every ASCII punctuation byte is a
+ * word of its own.  A word of more than max_word_chars characters is the id of `unk`; any other word is cut greedily,
+ * longest match first, into entries -- behind the word's front: entries that start with `prefix`, matched without it --,
+ * and is the id of `unk` alone when some piece has no match.  A null row has no ids.  A character starts at every byte
+ * that is no continuation byte. */
+typedef struct cs_wordpiece_vocab cs_wordpiece_vocab;
+/* The vocabulary's hash table on the device; the handle does not refer to `vocab` afterwards.  prefix NULL = "##", unk NULL =
+ * "[UNK]".  A null `vocab` / `out`, a prefix of no or more than 8 bytes, or an `unk` that is no entry: CS_ERR_INVALID_ARG;
+ * more than 2^24 rows or an entry of more than 255 bytes: CS_ERR_RANGE.  *out = NULL when anything fails. */
+int cs_wordpiece_vocab_create(const cs_column* vocab, const char* prefix, const char* unk, cs_stream stream, cs_wordpiece_vocab** out);
+void cs_wordpiece_vocab_destroy(cs_wordpiece_vocab* v);
+/* the distinct entries, the id of `unk` and the longest entry's bytes (any of the three may be NULL) */
+int cs_wordpiece_vocab_info(const cs_wordpiece_vocab* v, int64_t* entries, int32_t* unk_id, int32_t* max_entry_bytes);
+/* *id = the id of the entry token[0, nbytes), -1 when it is none */
+int cs_wordpiece_vocab_find(const cs_wordpiece_vocab* v, const char* token, int64_t nbytes, int32_t* id, cs_stream stream);
+/* size pass: offsets[rows + 1] (the exclusive scan of the rows' id counts; device memory when on_device) and the total.
+ * 1 <= max_word_chars <= 1024, else CS_ERR_RANGE (all three calls). */
+int cs_wordpiece_count(const cs_column* col, const cs_wordpiece_vocab* v, int max_word_chars, int punct, int64_t* offsets, int on_device, cs_stream stream,
+                       int64_t* total);
+/* write pass: ids[total] at the offsets cs_wordpiece_count gave (`offsets` and `ids` are both device memory when on_device).
+ * A row writes inside its own offsets only.  A NULL `ids` or a column of no rows writes nothing. */
+int cs_wordpiece_ids(const cs_column* col, const cs_wordpiece_vocab* v, int max_word_chars, int punct, const int64_t* offsets, int32_t* ids, int on_device,
+                     cs_stream stream);
+/* model input in one pass: rows x max_length ids and a rows x max_length mask (1 = token, 0 = padding; may be NULL).  A
+ * negative cls_id / sep_id means "none".  A row's ids are cut to max_length minus the specials present, cls_id goes in
+ * front of them, sep_id behind, then pad_id; a null row is the specials and padding.  max_length < 1 or less than the
+ * specials present: CS_ERR_INVALID_ARG. */
+int cs_wordpiece_encode(const cs_column* col, const cs_wordpiece_vocab* v, int max_word_chars, int punct, int max_length, int32_t cls_id, int32_t sep_id,
+                        int32_t pad_id, int32_t* ids, uint8_t* mask, int on_device, cs_stream stream);
+
 /* ---- the URL codec, translate and fillna (reference: cpp/src/strings/urlencode.cu, modify.cu:302-489; per-row logic in
  * custrings_amd/csrc/recode_ops.h; kernels cs_recode.hip) --------------------------------------------------------
  * url_encode, url_decode and translate keep null rows null (the output shares the input's validity); an output row of

@@ -61,7 +61,7 @@ def report(config, op, rows, in_bytes, alg_bytes, dt):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scale", type=float, default=1.0, help="row-count multiplier (1.0 = BASELINE.json single-GPU sizes)")
-    ap.add_argument("--only", default="C2,C3,C4,C5", help="comma-separated configs to run (CONV: the conversion ops, TS: the timestamp ones, PAD: substring / padding / wrapping, CHR: character types and swapcase / capitalize / title, TXT: the NVText matches, edit distance, stemmer measure and scatter_count, URL: url_encode / url_decode / translate / fillna, NUM: the numeric categories -- from_numbers, to_numbers, merge_and_remap -- beside two yardsticks, CSV: from_csv -- the line-start kernels, the field locator and the whole call, STATS: compute_statistics / get_info -- the fused pass beside the separate ops, the histogram layouts, the whole call, MINHASH: minhash on short and long rows at nperm 1 / 64 / 256 and the band keys, SPLITRE: split_re at three patterns with its steps' kernel times beside split and findall)")
+    ap.add_argument("--only", default="C2,C3,C4,C5", help="comma-separated configs to run (CONV: the conversion ops, TS: the timestamp ones, PAD: substring / padding / wrapping, CHR: character types and swapcase / capitalize / title, TXT: the NVText matches, edit distance, stemmer measure and scatter_count, URL: url_encode / url_decode / translate / fillna, NUM: the numeric categories -- from_numbers, to_numbers, merge_and_remap -- beside two yardsticks, CSV: from_csv -- the line-start kernels, the field locator and the whole call, STATS: compute_statistics / get_info -- the fused pass beside the separate ops, the histogram layouts, the whole call, MINHASH: minhash on short and long rows at nperm 1 / 64 / 256 and the band keys, SPLITRE: split_re at three patterns with its steps' kernel times beside split and findall, WP: WordPiece tokenize and encode on short and long rows under a 30 000-entry and a 300-entry vocabulary)")
     a = ap.parse_args()
     only = set(a.only.split(","))
     ov = 8.125  # native offset + validity bytes per row
@@ -96,6 +96,8 @@ def main():
         run_minhash(a)
     if "SPLITRE" in only:
         run_splitre(a)
+    if "WP" in only:
+        run_wordpiece(a)
 
 
 def run_splitre(a):
@@ -131,6 +133,67 @@ def run_splitre(a):
                     line[kern.decode() + "_ms"] = round(ms.value / reps, 3)
                 line["token_spans_share"] = round(line["k_token_spans_ms"] / (dt * 1e3), 4)
             print(json.dumps(line), flush=True)
+        del col
+
+
+def run_wordpiece(a):
+    """WordPiece (cs_wordpiece_*): tokenize (count + write, into device memory) and encode at max_length 128 with cls / sep, with
+    punct, on the C3 log-line column and the C5 column at 2M rows (x --scale) and a generated column of 20 000 rows of ~4 KB,
+    under a generated vocabulary of 30 000 entries and the 300-entry one of the tests -- the whole call's ms, ids per second,
+    the share of unk among them, the form that ran, and the input read rate beside the box's read-only stream rate."""
+    import numpy as np
+
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import wordpiece_model as wm
+    from custrings_amd import wordpiece
+
+    rates = (C.c_double * 6)()
+    _lib.check(L.cs_box_rates(2048, 3, None, rates))
+    print(json.dumps({"config": "WP box", "read_GBps": round(rates[1] * 1e3, 1)}), flush=True)
+    rows = int(2_000_000 * a.scale)
+    long_rows = max(int(20_000 * a.scale), 64)
+    rng = np.random.default_rng(SEED)
+    lens = rng.integers(3600, 4600, size=long_rows)
+    offs = np.zeros(long_rows + 1, dtype=np.int64)
+    np.cumsum(lens, out=offs[1:])
+    text = rng.integers(97, 123, size=int(offs[-1]), dtype=np.uint8)
+    text[rng.integers(0, 6, size=text.size) == 0] = 32
+    # 30 000 entries: the specials, every printable ASCII byte whole and as a continuation, runs of 2..4 of a-z0-9 either way
+    big = ["[UNK]", "[CLS]", "[SEP]", "[PAD]"] + [chr(c) for c in range(33, 127)] + ["##" + chr(c) for c in range(33, 127)]
+    seen = set(big)
+    letters = "abcdefghijklmnopqrstuvwxyz0123456789"
+    while len(big) < 30000:
+        run = "".join(letters[i] for i in rng.integers(0, 26 if rng.integers(0, 4) else 36, size=int(rng.integers(2, 5))))
+        e = run if rng.integers(0, 2) else "##" + run
+        if e not in seen:
+            seen.add(e)
+            big.append(e)
+    vocabs = [("30000", wordpiece.vocabulary(nvstrings.to_device(big))),
+              ("300", wordpiece.vocabulary(nvstrings.to_device([e.decode() for e in wm.make_vocab(300, 11)])))]
+    cols = [("C3", lambda: synth(3, rows)), ("C5", lambda: synth(5, rows)), ("4KB", lambda: nvstrings.from_offsets64(text, offs, long_rows, None))]
+    for name, make in cols:
+        col = make()
+        n, nb = col.size(), nbytes(col)
+        for vname, v in vocabs:
+            d_offs = torch.empty(n + 1, dtype=torch.int64, device="cuda")
+            total = C.c_int64()
+            _lib.check(L.cs_wordpiece_count(col.m_cptr, v.m_cptr, 100, 1, d_offs.data_ptr(), 1, None, C.byref(total)))
+            d_ids = torch.empty(max(total.value, 1), dtype=torch.int32, device="cuda")
+            enc = torch.empty((n, 128), dtype=torch.int32, device="cuda")
+            mask = torch.empty((n, 128), dtype=torch.uint8, device="cuda")
+            calls = [("tokenize", lambda: wordpiece.tokenize(col, v, punct=True, devptrs=(d_ids, d_offs)), total.value),
+                     ("encode 128", lambda: wordpiece.encode(col, v, 128, cls="[CLS]", sep="[SEP]", pad="[PAD]", punct=True, devptrs=(enc, mask)), None)]
+            for op, fn, ids in calls:
+                dt = timed(fn, reps=3)
+                if ids is None:
+                    ids = int(mask.sum(dtype=torch.int64).item())
+                line = {"config": "WP %s vocab %s" % (name, vname), "op": op, "route": L.cs_debug_last_route().decode(), "rows": n, "bytes": nb,
+                        "ids": ids, "ms": round(dt * 1e3, 3), "ids_per_s": round(ids / dt, 0), "input_GBps": round((nb + 8.125 * n) / dt / 1e9, 1),
+                        "frac_of_box_read_rate": round((nb + 8.125 * n) / dt / (rates[1] * 1e12), 4)}
+                if op == "tokenize":
+                    line["unk_share"] = round(float((d_ids[:total.value] == v.unk_id).float().mean().item()), 4) if total.value else 0.0
+                print(json.dumps(line), flush=True)
+            del d_offs, d_ids, enc, mask
         del col
 
 
